@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train impressions/sec of the UserModel hot path on synthetic EBNeRD-shaped batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3-large]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3-large] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is the reference's train.py:66-75 on one batch: forward -> loss -> backward -> [one gradient
@@ -9,7 +9,19 @@ all-reduce when N > 1] -> Adam(lr 1e-3, weight_decay 1e-5) -> zero_grad, train-m
 resident in HBM as fp32.  Every rank holds its own batch of B impressions (weak scaling: global batch
 N*B, BASELINE config 4 at N=8).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, ...).  Everything
+else it can measure or check runs only with --full, after the timed steps or before the warm-up.
+
+--dump-outputs DIR: what the timed path returns to its caller (train: loss, logits; --mode infer: scores, live)
+for fixed inputs, as DIR/<name>.npy (float32 / float64); a tensor of more than DUMP_SAMPLE elements is a fixed
+seeded sample of it.  The kernels reduce with atomic adds, so every step is reproducible only to rounding, and
+training steps compound that: the weights after the timed steps differ from run to run by more than rounding.
+So after all timed work the model and the optimizer are put back to their seeded initial state and the timed
+path (the same eager step or captured graph) runs TWO more steps, on resident batches 0 and 1.  The second
+step is dumped: its forward runs on the weights the first step's backward and Adam update produced, so the
+whole step reaches the files.  Two runs, or two builds, with the same arguments then agree to rounding.
+
+Extra objects on the line with --full:
   roofline      the dominant HIP kernel (largest summed time in the timed region): algorithmic FLOPs per
                 launch (2*B*T*H*D^2, the contraction only) / its mean launch duration measured
                 with HIP events on the launch stream, against the dense fp32 MFMA peak of gfx950.  Inside the timed
@@ -45,13 +57,21 @@ PMC_TRAFFIC_FILES = {("C3-large", "f32"): "r5_c3_pmc_traffic.json", ("C5-long", 
                      ("C2-small", "bf16x3"): "r5_c2_bf16x3_pmc_traffic.json", ("C1-demo", "f32"): "r5_c1_pmc_traffic.json",
                      ("ref-default", "f32"): "r5_refdefault_pmc_traffic.json"}
 INFER_TRAFFIC_FILES = {("C3-large", "f32"): "r5_infer_c3_pmc_traffic.json"}
+DUMP_SAMPLE = 1 << 20           # --dump-outputs: elements kept of a larger tensor (logits of a --batch override)
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the per-kernel table and roofline (extra "
+                         "one-stream steps before the warm-up), the eager-vs-hipGraph launch probe after the timed steps, the "
+                         "forward parity against a reference fixture and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--workload", default="C3-large")
     ap.add_argument("--mode", default="train", choices=["train", "infer"],
                     help="train (default): the headline metric, one step = reference train.py:66-75.  infer: the OTHER caller of "
@@ -73,7 +93,7 @@ def parse():
     ap.add_argument("--batches", type=int, default=4,
                     help="resident synthetic batches per rank the steps cycle through (all in HBM before the timed region starts)")
     ap.add_argument("--probe-steps", type=int, default=10, help="steps per launch mode in the eager-vs-hipGraph probe (>= 10)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the probe of both launch modes that follows the timed region")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the probe of both launch modes that follows the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="(default since round 3) no HIP event pairs inside the timed region: the per-kernel durations and the "
@@ -91,7 +111,49 @@ def parse():
                          "same figure to the whole run, terminates, then kills, the rank processes and names the ranks that hung")
     ap.add_argument("--cpu-batch", type=int, default=None)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.timed_kernel_events:
+        args.full = True                        # its events feed the kernel table, which only --full reports
+    return args
+
+
+def snapshot_outputs(named):
+    """Host copies (float32 / float64) of ``named`` {name: tensor}.  A tensor of more than DUMP_SAMPLE elements keeps a fixed
+    seeded sample (the same indices for the same size in every run)."""
+    out = {}
+    for name, t in named.items():
+        a = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed {DUMP_LIMIT_BYTES}")
+    return out
+
+
+def write_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def save_train_state(model):
+    """Device copies of the model's state_dict (parameters and BatchNorm buffers) before the first step."""
+    return {k: v.clone() for k, v in model.state_dict().items()}
+
+
+def restore_train_state(model, opt, saved):
+    """Model and FlatAdam back to ``saved`` and a fresh optimizer, in place: the parameters are views of opt.flat_param and a
+    captured step reads these very buffers.  The cached packed weight images are refreshed from the restored weights."""
+    from news_recommendation_model_amd import ops
+    for k, v in model.state_dict().items():
+        v.copy_(saved[k])
+    for t in (opt.exp_avg, opt.exp_avg_sq, opt.state, opt.flat_grad):
+        t.zero_()
+    ops.repack_persistent(opt.params)
 
 
 def host_cores():
@@ -459,14 +521,15 @@ def main_infer(args):
     for _ in range(max(args.warmup, 2)):
         scores, live = evaluation.predict(models, tb)
     torch.cuda.synchronize()
-    native.kernel_events = []
     inv = model.invariant_interest_model
-    inv.two_streams = False                             # kernel table: untimed, bracketed, every kernel alone on the chip
-    for _ in range(3):
-        evaluation.predict(models, tb)
-    torch.cuda.synchronize()
-    inv.two_streams = None
-    events, native.kernel_events = native.kernel_events, None
+    if args.full:
+        native.kernel_events = []
+        inv.two_streams = False                         # kernel table: untimed, bracketed, every kernel alone on the chip
+        for _ in range(3):
+            evaluation.predict(models, tb)
+        torch.cuda.synchronize()
+        inv.two_streams = None
+        events, native.kernel_events = native.kernel_events, None
     for _ in range(2):
         scores, live = run(tb)                          # (graph mode: capture happens here, outside the timed region)
     torch.cuda.synchronize()
@@ -476,6 +539,25 @@ def main_infer(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     _ops.check_index_errors(dev)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, snapshot_outputs({"scores": scores, "live": live}))
+    ms = elapsed / args.steps * 1e3
+    line = {"metric": "inference impressions/sec (reference test.py:31-74 model_test, one model)", "value": round(B * args.steps / elapsed, 2),
+            "unit": "impressions/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 2), "ms_per_step": round(ms, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": args.workload, "mode": "infer", "batch": B, "hist": H, "candidates": T, "emb": D, "launch": "hipGraph replay (evaluation.GraphedPredict)" if args.graph else "eager",
+                       "attention_streams": 2 if inv.uses_two_streams(B * T * H * D) else 1,
+                       "kernel_durations_from": "3 extra one-stream batches after the warm-up" if args.full else None,
+                       "step": "evaluation.predict: trim + eval-mode forward (no saved z) + softmax + de-padding softmax"}}
+    if args.full:
+        line.update(infer_kernel_fields(args, events, B, H, T, D))
+        if not args.no_cpu_baseline:
+            line["cpu_baseline"] = infer_cpu_baseline(dims, wl, args.cpu_seconds, args.cpu_batch)
+    print(json.dumps(line), flush=True)
+
+
+def infer_kernel_fields(args, events, B, H, T, D):
+    """--mode infer --full: roofline of the forward kernel and the per-kernel table of the 3 bracketed batches."""
     per = {}
     for tag, e0, e1 in events:
         per.setdefault(tag, []).append(e0.elapsed_time(e1))
@@ -497,20 +579,89 @@ def main_infer(args):
         else:
             roof["traffic"] = prof.get("nrm_pwattn_fwd", {}).get("corrected_bytes")
             roof["traffic_source"] = f"{os.path.basename(tpath)} (rocprofv3 --pmc, commit {prof.get('git_head', '?')}, same kernel sources)"
-    ms = elapsed / args.steps * 1e3
-    line = {"metric": "inference impressions/sec (reference test.py:31-74 model_test, one model)", "value": round(B * args.steps / elapsed, 2),
-            "unit": "impressions/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 2), "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": args.workload, "mode": "infer", "batch": B, "hist": H, "candidates": T, "emb": D, "launch": "hipGraph replay (evaluation.GraphedPredict)" if args.graph else "eager",
-                       "attention_streams": 2 if inv.uses_two_streams(B * T * H * D) else 1,
-                       "kernel_durations_from": "3 extra one-stream batches after the warm-up",
-                       "step": "evaluation.predict: trim + eval-mode forward (no saved z) + softmax + de-padding softmax"},
-            "roofline": roof,
+    return {"roofline": roof,
             "kernels": {k: {"launches": v["launches"], "mean_ms": round(v["mean_ms"], 4)} for k, v in kern.items()},
             "gpu_kernel_ms_per_step": round(sum(v["mean_ms"] * v["launches"] for v in kern.values()) / 3, 4)}
-    if not args.no_cpu_baseline:
-        line["cpu_baseline"] = infer_cpu_baseline(dims, wl, args.cpu_seconds, args.cpu_batch)
-    print(json.dumps(line), flush=True)
+
+
+def train_kernel_fields(args, events, flop_meter, ms, B, H, T, D):
+    """--full: the per-kernel table of the bracketed steps, the roofline of the dominant kernel (with the HBM traffic of the
+    committed PMC profile) and the whole-step matrix-FLOP roofline."""
+    # per-kernel launch durations from the event pairs recorded on the launch stream
+    per = {}
+    for tag, e0, e1 in events:
+        per.setdefault(tag, []).append(e0.elapsed_time(e1))
+    kern = {k: {"launches": len(v), "mean_ms": float(np.mean(v)), "total_ms": float(np.sum(v))} for k, v in per.items()}
+    heavy = {k: v for k, v in kern.items() if k in HEAVY[:5]}      # the fp32 contraction kernels
+    dom = max(heavy, key=lambda k: heavy[k]["total_ms"])
+    flops_per_launch = 2.0 * B * T * H * D * D            # both attentions have width D in BASELINE shapes
+    achieved = flops_per_launch / (heavy[dom]["mean_ms"] * 1e-3) / 1e12
+    peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
+    roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4), "flops_per_launch": flops_per_launch, "mean_launch_ms": round(heavy[dom]["mean_ms"], 4)}
+    if args.dtype != "f32":
+        # With bf16 matrix cores no attention kernel is bound by the algorithmic FLOPs any more: price the kernel with the largest
+        # summed time against BOTH roofs and report the larger fraction --
+        #   hbm:  algorithmic bytes (one pass over z / dz [B,T,H,D] fp32; two for the in-place dz pass) / t against 8 TB/s (spec; the
+        #         guide measures 6.3 TB/s achievable: `frac_of_achievable_hbm`);
+        #   mfma: ISSUED matrix-core FLOPs / t against the dense bf16 peak -- bf16x3 issues three MFMAs per product, so its matrix
+        #         pipe does 3x the algorithmic 2 B T H D^2 (`mfma_frac_algorithmic` is the 1x figure).
+        allheavy = {k: v for k, v in kern.items() if k in HEAVY}
+        dom = max(allheavy, key=lambda k: allheavy[k]["total_ms"])
+        zbytes = 4.0 * B * T * H * D
+        bytes_per_launch = 2 * zbytes if dom == "nrm_pwattn_bwd_dz" else zbytes
+        t_s = allheavy[dom]["mean_ms"] * 1e-3
+        issue = 3.0 if args.dtype == "bf16x3" else 1.0
+        f_alg = 0.0 if dom == "nrm_pwattn_bwd_dz" else flops_per_launch / t_s / 1e12 / BF16_MFMA_PEAK_TFLOPS
+        f_mfma = issue * f_alg
+        f_hbm = bytes_per_launch / t_s / 1e9 / HBM_PEAK_GBS
+        both = {"hbm_frac": round(f_hbm, 4), "frac_of_achievable_hbm": round(bytes_per_launch / t_s / 1e9 / 6300.0, 4),
+                "mfma_frac_issued": round(f_mfma, 4), "mfma_frac_algorithmic": round(f_alg, 4),
+                "bytes_per_launch": bytes_per_launch, "flops_per_launch": flops_per_launch, "issued_flops_per_launch": issue * flops_per_launch,
+                "mean_launch_ms": round(allheavy[dom]["mean_ms"], 4),
+                "all_heavy_kernels": {k: {"mean_ms": round(v["mean_ms"], 4),
+                                          "hbm_frac": round((2 if k == "nrm_pwattn_bwd_dz" else 1) * zbytes / (v["mean_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                          "mfma_frac_issued": 0.0 if k == "nrm_pwattn_bwd_dz" else round(issue * flops_per_launch / (v["mean_ms"] * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)}
+                                      for k, v in allheavy.items()}}
+        if f_hbm >= f_mfma:
+            roof = dict({"bound": "hbm", "kernel": dom, "achieved": round(bytes_per_launch / t_s / 1e9, 1), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(f_hbm, 4)}, **both)
+        else:
+            roof = dict({"bound": "mfma", "kernel": dom, "achieved": round(issue * flops_per_launch / t_s / 1e12, 2), "peak": BF16_MFMA_PEAK_TFLOPS,
+                         "unit": "TFLOP/s", "frac": round(f_mfma, 4)}, **both)
+
+    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; the figure comes from
+    # the committed rocprofv3 --pmc passes of this same command (profiles/<round>_<workload>_pmc_traffic.json, written by
+    # scripts/pmc_summary.py, which stamps the digest of the kernel sources it measured).  A profile of other sources
+    # is stale: traffic is then null and the note says so.
+    traffic, traffic_note = None, "no committed PMC profile for this workload"
+    from news_recommendation_model_amd import build as _build
+    tpath = os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILES.get((args.workload, args.dtype), ""))
+    if not args.batch and os.path.isfile(tpath):
+        try:
+            prof = json.load(open(tpath))
+            if prof.get("kernel_sources_sha256") != _build.sources_digest():
+                traffic_note = f"stale: {os.path.basename(tpath)} was measured on other kernel sources (commit {prof.get('git_head', '?')})"
+            else:
+                traffic = prof.get(dom, {}).get("corrected_bytes")
+                traffic_note = f"{os.path.basename(tpath)} (rocprofv3 --pmc, commit {prof.get('git_head', '?')}, same kernel sources)"
+        except Exception as e:
+            traffic_note = "unreadable profile: " + repr(e)
+
+    # whole-step roofline: the matrix FLOPs one step ISSUES on the MFMA pipe (attention contractions + every dense GEMM incl.
+    # side projections and weight gradients; algorithmic 2MNK, no tile padding; x3 for the bf16x3 split) / ms_per_step / peak
+    issue = 3.0 if args.dtype == "bf16x3" else 1.0
+    step_roof = None
+    if flop_meter is not None:
+        mf = issue * (flop_meter["dense"] + flop_meter["contraction"])
+        step_roof = {"matrix_flops_per_step": mf, "contraction_flops": issue * flop_meter["contraction"],
+                     "dense_flops": issue * flop_meter["dense"], "contraction_launches": flop_meter["contraction_launches"],
+                     "gemm_launches": flop_meter["dense_launches"], "issue_factor": issue, "peak": peak, "unit": "TFLOP/s",
+                     "achieved": round(mf / (ms * 1e-3) / 1e12, 2), "frac": round(mf / (ms * 1e-3) / 1e12 / peak, 4),
+                     "ms_at_peak": round(mf / (peak * 1e12) * 1e3, 3)}
+    roof["step"] = step_roof
+    return {"roofline": dict(roof, traffic=traffic, traffic_source=traffic_note),
+            "kernels": {k: {"launches": v["launches"], "mean_ms": round(v["mean_ms"], 4)} for k, v in kern.items()}}
 
 
 def main():
@@ -590,6 +741,7 @@ def main():
     sd = synth.make_state_dict(dims, seed=1, user_num=user_num, perturb=False)
     model = trainer.build_model(dims, user_num, sd, device=dev, attention_mma=args.dtype).train()
     opt = trainer.FlatAdam(model)              # Adam(lr 1e-3, wd 1e-5) + zero_grad as one launch; flat grad buffer
+    initial_state = save_train_state(model) if args.dump_outputs else None
     reducer = None                             # the all-reduce runs on opt.flat_grad (no gather copy)
     NB = max(1, args.batches)
     tbs = [trainer.batch_to_device(synth.make_batch(dims, B, H, T, seed=rank * NB + i, user_num=user_num, dtype=np.float32), dev)
@@ -653,33 +805,35 @@ def main():
     else:
         os.environ["NRM_WGRAD_STREAM"] = "0"           # event-timed kernels must own the machine
     if args.graph or args.no_kernel_timing:
-        # per-kernel durations cannot be event-timed inside a graph, and a kernel that shares the chip with a kernel of another
-        # stream cannot be priced against a roofline: take them from 3 eager ONE-STREAM steps first (no second attention stream,
-        # no weight-gradient stream); the first of them also runs under the matrix-FLOP meter (roofline.step)
-        beat("kernel table steps")
-        inv.two_streams = False
-        prev_wg = os.environ.get("NRM_WGRAD_STREAM")
-        os.environ["NRM_WGRAD_STREAM"] = "0"
-        for _ in range(2):
-            eager_step()
-        sync()
-        native.kernel_events = []
-        if use_dist:
-            opt.collective_events = []                 # an event pair around the step's one all-reduce (eager steps only)
-        for k_ in range(3):
-            if k_ == 0:
-                _ops.flop_meter_start()
-            loss, _ = eager_step()
-            if k_ == 0:
-                flop_meter = _ops.flop_meter_stop()
-        sync()
-        events, native.kernel_events = native.kernel_events, None
-        table_collective_events, opt.collective_events = opt.collective_events, None
-        inv.two_streams = None
-        if prev_wg is None:
-            del os.environ["NRM_WGRAD_STREAM"]
-        else:
-            os.environ["NRM_WGRAD_STREAM"] = prev_wg
+        table_collective_events = None
+        if args.full:
+            # per-kernel durations cannot be event-timed inside a graph, and a kernel that shares the chip with a kernel of another
+            # stream cannot be priced against a roofline: take them from 3 eager ONE-STREAM steps first (no second attention stream,
+            # no weight-gradient stream); the first of them also runs under the matrix-FLOP meter (roofline.step)
+            beat("kernel table steps")
+            inv.two_streams = False
+            prev_wg = os.environ.get("NRM_WGRAD_STREAM")
+            os.environ["NRM_WGRAD_STREAM"] = "0"
+            for _ in range(2):
+                eager_step()
+            sync()
+            native.kernel_events = []
+            if use_dist:
+                opt.collective_events = []                 # an event pair around the step's one all-reduce (eager steps only)
+            for k_ in range(3):
+                if k_ == 0:
+                    _ops.flop_meter_start()
+                loss, _ = eager_step()
+                if k_ == 0:
+                    flop_meter = _ops.flop_meter_stop()
+            sync()
+            events, native.kernel_events = native.kernel_events, None
+            table_collective_events, opt.collective_events = opt.collective_events, None
+            inv.two_streams = None
+            if prev_wg is None:
+                del os.environ["NRM_WGRAD_STREAM"]
+            else:
+                os.environ["NRM_WGRAD_STREAM"] = prev_wg
         # Launch mode of the timed region (launch_policy): --graph / --eager force it; one process without a process group times
         # BOTH over PROBE >= 10 steps in the same state of the box and takes the captured step when a step is launch-bound
         # (< 10 ms) or the replay is at least 1 % faster; with a process group the step is eager unless --graph asks otherwise.
@@ -729,7 +883,7 @@ def main():
         sync()
         elapsed = time.perf_counter() - t0
         steps_done = counter["i"]
-        if mode == "rule" and not args.no_probe:
+        if mode == "rule" and args.full and not args.no_probe:
             # both launch modes over PROBE steps each, in the state the timed region left the chip in: information, not a decision
             beat("launch probe (after the timed region)")
             if graphs or try_capture():
@@ -809,82 +963,24 @@ def main():
         pcie = {"value": round(B * args.steps / el, 2), "unit": "impressions/s", "ms_per_step": round(el / args.steps * 1e3, 3),
                 "host_dtype": "f64", "bytes_per_step": nbytes, "overlap": "pinned host batch, copy stream, one batch ahead"}
 
-    # per-kernel launch durations from the event pairs recorded on the launch stream
-    per = {}
-    for tag, e0, e1 in events:
-        per.setdefault(tag, []).append(e0.elapsed_time(e1))
-    kern = {k: {"launches": len(v), "mean_ms": float(np.mean(v)), "total_ms": float(np.sum(v))} for k, v in per.items()}
-    heavy = {k: v for k, v in kern.items() if k in HEAVY[:5]}      # the fp32 contraction kernels
-    dom = max(heavy, key=lambda k: heavy[k]["total_ms"])
-    flops_per_launch = 2.0 * B * T * H * D * D            # both attentions have width D in BASELINE shapes
-    achieved = flops_per_launch / (heavy[dom]["mean_ms"] * 1e-3) / 1e12
-    peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
-    roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-            "frac": round(achieved / peak, 4), "flops_per_launch": flops_per_launch, "mean_launch_ms": round(heavy[dom]["mean_ms"], 4)}
-    if args.dtype != "f32":
-        # With bf16 matrix cores no attention kernel is bound by the algorithmic FLOPs any more: price the kernel with the largest
-        # summed time against BOTH roofs and report the larger fraction --
-        #   hbm:  algorithmic bytes (one pass over z / dz [B,T,H,D] fp32; two for the in-place dz pass) / t against 8 TB/s (spec; the
-        #         guide measures 6.3 TB/s achievable: `frac_of_achievable_hbm`);
-        #   mfma: ISSUED matrix-core FLOPs / t against the dense bf16 peak -- bf16x3 issues three MFMAs per product, so its matrix
-        #         pipe does 3x the algorithmic 2 B T H D^2 (`mfma_frac_algorithmic` is the 1x figure).
-        allheavy = {k: v for k, v in kern.items() if k in HEAVY}
-        dom = max(allheavy, key=lambda k: allheavy[k]["total_ms"])
-        zbytes = 4.0 * B * T * H * D
-        bytes_per_launch = 2 * zbytes if dom == "nrm_pwattn_bwd_dz" else zbytes
-        t_s = allheavy[dom]["mean_ms"] * 1e-3
-        issue = 3.0 if args.dtype == "bf16x3" else 1.0
-        f_alg = 0.0 if dom == "nrm_pwattn_bwd_dz" else flops_per_launch / t_s / 1e12 / BF16_MFMA_PEAK_TFLOPS
-        f_mfma = issue * f_alg
-        f_hbm = bytes_per_launch / t_s / 1e9 / HBM_PEAK_GBS
-        both = {"hbm_frac": round(f_hbm, 4), "frac_of_achievable_hbm": round(bytes_per_launch / t_s / 1e9 / 6300.0, 4),
-                "mfma_frac_issued": round(f_mfma, 4), "mfma_frac_algorithmic": round(f_alg, 4),
-                "bytes_per_launch": bytes_per_launch, "flops_per_launch": flops_per_launch, "issued_flops_per_launch": issue * flops_per_launch,
-                "mean_launch_ms": round(allheavy[dom]["mean_ms"], 4),
-                "all_heavy_kernels": {k: {"mean_ms": round(v["mean_ms"], 4),
-                                          "hbm_frac": round((2 if k == "nrm_pwattn_bwd_dz" else 1) * zbytes / (v["mean_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                          "mfma_frac_issued": 0.0 if k == "nrm_pwattn_bwd_dz" else round(issue * flops_per_launch / (v["mean_ms"] * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)}
-                                      for k, v in allheavy.items()}}
-        if f_hbm >= f_mfma:
-            roof = dict({"bound": "hbm", "kernel": dom, "achieved": round(bytes_per_launch / t_s / 1e9, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(f_hbm, 4)}, **both)
-        else:
-            roof = dict({"bound": "mfma", "kernel": dom, "achieved": round(issue * flops_per_launch / t_s / 1e12, 2), "peak": BF16_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(f_mfma, 4)}, **both)
-
-    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; the figure comes from
-    # the committed rocprofv3 --pmc passes of this same command (profiles/<round>_<workload>_pmc_traffic.json, written by
-    # scripts/pmc_summary.py, which stamps the digest of the kernel sources it measured).  A profile of other sources
-    # is stale: traffic is then null and the note says so.
-    traffic, traffic_note = None, "no committed PMC profile for this workload"
-    from news_recommendation_model_amd import build as _build
-    tpath = os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILES.get((args.workload, args.dtype), ""))
-    if not args.batch and os.path.isfile(tpath):
-        try:
-            prof = json.load(open(tpath))
-            if prof.get("kernel_sources_sha256") != _build.sources_digest():
-                traffic_note = f"stale: {os.path.basename(tpath)} was measured on other kernel sources (commit {prof.get('git_head', '?')})"
-            else:
-                traffic = prof.get(dom, {}).get("corrected_bytes")
-                traffic_note = f"{os.path.basename(tpath)} (rocprofv3 --pmc, commit {prof.get('git_head', '?')}, same kernel sources)"
-        except Exception as e:
-            traffic_note = "unreadable profile: " + repr(e)
+    loss = float(loss)
+    if args.dump_outputs:
+        # two steps of the timed path from the seeded state, the second one dumped (see the module docstring); the timed
+        # steps' all-reduce events are set aside so that the collective figures do not take these in
+        beat("dump steps")
+        timed_collective_events, opt.collective_events = opt.collective_events, None
+        restore_train_state(model, opt, initial_state)
+        counter["i"] = 0
+        for _ in range(2):
+            dump_loss, dump_out = (graph_step if args.graph else eager_step)()
+        sync()
+        opt.collective_events = timed_collective_events
+        if rank == 0:
+            write_outputs(args.dump_outputs, snapshot_outputs({"loss": dump_loss, "logits": dump_out}))
 
     beat("assembling the line")
     if rank == 0:
         ms = elapsed / args.steps * 1e3
-        # whole-step roofline: the matrix FLOPs one step ISSUES on the MFMA pipe (attention contractions + every dense GEMM incl.
-        # side projections and weight gradients; algorithmic 2MNK, no tile padding; x3 for the bf16x3 split) / ms_per_step / peak
-        issue = 3.0 if args.dtype == "bf16x3" else 1.0
-        step_roof = None
-        if flop_meter is not None:
-            mf = issue * (flop_meter["dense"] + flop_meter["contraction"])
-            step_roof = {"matrix_flops_per_step": mf, "contraction_flops": issue * flop_meter["contraction"],
-                         "dense_flops": issue * flop_meter["dense"], "contraction_launches": flop_meter["contraction_launches"],
-                         "gemm_launches": flop_meter["dense_launches"], "issue_factor": issue, "peak": peak, "unit": "TFLOP/s",
-                         "achieved": round(mf / (ms * 1e-3) / 1e12, 2), "frac": round(mf / (ms * 1e-3) / 1e12 / peak, 4),
-                         "ms_at_peak": round(mf / (peak * 1e12) * 1e3, 3)}
-        roof["step"] = step_roof
         job = job_fields(world, B, args.steps, elapsed, per_rank_ms, opt, use_dist, devices, replicas_in_sync, table_collective_events)
         line = {
             "metric": "train impressions/sec", "value": job["value"],
@@ -897,26 +993,30 @@ def main():
                        "per_gpu_batch": B, "global_batch": world * B, "resident_batches_per_gpu": NB, "hist": H, "candidates": T, "emb": D,
                        "user_num": user_num, "parallelism": f"dp{world}", "attention_streams": 2 if (inv.uses_two_streams(B * T * H * D) and not args.timed_kernel_events) else 1,
                        "weight_gradient_stream": bool(_ops._wgrad["streams"]) and not args.timed_kernel_events,
-                       "kernel_durations_from": "timed region (event pairs on the launch stream)" if args.timed_kernel_events else "3 extra eager one-stream steps after the warm-up", "launch": "hipGraph replay" if args.graph else "eager",
+                       "kernel_durations_from": "timed region (event pairs on the launch stream)" if args.timed_kernel_events else
+                                                "3 extra eager one-stream steps after the warm-up" if args.full else None,
+                       "launch": "hipGraph replay" if args.graph else "eager",
                        "step": "fwd+loss+bwd+allreduce+Adam(wd=1e-5)" if use_dist else "fwd+loss+bwd+Adam(wd=1e-5)"},
             "loss": round(float(loss), 6), "first_step_loss": round(first_step_loss, 6),
-            "loss_note": f"first_step_loss: initial weights, batch 0 (the oracle's value for its sample of the same batch: cpu_baseline."
-                         f"hip_vs_oracle_first_step.oracle_loss); loss: last timed step, after {steps_done} steps cycling {NB} resident batches",
+            "loss_note": f"first_step_loss: initial weights, batch 0 (the oracle's value for its sample of the same batch, with --full: "
+                         f"cpu_baseline.hip_vs_oracle_first_step.oracle_loss); loss: last timed step, after {steps_done} steps cycling {NB} "
+                         "resident batches",
             "launch_probe": probe, "per_rank_ms_per_step": job["per_rank_ms_per_step"],
-            "roofline": dict(roof, traffic=traffic, traffic_source=traffic_note),
-            "kernels": {k: {"launches": v["launches"], "mean_ms": round(v["mean_ms"], 4)} for k, v in kern.items()},
+            **(train_kernel_fields(args, events, flop_meter, ms, B, H, T, D) if args.full else {}),
             "grad_allreduce_bytes": job["grad_allreduce_bytes"], "replicas_in_sync": job["replicas_in_sync"],
             "collective": job["collective"],
         }
         # provenance: which kernel sources the loaded binary says it was built from, next to the sources this run sees
+        from news_recommendation_model_amd import build as _build
         line["build"] = dict(native.provenance(), kernel_sources_sha256=_build.sources_digest())
         line["build"]["match"] = line["build"]["library_sources_sha256"] == line["build"]["kernel_sources_sha256"]
         if pcie is not None:
             line["pcie_inclusive"] = pcie
-        line["fwd_auc_parity"] = fwd_auc_parity(dev, args.dtype, {"C2-small": "c2_small", "C1-demo": "c1_demo", "C5-long": "c5_long",
-                                                                  "ref-default": "refdefault"}.get(args.workload, "c3_large"))
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(dims, wl, args.cpu_seconds, args.cpu_batch, args.dtype)
+        if args.full:
+            line["fwd_auc_parity"] = fwd_auc_parity(dev, args.dtype, {"C2-small": "c2_small", "C1-demo": "c1_demo", "C5-long": "c5_long",
+                                                                      "ref-default": "refdefault"}.get(args.workload, "c3_large"))
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(dims, wl, args.cpu_seconds, args.cpu_batch, args.dtype)
         beat("printing")
         print(json.dumps(line), flush=True)
     if use_dist:

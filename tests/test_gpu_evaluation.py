@@ -331,7 +331,7 @@ def test_bench_inference_mode_prints_the_contract_line(lib, graph):
     import sys
     from conftest import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "infer", "--workload", "ref-test80", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline"] + (["--graph"] if graph else [])
+           "--full", "--no-cpu-baseline"] + (["--graph"] if graph else [])
     pr = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in pr.stdout.decode().splitlines() if ln.startswith("{")]
