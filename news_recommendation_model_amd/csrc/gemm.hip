@@ -159,8 +159,8 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
 #pragma unroll
         for (int jt = 0; jt < MT; ++jt) acc[it][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // Columns >= K of the last chunk are multiplied by the zero padding of the packed weights; what X holds
-    // there only has to be finite (caller guarantee: row padding up to ldx is zero-initialised).
+    // Columns >= K of a ragged last chunk hold the row's padding and then the first columns of the NEXT row (the DMA reads 16
+    // columns at row stride ldx).  The packed weights are zero there, but NaN * 0 = NaN: compute() zeroes those X values.
     auto dma_chunk = [&](int c, float* buf) {
         const int wbase = (c * p.rows + n0) * 64;
         for (int pc = wave; pc < NT; pc += 4)
@@ -181,12 +181,21 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
     // issue no MFMA: 3-4 % of the launch at those widths.  (The zero padding of the last K-chunk cannot be skipped the same way:
     // K-step j of a chunk covers k = 4 q + j over the four lane groups q -- the 16-byte fragment layout -- so at K = 402 every
     // step of the last chunk still holds k = 400 or 401.)
-    auto compute = [&](const float* buf, auto full, int ntv) {
+    // kleft = K - 16 * (chunk index): below 16 only in a ragged last chunk (uniform), where the X values of columns >= K are zeroed
+    auto compute = [&](const float* buf, auto full, int ntv, int kleft) {
         constexpr bool FULL = decltype(full)::value;
         const float* Xl = buf + WROWS * 16;
         f32x4 pf[MT];
 #pragma unroll
         for (int jt = 0; jt < MT; ++jt) pf[jt] = *reinterpret_cast<const f32x4*>(&Xl[((wave * MT + jt) * 16 + r16) * 16 + rslot]);
+        if (kleft < 16) {
+            asm volatile("");                                          // a real (uniform) branch: keeps the select out of the other chunks
+            const int kl = kleft - 4 * q;                                // the fragment holds k = 4 q .. 4 q + 3
+#pragma unroll
+            for (int jt = 0; jt < MT; ++jt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pf[jt][e] = e < kl ? pf[jt][e] : 0.f;
+        }
         f32x4 af = *reinterpret_cast<const f32x4*>(&buf[r16 * 16 + rslot]);
 #pragma unroll
         for (int it = 0; it < NT; ++it) {
@@ -215,8 +224,9 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
             if (KC > 1 && c * KC + k >= p.kchunks) break;
-            if (nt_valid == NT) compute(cur + k * SUB, std::true_type{}, NT);
-            else compute(cur + k * SUB, std::false_type{}, nt_valid);
+            const int kleft = p.K - 16 * (c * KC + k);
+            if (nt_valid == NT) compute(cur + k * SUB, std::true_type{}, NT, kleft);
+            else compute(cur + k * SUB, std::false_type{}, nt_valid, kleft);
         }
         if (!(NRM_DIAG_GEMM & 1)) __syncthreads();
     }
@@ -422,7 +432,7 @@ __global__ __launch_bounds__(256, tn_waves_per_simd(KT, DT)) void gemm_tn_kernel
     const int nsteps = nrows > 0 ? (nrows + 3) >> 2 : 0;
 
     // descriptors start at this wave's first row; rows >= r_hi read 0.  Columns past the matrix edge read
-    // whatever follows in memory (finite) and only feed outputs that are never stored.
+    // whatever follows in memory (any value, NaN included) and only feed outputs (i, j) that are never stored.
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.A) + (size_t)r_lo * p.lda, 0, nrows > 0 ? ((nrows - 1) * p.lda + p.acols) * 4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(

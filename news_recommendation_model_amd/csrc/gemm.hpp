@@ -14,7 +14,7 @@ struct GemmNtParams {
     float* y; int ldy;                    // [M, ldy]
     float* z; int ldz;                    // EPI_GELU: pre-activation out, EPI_DGELU: pre-activation in, EPI_MUL: un-multiplied out
     const float* m; int ldm;              // EPI_MUL: y = (x W^T + bias) * m   (the gate of user_model.py:33)
-    int M, kchunks;
+    int M, K, kchunks;                    // K: reduction width (columns >= K of the last chunk are masked)
 };
 struct GemmNtPlan { int NT, MT, nchunks, rows; };
 GemmNtPlan gemm_nt_plan(int N);

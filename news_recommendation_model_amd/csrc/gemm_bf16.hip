@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const GemmTnParams
     const int nss = nrows > 0 ? (nrows + 31) >> 5 : 0;
 
     // descriptors start at this wave's first row; rows >= r_hi read 0.  Columns past the matrix edge read whatever follows in
-    // memory (finite: padding is zero-initialised) and only feed outputs that are never stored.
+    // memory (any value, NaN included) and only feed outputs (i, j) that are never stored.
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.A) + (size_t)r_lo * p.lda, 0, nrows > 0 ? ((nrows - 1) * p.lda + p.acols) * 4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(RX_WAVES * 64, RT <= 2 ? RX_WAVES / 2 : RX_WAVES / 
                 unsigned short hi[4], lo[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float ve = k + e < p.K ? v[u][e] : 0.f;        // (columns in [K, ldx) are finite padding: drop them)
+                    const float ve = k + e < p.K ? v[u][e] : 0.f;        // (columns in [K, ldx) are padding of any value: drop them)
                     __bf16 h, l;
                     split_bf16(ve, h, l);
                     hi[e] = __builtin_bit_cast(unsigned short, h);

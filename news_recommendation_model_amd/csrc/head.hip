@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void small_linear_relu_fwd_kernel(const XT* __
             v = b ? b[n] : 0.f;
 #pragma unroll
             for (int k = 0; k < SL_KMAX; ++k) if (k < K) v = fmaf(w[n * K + k], xk[k], v);
-            v = fmaxf(v, 0.f);
+            v = v <= 0.f ? 0.f : v;                                      // NaN stays NaN, as in torch.relu (fmaxf would give 0)
         }
         yr[n] = v;                                                       // padding columns are written as 0
     }

@@ -240,7 +240,11 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
             if (c + 1 < KCH) dma_chunk(c + 1, t, nxt);
             else if (more && same_item) dma_chunk(0, t + 1, nxt);         // the ring runs on across steps of one item
             {
-                const f32x4 pf = *reinterpret_cast<const f32x4*>(&cur[(WROWS + wave * 16 + c16) * 16 + rslot]);   // dz[row c16][k = 16c + 4q + j]
+                f32x4 pf = *reinterpret_cast<const f32x4*>(&cur[(WROWS + wave * 16 + c16) * 16 + rslot]);   // dz[row c16][k = 16c + 4q + j]
+                // dz rows are read at stride D: columns >= D of a ragged last chunk are the NEXT row's first columns.  W is zero there,
+                // but a NaN / Inf in that row times 0 is NaN, so they are zeroed (D % 4 == 0: a lane's 4 are all in or out).  The empty asm
+                // keeps this a uniform branch: hipcc would otherwise turn it into selects that every chunk executes.
+                if (D - 16 * c < 16) { asm volatile(""); pf = 4 * q < D - 16 * c ? pf : f32x4{0.f, 0.f, 0.f, 0.f}; }
                 f32x4 af = *reinterpret_cast<const f32x4*>(&cur[c16 * 16 + rslot]);
 #pragma unroll
                 for (int it = 0; it < NT; ++it) {

@@ -171,8 +171,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        // K-chunk c of this N-chunk -> LDS buffer `buf` (asynchronous; completion is tracked by vmcnt).
-        // Columns >= D of the last chunk need no mask: the packed W_p is zero there.
+        // K-chunk c of this N-chunk -> LDS buffer `buf` (asynchronous; completion is tracked by vmcnt).  t and h rows are read at
+        // row stride D, so columns >= D of a ragged last chunk hold the NEXT row's first columns: compute() zeroes them (the
+        // packed W_p is zero there, but a NaN / Inf in the next row times 0 is NaN).
         auto dma_chunk = [&](int c, float* buf) {
             const int wbase = (c * p.rows + nc * WROWS) * 64;             // bytes, uniform
             for (int pc = wave; pc < NT; pc += NW)
@@ -192,7 +193,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
             if (CT && wave == (NT % NW == 0 ? NW - 1 : NT % NW))
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_t, (__attribute__((address_space(3))) void*)(buf + (WROWS + BM) * 16), 16, voff_tc, c * 64, 0, 0);
         };
-        auto compute = [&](const float* buf) {
+        // kleft = D - 16 c: below 16 only in a ragged last chunk (uniform); D % 4 == 0, so a lane's 4 columns 4q .. 4q+3 are all in or all out
+        auto compute = [&](const float* buf, int kleft) {
             const float* Tl = buf + WROWS * 16;
             f32x4 pf[MT];                                    // B operand rows: P[m,:] = t[b,t,:] * h[b,h,:]
 #pragma unroll
@@ -200,6 +202,11 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
                 const int ro = ((wave * MT + jt) * 16 + r16) * 16 + rslot;
                 if (CT) pf[jt] = *reinterpret_cast<const f32x4*>(&Tl[ro]) * *reinterpret_cast<const f32x4*>(&Tl[BM * 16 + tfrag[jt]]);
                 else pf[jt] = *reinterpret_cast<const f32x4*>(&Tl[ro]) * *reinterpret_cast<const f32x4*>(&Tl[BM * 16 + ro]);
+            }
+            if (kleft < 16) {
+                asm volatile("");                            // a real uniform branch, not selects that every chunk executes
+#pragma unroll
+                for (int jt = 0; jt < MT; ++jt) pf[jt] = 4 * q < kleft ? pf[jt] : f32x4{0.f, 0.f, 0.f, 0.f};
             }
             // W fragments are read one tile ahead; the scheduling barrier keeps hipcc from hoisting
             // all NT reads in front of the MFMAs (that costs 4*NT registers).
@@ -227,7 +234,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
             float* cur = smem + (c & 1) * BUF;
             float* nxt = smem + ((c & 1) ^ 1) * BUF;
             if (c + 1 < p.kchunks && !((NRM_DIAG_FWD & 2) && c > 0)) dma_chunk(c + 1, nxt);
-            compute(cur);
+            compute(cur, D - 16 * c);
             __syncthreads();
         }
         if (NRM_PRIO) __builtin_amdgcn_s_setprio(0);

@@ -87,7 +87,8 @@ def _pad4(n):
 
 def _rows(x):
     """A 2-D fp32 view the GEMM kernels can stream: unit column stride, row stride a multiple of 4 floats,
-    16-byte aligned rows.  Anything else is copied once into a zero-padded buffer (padding must be finite)."""
+    16-byte aligned rows.  Anything else is copied once into a zero-padded buffer.  The padding of a view that is passed
+    through may hold anything, NaN included: the kernels never let a column >= the width reach an output."""
     if (x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0
             and x.stride(0) >= x.shape[1] and x.data_ptr() % 16 == 0):
         return x

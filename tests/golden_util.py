@@ -61,6 +61,25 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
+def masked_rel_err(a, b, allow_finite_where_ref_not=False):
+    """Compare a (kernel) with b (reference) when b may hold NaN / Inf.  Returns (problems, err): ``problems`` lists what breaks
+    the finite pattern -- entries non-finite in a where b is finite (always an error), and, unless ``allow_finite_where_ref_not``,
+    entries finite in a where b is not; ``err`` is rel_err on the entries finite in both (0 if there are none)."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    fa, fb = np.isfinite(a), np.isfinite(b)
+    problems = []
+    leak = ~fa & fb
+    if leak.any():
+        problems.append(f"{int(leak.sum())} non-finite where the reference is finite, first at {np.argwhere(leak)[0].tolist()}")
+    extra = fa & ~fb
+    if extra.any() and not allow_finite_where_ref_not:
+        problems.append(f"{int(extra.sum())} finite where the reference is not, first at {np.argwhere(extra)[0].tolist()}")
+    both = fa & fb
+    err = rel_err(a[both], b[both]) if both.any() else 0.0
+    return problems, err
+
+
 # ----------------------------------------------------------------------------------------- instant-interest gradient bound
 II_W, II_B = "instant_interest_model.out_fc.0.weight", "instant_interest_model.out_fc.0.bias"
 II_NOISE = 4e-6     # allowed fp32 noise per unit of the term-magnitude sum below (measured: reference and oracle sit at 1e-7 .. 1.3e-6)
