@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define NRM_ABI_VERSION 6
+#define NRM_ABI_VERSION 7
 #define NRM_OK 0
 #define NRM_EINVAL (-1)   /* bad shape / alignment / null pointer */
 #define NRM_ELAUNCH (-2)  /* HIP launch error */
@@ -287,6 +287,25 @@ int nrm_frontend_cat_grad(const void* x0, int nrows0, int xcols0, const float* d
  * (int32, candidates that count per row, NULL = T).  auc[b] = -1 where a row holds a single class. */
 int nrm_row_auc(const float* score, const float* label, const int* len, int B, int T, float* auc, int* top1,
                 nrm_stream_t stream);
+
+/* ---- scoring tail of a test set (reference test.py:58-70 model_test, :118-126 get_string_of_prediction), one launch:
+ *   p_m = softmax over ALL T columns of model m's logits (padding columns included, as in the reference), out = mean over the
+ *   M models (summed in model order), score = softmax(out[0:n]) on rows with n < T and out otherwise, where
+ *   n = clamp(T - empty[b], 0, T); rank[j] = 1 + #{i < n: score[i] > score[j]} + #{i < j: score[i] == score[j]} -- the 1-based
+ *   position a stable descending sort gives.  Columns j >= n get score 0 and rank 0 (a row with n = 0 is all zeros; ATen's
+ *   softmax of an all-masked row gives NaN there).  live[b] = n.
+ * logits / row_stride / col_stride: HOST arrays of M (1 .. 8) entries: device pointer of each model's [B, T] fp32 logits, its row
+ *   stride and its column stride in floats (col_stride NULL = 1 everywhere; the models' own logits are column 0 of a padded
+ *   [B*T, 4] GEMM output, column stride 4).  The pointers travel to the kernel by value: nothing is stacked or copied.
+ * empty [B] int32 (trailing padding candidates per row after the caller's common trim; NULL = 0 everywhere).
+ * label [B, T] fp32 and metrics [B, 3] fp32 are NULL together.  With y = label > 0.5 over the live columns, metrics[b] =
+ *   (rr, ndcg5, ndcg10): rr = (sum y / rank) / sum y, ndcg_k = (sum over rank <= k of y / log2(1 + rank)) / (sum over
+ *   r = 1 .. min(k, n_pos) of 1 / log2(1 + r)); all three are -1 where the row has no live positive.  (Sums in fp64, stored as fp32.)
+ * score [B, T] fp32, rank [B, T] int32, live [B] int32, all dense.  1 <= T <= nrm_ensemble_rank_max_candidates() (>= 1024); B = 0 is a
+ * no-op.  Rows are independent: a NaN / Inf in one row's logits stays in that row's outputs. */
+int nrm_ensemble_rank_max_candidates(void);
+int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const long* col_stride, int M, const int* empty,
+                      const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 #include "head.hpp"
 #include "pool_loss.hpp"
 #include "frontend.hpp"
+#include "scoring.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -517,6 +518,26 @@ int nrm_row_auc(const float* score, const float* label, const int* len, int B, i
     if (!score || !label || !auc || !top1) return fail(NRM_EINVAL, "nrm_row_auc: null pointer");
     if (B < 0 || T <= 0) return fail(NRM_EINVAL, "nrm_row_auc: B=%d T=%d", B, T);
     return check_hip(nrm::row_auc_launch(score, label, len, B, T, auc, top1, (hipStream_t)stream), "row_auc");
+}
+
+int nrm_ensemble_rank_max_candidates(void) { return nrm::ENSEMBLE_MAX_CANDIDATES; }
+
+int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const long* col_stride, int M, const int* empty,
+                      const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream) {
+    if (!logits || !row_stride || !score || !rank || !live) return fail(NRM_EINVAL, "nrm_ensemble_rank: null pointer");
+    if (M < 1 || M > nrm::ENSEMBLE_MAX_MODELS) return fail(NRM_EINVAL, "nrm_ensemble_rank: M=%d models (1 .. %d)", M, nrm::ENSEMBLE_MAX_MODELS);
+    if (B < 0 || T <= 0) return fail(NRM_EINVAL, "nrm_ensemble_rank: B=%d T=%d", B, T);
+    if (T > nrm::ENSEMBLE_MAX_CANDIDATES)
+        return fail(NRM_EINVAL, "nrm_ensemble_rank: T=%d candidates exceed the cap of %d (nrm_ensemble_rank_max_candidates)", T, nrm::ENSEMBLE_MAX_CANDIDATES);
+    if ((label == nullptr) != (metrics == nullptr)) return fail(NRM_EINVAL, "nrm_ensemble_rank: label and metrics must be given together or both be NULL");
+    nrm::EnsembleLogits lg = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return fail(NRM_EINVAL, "nrm_ensemble_rank: logits[%d] is a null pointer", m);
+        const long cs = col_stride ? col_stride[m] : 1;
+        if (row_stride[m] < 0 || cs < 1) return fail(NRM_EINVAL, "nrm_ensemble_rank: model %d has row stride %ld, column stride %ld (need >= 0, >= 1)", m, row_stride[m], cs);
+        lg.ptr[m] = logits[m]; lg.row_stride[m] = row_stride[m]; lg.col_stride[m] = cs;
+    }
+    return check_hip(nrm::ensemble_rank_launch(lg, M, empty, label, B, T, score, rank, live, metrics, (hipStream_t)stream), "ensemble_rank");
 }
 
 // ------------------------------------------------------------------------------------------- embedding front end

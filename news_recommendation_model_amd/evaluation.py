@@ -8,6 +8,11 @@
                                 (C ABI nrm_row_auc) instead of one sklearn call per row on the host.
   validate(models, batches)     verify.py:19-43 model_validation: [mean AUC, top-1 rate].
   rank_row(scores)              test.py:118-126: 1-based rank of every candidate, highest score first.
+  predict_ranked(models, batch) test.py:58-70 + :118-126 with the whole tail after the forwards -- softmax per model, mean,
+                                second softmax, rank, optionally MRR / nDCG -- as ONE launch (C ABI nrm_ensemble_rank).
+  validate_ranked(models, batches)   validate() plus MRR, nDCG@5, nDCG@10.
+  write_predictions / zip_predictions   test.py:76-132: one "<impression id> [r1,r2,...]" line per impression, zipped.
+  score_dataset(models, head_path, out_dir)   test.py's model_test + write_submission_file over a processed test set.
   save_checkpoint / load_checkpoint   train.py:95-97 (state_dict minus 'delta'), test.py:160 (strict=False).
 """
 from __future__ import annotations
@@ -170,6 +175,138 @@ def rank_row(scores_row):
     for r, i in enumerate(order):
         rank[i] = r + 1
     return rank
+
+
+@torch.no_grad()
+def predict_ranked(models, batch, with_metrics=False):
+    """-> (scores [B, T'] fp32, rank [B, T'] int32, live [B] int32[, metrics [B, 3] fp32 = (rr, ndcg5, ndcg10)]), all on the device.
+
+    predict() with its tail fused: the same host-side trim decision (taken from ``empty_num`` where it lives: a host tensor
+    costs no device synchronisation), the models' eval-mode forwards, then one ``ops.ensemble_rank`` launch that reads every
+    model's logits where the last GEMM left them.  ``rank`` is what ``rank_row`` gives for the row's live scores (1 = highest,
+    ties by index), 0 on padding columns.  Differences from predict(): padding columns of rows that keep their own padding
+    hold score 0 either way, but a row with NO live candidate is all zeros here (NaN there), and ``live`` is int32.
+    ``with_metrics`` needs ``batch["label"]``; rows without a live positive get -1 in all three metrics.
+    Capturable into a graph (``torch.cuda.graph``) when ``empty_num`` answers ``.min()`` on the host, as GraphedPredict's
+    ``_HostMin`` does, and the label (if any) is a float32 device tensor."""
+    xh, xt, xg = batch["x_history"], batch["x_target"], batch["x_global"]
+    ops._require_gpu(xh, xt, xg)
+    e_in = batch["empty_num"]
+    trim = int(e_in.min()) if e_in.numel() else 0             # host decision (it changes T), as in predict()
+    if isinstance(e_in, torch.Tensor) and not e_in.is_cuda:   # a DataLoader's host tensor: subtract and narrow before the one copy
+        empty = (e_in - trim).to(torch.int32).to(xt.device, non_blocking=True)
+    else:
+        empty = e_in.to(xt.device, non_blocking=True)
+        empty = empty - trim if trim > 0 else empty
+    if trim > 0:                                              # test.py:48-56
+        xt, xg = xt[:, :-trim], xg[:, :-trim]
+    logits = [m.eval()(xh, xt, xg) for m in models]           # test.py:58-64; the softmaxes happen inside the kernel
+    label = None
+    if with_metrics:
+        label = batch["label"][:, :xt.shape[1]].to(xt.device, non_blocking=True)
+    scores, rank, live, metrics = ops.ensemble_rank(logits, empty, label)
+    return (scores, rank, live, metrics) if with_metrics else (scores, rank, live)
+
+
+@torch.no_grad()
+def validate_ranked(models, batches):
+    """validate() with the ranking metrics: {"auc", "top1", "mrr", "ndcg5", "ndcg10"}, means over the impressions of an iterable
+    of device batches (with labels).  AUC and top-1 come from ``row_auc`` on predict_ranked's scores; the sums are kept on the
+    device in float64 and read once at the end (one synchronise), where a single-class row raises validate()'s ValueError."""
+    dev = next(models[0].parameters()).device
+    sums = torch.zeros(6, dtype=torch.float64, device=dev)   # auc, top1, rr, ndcg5, ndcg10, rows with a single class
+    n = 0
+    for batch in batches:
+        scores, _rank, live, metrics = predict_ranked(models, batch, with_metrics=True)
+        label = batch["label"][:, :scores.shape[1]].to(scores.device)
+        auc, top1 = row_auc_top1(scores, label, live)
+        per_row = torch.cat([auc[:, None].double(), top1[:, None].double(), metrics.double(), (auc < 0)[:, None].double()], dim=1)
+        sums += per_row.sum(0)
+        n += scores.shape[0]
+    ops.check_index_errors(dev)                               # (the one synchronise; the flag of the MODELS' device)
+    out = sums.tolist()
+    if out[5] > 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    return {k: v / max(n, 1) for k, v in zip(("auc", "top1", "mrr", "ndcg5", "ndcg10"), out)}
+
+
+def prediction_lines(impression_ids, rank, live):
+    """The text of test.py:124-130 for a batch: ``"{int(impression_id)} [{r1},{r2},...]\\n"`` per row with the row's first
+    ``live[b]`` ranks, no spaces.  Host arrays or device tensors; ranks, live counts and ids on a device are gathered into ONE
+    device-to-host copy."""
+    import numpy as np
+    if isinstance(rank, torch.Tensor) and rank.is_cuda:
+        B, T = rank.shape
+        parts = [rank.reshape(-1).to(torch.int64), torch.as_tensor(live).to(rank.device, torch.int64).reshape(-1)]
+        ids_on_device = isinstance(impression_ids, torch.Tensor) and impression_ids.is_cuda
+        if ids_on_device:
+            parts.append(impression_ids.to(torch.int64).reshape(-1))
+        host = torch.cat(parts).cpu().numpy()                 # the one D2H copy
+        rank, live = host[:B * T].reshape(B, T), host[B * T:B * T + B]
+        if ids_on_device:
+            impression_ids = host[B * T + B:]
+    rank = np.asarray(rank.cpu() if isinstance(rank, torch.Tensor) else rank)
+    live = np.asarray(live.cpu() if isinstance(live, torch.Tensor) else live).astype(np.int64).reshape(-1)
+    ids = np.asarray(impression_ids.cpu() if isinstance(impression_ids, torch.Tensor) else impression_ids).reshape(-1)
+    if rank.ndim != 2 or len(live) != rank.shape[0] or len(ids) != rank.shape[0]:
+        raise ValueError(f"prediction_lines: {len(ids)} ids, rank {rank.shape}, {len(live)} live counts do not agree")
+    if len(live) and (live.min() < 0 or live.max() > rank.shape[1]):
+        raise ValueError("prediction_lines: a live count lies outside [0, T]")
+    rows = rank.tolist()
+    return "".join(f"{int(i)} [{','.join(map(str, r[:k]))}]\n" for i, r, k in zip(ids.tolist(), rows, live.tolist()))
+
+
+def write_predictions(path, impression_ids, rank, live, append=False):
+    """test.py:106-110,124-130: write (or append) one line per impression to ``path``; returns the number of lines."""
+    text = prediction_lines(impression_ids, rank, live)
+    with open(path, "a" if append else "w", encoding="utf-8") as f:
+        f.write(text)
+    return text.count("\n")
+
+
+def zip_predictions(txt_path, zip_path):
+    """test.py:113-115: one deflated member named by the text file's base name."""
+    import os
+    import zipfile
+    with zipfile.ZipFile(zip_path, "w", zipfile.ZIP_DEFLATED) as z:
+        z.write(txt_path, arcname=os.path.basename(txt_path))
+    return zip_path
+
+
+def iter_dataset_batches(head_path, batch_size):
+    """Batches of a processed test set in FILE order (DataLoader(shuffle=False), test.py:33), streamed: one subvolume is held
+    at a time, a batch may straddle two of them, the last one may be short."""
+    from . import data_io
+    n_sub, total = data_io.import_processed_data(head_path)[:2]
+    pending, seen = [], 0
+    for rec in data_io._iter_subvolumes(head_path, n_sub):
+        if seen >= total:
+            break
+        pending.append(rec)
+        seen += 1
+        if len(pending) == batch_size:
+            yield data_io.collate(pending)
+            pending = []
+    if pending:
+        yield data_io.collate(pending)
+
+
+def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions"):
+    """test.py's ``model_test`` + ``write_submission_file`` for a processed test set: -> path of ``<out_dir>/<name>.zip`` holding
+    ``predictions.txt``.  Every batch goes through predict_ranked (ranks computed on the device) and write_predictions (one
+    device-to-host copy); nothing but the current batch and subvolume is held."""
+    import os
+    dev = next(models[0].parameters()).device
+    os.makedirs(out_dir, exist_ok=True)
+    txt_path = os.path.join(out_dir, "predictions.txt")
+    open(txt_path, "w").close()
+    for batch in iter_dataset_batches(head_path, batch_size):
+        tb = {k: torch.from_numpy(batch[k]).to(dev, non_blocking=True) for k in ("x_history", "x_target", "x_global")}
+        tb["empty_num"] = torch.from_numpy(batch["empty_num"])         # stays on the host: the trim costs no synchronisation
+        _scores, rank, live = predict_ranked(models, tb)
+        write_predictions(txt_path, batch["impression_id"], rank, live, append=True)
+    ops.check_index_errors(dev)
+    return zip_predictions(txt_path, os.path.join(out_dir, f"{name}.zip"))
 
 
 def save_checkpoint(model, path):

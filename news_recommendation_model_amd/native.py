@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NRM_HOTPATH_LIB") or os.path.join(_HERE, "libnrm_hotpath.so")   # override: diagnostic builds (scripts/_diag)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _c_fp = ctypes.c_void_p      # device pointers travel as integers
 _c_i, _c_l = ctypes.c_int, ctypes.c_long
@@ -62,6 +62,8 @@ SIGNATURES = {
     "nrm_adam_step_dev": (_c_i, [_c_fp] * 4 + [_c_l] + [ctypes.c_float] * 5 + [_c_fp, _c_i, _c_fp]),
     "nrm_gather_flat": (_c_i, [_c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_l, _c_fp]),
     "nrm_row_auc": (_c_i, [_c_fp] * 3 + [_c_i, _c_i] + [_c_fp] * 3),
+    "nrm_ensemble_rank_max_candidates": (_c_i, []),
+    "nrm_ensemble_rank": (_c_i, [_c_fp] * 3 + [_c_i, _c_fp, _c_fp, _c_i, _c_i] + [_c_fp] * 5),      # the first three: HOST arrays
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,
                                  _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp]),

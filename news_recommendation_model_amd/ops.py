@@ -1785,6 +1785,49 @@ row_auc = _op("row_auc", "(Tensor score, Tensor label, Tensor? length) -> (Tenso
                                             score.new_empty((score.shape[0],), dtype=torch.int32)))
 
 
+def _ensemble_rank_impl(logits, empty, label):
+    """The scoring tail of reference test.py:58-70,118-126 in one launch (C ABI nrm_ensemble_rank): softmax per model over all
+    columns, mean over the models, second softmax over the de-padded slice of rows with padding, 1-based rank of every live
+    candidate and -- with labels -- reciprocal rank, nDCG@5, nDCG@10 per row.  fp32 logits are read where they lie, by row and
+    column stride (a column slice of a wider tensor, column 0 of the last GEMM's padded output): nothing is stacked or copied."""
+    import ctypes
+    logits = list(logits)
+    _require_gpu(*logits, empty, label)
+    if not logits or any(x.dim() != 2 or x.shape != logits[0].shape for x in logits):
+        raise RuntimeError(f"ensemble_rank: needs 1 .. 8 logit matrices of one [B, T] shape, got {[tuple(x.shape) for x in logits]}")
+    B, T = logits[0].shape
+    xs = [x if (x.dtype == torch.float32 and (B <= 1 or x.stride(0) >= 0) and (T <= 1 or x.stride(1) >= 1)) else _f32c(x) for x in logits]
+    M, dev = len(xs), xs[0].device
+    score = torch.empty(B, T, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, T, dtype=torch.int32, device=dev)
+    live = torch.empty(B, dtype=torch.int32, device=dev)
+    metrics = torch.empty(B if label is not None else 0, 3, dtype=torch.float32, device=dev)
+    if empty is not None and tuple(empty.shape) != (B,):
+        raise RuntimeError(f"ensemble_rank: empty has shape {tuple(empty.shape)}, expected ({B},)")
+    if label is not None and tuple(label.shape) != (B, T):
+        raise RuntimeError(f"ensemble_rank: label has shape {tuple(label.shape)}, expected ({B}, {T})")
+    em = empty.to(torch.int32).contiguous() if empty is not None else None
+    y = _f32c(label) if label is not None else None
+    ptrs = (ctypes.c_void_p * M)(*[x.data_ptr() for x in xs])
+    rows = (ctypes.c_long * M)(*[x.stride(0) if B > 1 else 0 for x in xs])          # (one row: the stride is never used)
+    cols = (ctypes.c_long * M)(*[x.stride(1) if T > 1 else 1 for x in xs])
+    native.call("nrm_ensemble_rank", ptrs, rows, cols, M, native.ptr(em) if em is not None else None,
+                native.ptr(y) if y is not None else None, B, T, native.ptr(score), native.ptr(rank), native.ptr(live),
+                native.ptr(metrics) if y is not None else None, native.stream_ptr())
+    return score, rank, live, metrics
+
+
+def _ensemble_rank_fake(logits, empty, label):
+    x = logits[0]
+    B, T = x.shape
+    return (x.new_empty((B, T), dtype=torch.float32), x.new_empty((B, T), dtype=torch.int32), x.new_empty((B,), dtype=torch.int32),
+            x.new_empty((B if label is not None else 0, 3), dtype=torch.float32))
+
+
+ensemble_rank = _op("ensemble_rank", "(Tensor[] logits, Tensor? empty, Tensor? label) -> (Tensor score, Tensor rank, Tensor live, Tensor metrics)",
+                    _ensemble_rank_impl, _ensemble_rank_fake)
+
+
 def _adam_step_impl(param, grad, exp_avg, exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, zero_grad):
     """train.py:48,73-75 over one flat buffer: Adam(lr, weight_decay) + optional zero_grad in one launch; the step
     counter lives in ``state`` on the device (hipGraph-capturable)."""
@@ -1801,4 +1844,4 @@ adam_step = _op("adam_step", "(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp
 OPS = ("pwattn_fwd", "pwattn_bwd", "linear_fwd", "linear_bwd", "small_linear_relu_fwd", "small_linear_relu_bwd", "mlp_gelu_fwd", "mlp_gelu_bwd", "batch_norm_stats", "batch_norm_apply",
        "batch_norm_bwd", "gate_block_fwd", "gate_block_bwd", "concat_cols",
        "weighted_pool_fwd", "weighted_pool_bwd", "attend_pool_fwd", "attend_pool_bwd", "softmax_bce_loss", "frontend_fwd", "frontend_bwd",
-       "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "adam_step")
+       "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "adam_step")
