@@ -1,12 +1,15 @@
 """GPU: the HIP pointwise-attention op (through the C ABI) against the oracle's literal
 [B,T,H,4D]-concat implementation, forward and every gradient.
-Tolerances (BASELINE.json north_star): forward <= 1e-3 relative, gradients <= 1e-2 relative."""
+Tolerances (BASELINE.json north_star): forward <= 1e-3 relative, gradients <= 1e-2 relative -- and, where _budget is called, the fp32
+error budget of tests/attention_budget.py: a float64 oracle, judged per impression / per fc1 block at a small multiple of what the
+fp32 oracle itself loses on the same case."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import attention_budget as ab
 from golden_util import GOLDEN, rel_err
 from oracle import user_model_oracle as orc
 
@@ -47,6 +50,21 @@ def _run_both(w, tgt, his, gs, mma=None):
     return s_g.detach().cpu().numpy(), got, s_c.detach().numpy(), ref
 
 
+def _budget(w, tgt, his, gs, s, got, arithmetic="f32"):
+    """The result of _run_both under the float64 error budget; w / tgt / his / gs as given to _run_both."""
+    return ab.assert_within_budget(ab.from_run_both(s, got), ab.Case(w, tgt, his, gs), arithmetic)
+
+
+def _budget_spot(arithmetic, w4, t, h, g, s, dt, dh, gw):
+    """Oracle spot check of a full-size launch under the error budget: ``t, h, g, s, dt, dh`` are the chosen impressions' slices of
+    the FULL launch, ``gw`` the four weight gradients of a launch over those impressions alone (weight gradients sum over the batch)."""
+    w = {k: v.detach().cpu().numpy() for k, v in zip(ab.WKEYS, w4)}
+    case = ab.Case(w, t.detach().cpu().numpy(), h.detach().cpu().numpy(), g.detach().cpu().numpy())
+    got = {"s": s.detach().cpu().numpy(), "d_target": dt.cpu().numpy(), "d_history": dh.cpu().numpy()}
+    got.update({k: v.cpu().numpy() for k, v in zip(ab.WKEYS, gw)})
+    return ab.assert_within_budget(got, case, arithmetic)
+
+
 # (B, T, H, D): BASELINE shapes at reduced B, reference default, ragged / tiny / non-multiple-of-16 cases
 SHAPES = [
     (2, 30, 50, 400),     # C3 large: 25x1 forward tiles (one N-chunk), 5x5 E tiles with 3+2 sub-passes
@@ -81,6 +99,7 @@ def test_scores_and_grads_match_oracle(lib, B, T, H, D):
     assert rel_err(s, s_ref) < FWD_TOL
     for k in ref:
         assert rel_err(got[k], ref[k]) < GRAD_TOL, k
+    _budget(w, tgt, his, gs, s, got)
 
 
 # fp32 "walk" form of the resident-W forward (pwattn_fwd_walk_f32_kernel, round 5; the default at D = 64, NRM_FWD_WALK_F32=1 at D = 128):
@@ -273,6 +292,7 @@ def test_default_dispatch_at_batch_32_matches_oracle(lib, monkeypatch, mma, B, T
     assert rel_err(s, s_ref) < fwd_tol
     for k in ref:
         assert rel_err(got[k], ref[k]) < grad_tol, (k, rel_err(got[k], ref[k]))
+    _budget(w, tgt, his, gs, s, got, mma)
 
 
 # bf16 MFMA operands, fp32 accumulation (BASELINE config 2).  Gates are the same as for the fp32 path and are taken against
@@ -304,6 +324,8 @@ def test_bf16_mfma_scores_and_grads_match_fp32_oracle(lib, mma, B, T, H, D):
     assert rel_err(s, s_ref) < fwd_tol, rel_err(s, s_ref)
     for k in ref:
         assert rel_err(got[k], ref[k]) < grad_tol, (k, rel_err(got[k], ref[k]))
+    if mma == "bf16x3":
+        _budget(w, tgt, his, gs, s, got, "bf16x3")
     # and it really is a different arithmetic from the fp32 path (unless the contraction is degenerate)
     s32, _, _, _ = _run_both(w, tgt, his, gs, mma="f32")
     if D >= 64 and H * T > 1:
@@ -427,6 +449,8 @@ def test_full_size_linearity_property(lib):
     (s_c * g[idx].cpu()).sum().backward()
     for a, k in zip(gw_two, ("a.mlp.fc1.weight", "a.mlp.fc1.bias", "a.mlp.fc2.weight", "a.mlp.fc2.bias")):
         assert rel_err(a.cpu().numpy().reshape(-1), pc[k].grad.numpy().reshape(-1)) < GRAD_TOL, k
+    # the same spot check under the error budget (dP walk, full-row dz pass and two streams are this size's default dispatch)
+    _budget_spot("f32", (w1, b1, w2, b2), t[idx], h[idx], g[idx], s[idx], gt_full[idx], gh_full[idx], gw_two)
 
 
 def test_full_size_c2_bf16x3_properties(lib):
@@ -464,6 +488,14 @@ def test_full_size_c2_bf16x3_properties(lib):
     p = {"a.mlp.fc1.weight": w1.detach().cpu(), "a.mlp.fc1.bias": b1.cpu(), "a.mlp.fc2.weight": w2.cpu(), "a.mlp.fc2.bias": b2.cpu()}
     ref = orc.pointwise_attention_scores(p, "a", t[idx].cpu(), h[idx].detach().cpu())[..., 0]
     assert rel_err(whole[idx].cpu().numpy(), ref.numpy()) < FWD_TOL
+    # the two impressions under the bf16x3 error budget: scores and row gradients of the FULL launch, weight gradients of a launch
+    # over those two alone
+    tq = t.clone().requires_grad_(True)
+    s = ops.pointwise_attention_scores(tq, h, w1, b1, w2, b2, mma="bf16x3")
+    gt_full, gh_full = torch.autograd.grad(s, [tq, h], g)
+    wq = [x.detach().clone().requires_grad_(True) for x in (w1, b1, w2, b2)]
+    gw_two = torch.autograd.grad(ops.pointwise_attention_scores(t[idx], h[idx].detach(), *wq, mma="bf16x3"), wq, g[idx])
+    _budget_spot("bf16x3", (w1, b1, w2, b2), t[idx], h[idx], g[idx], s[idx], gt_full[idx], gh_full[idx], gw_two)
 
 
 def _fuzz_shapes(n=48, seed=20260101):
@@ -491,6 +523,7 @@ def test_random_shapes_match_oracle_bf16x3(lib, B, T, H, D):
     assert rel_err(s, s_ref) < FWD_TOL
     for k in ref:
         assert rel_err(got[k], ref[k]) < GRAD_TOL, k
+    _budget(w, tgt, his, gs, s, got, "bf16x3")
 
 
 def _fuzz_shapes_dp(n=24, seed=20261005):
@@ -521,6 +554,7 @@ def test_random_shapes_match_oracle_dp_walk(lib, monkeypatch, B, T, H, D):
     for k in ref:
         assert rel_err(got[k], ref[k]) < GRAD_TOL, (k, rel_err(got[k], ref[k]))
         assert rel_err(got[k], ref[k]) < 1e-4, (k, rel_err(got[k], ref[k]))          # (measured: 1e-6; a wrong segment or tail shows as 1e-1)
+    _budget(w, tgt, his, gs, s, got)
 
 
 @pytest.mark.parametrize("B,T,H,D", _fuzz_shapes())
@@ -537,6 +571,7 @@ def test_random_shapes_match_oracle(lib, B, T, H, D):
     assert rel_err(s, s_ref) < FWD_TOL
     for k in ref:
         assert rel_err(got[k], ref[k]) < GRAD_TOL, k
+    _budget(w, tgt, his, gs, s, got)
 
 
 # The dt/dW pass has two group walks (csrc/capi.hip): blocked (every wave its own run of groups) and interleaved (the four
@@ -627,3 +662,4 @@ def test_full_size_c5_properties(lib):
     gw_one = torch.autograd.grad(ops.pointwise_attention_scores(t[i:i + 1], h[i:i + 1], *wq), wq, g[i:i + 1])
     for a, k in zip(gw_one, ("a.mlp.fc1.weight", "a.mlp.fc1.bias", "a.mlp.fc2.weight", "a.mlp.fc2.bias")):
         assert rel_err(a.cpu().numpy().reshape(-1), pc[k].grad.numpy().reshape(-1)) < GRAD_TOL, k
+    _budget_spot("f32", (w1, b1, w2, b2), t[i:i + 1], h[i:i + 1], g[i:i + 1], whole[i:i + 1], grads1[0][i:i + 1], grads1[1][i:i + 1], gw_one)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from attention_budget import FORMS, form_skip_reason
 from golden_util import masked_rel_err
 from oracle import user_model_oracle as orc
 
@@ -132,30 +133,14 @@ def _attn_case(entry, mma, B, T, H, D, rowgrads=True):
 ATTN_SHAPES = [(3, 3, 20, 72), (3, 2, 17, 100), (3, 2, 18, 132), (3, 2, 17, 388), (3, 2, 16, 420), (3, 2, 20, 64), (3, 2, 16, 256),
                (3, 2, 20, 400), (3, 3, 7, 66), (4, 3, 6, 132), (3, 2, 5, 196), (3, 2, 19, 300), (3, 2, 17, 128), (3, 2, 17, 188)]
 
-# per-launch knobs (read at every launch): forward image / walk forms and every backward form
-FORMS = {
-    "default": {},
-    "fwd_ct0": {"NRM_FWD_CT": "0"},
-    "fwd_ct1": {"NRM_FWD_CT": "1"},
-    "walk_f32_0": {"NRM_FWD_WALK_F32": "0"},
-    "walk_f32_1": {"NRM_FWD_WALK_F32": "1"},
-    "e_form": {"NRM_BWD_DP": "0"},
-    "dp_walk": {"NRM_BWD_DP": "1"},
-    "dp_walk_grid1": {"NRM_BWD_DP": "1", "NRM_DP_GRID": "1"},
-    "dz_rows0": {"NRM_DZ_ROWS": "0"},
-    "dz_rows1": {"NRM_DZ_ROWS": "1"},
-}
-
-
+# per-launch knobs (read at every launch): forward image / walk forms and every backward form -- the table and its skip rules are
+# shared with the error-budget tests (tests/attention_budget.py)
 @pytest.mark.parametrize("B,T,H,D", ATTN_SHAPES)
 @pytest.mark.parametrize("form", list(FORMS))
 def test_attention_f32_keeps_rows_apart(lib, monkeypatch, form, B, T, H, D):
-    if form.startswith("walk") and D not in (64, 128):
-        pytest.skip("the fp32 walk switch only matters at D = 64 / 128")
-    if form.startswith("fwd_ct") and (D <= 128 or D % 4):
-        pytest.skip("the candidate-image switch only matters for the chunk-streaming fp32 forward")
-    if form.startswith("dp_walk") and not lib.nrm_pwattn_bwd_dp_supported(D, H):
-        pytest.skip("no dP walk for this shape")
+    why = form_skip_reason(form, D, H, lib)
+    if why:
+        pytest.skip(why)
     for k, v in FORMS[form].items():
         monkeypatch.setenv(k, v)
     _attn_case("scores", "f32", B, T, H, D)
