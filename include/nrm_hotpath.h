@@ -307,6 +307,39 @@ int nrm_ensemble_rank_max_candidates(void);
 int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const long* col_stride, int M, const int* empty,
                       const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream);
 
+/* ---- compact scoring path (inference only; additive entry points, the ABI version is unchanged).
+ * A processed test set pads every candidate list with all-zero rows to the longest list of the data set.  All padded candidates of
+ * one impression have the same inputs, hence the same logit, so an impression with n live candidates that keeps e' padded columns
+ * after the batch's common trim needs n + [e' > 0] forward rows instead of T' = n + e': the live ones and ONE representative padded
+ * candidate whose exp enters the first softmax e' times.  Tables (int32, device): cand_off [B + 1] prefix sums of the rows per
+ * impression, cand_imp [N] impression of each compact row, pad_mult [B] = e'.  The kernels clamp table entries to the arrays.
+ *
+ * nrm_compact_gather: copies the N rows (b, t), t < n_b + [e'_b > 0], of x_target [B, T, target_cols] and x_global
+ *   [B, T, global_cols] (each float64 or float32, as its *_is_f64 says) into xt_compact [N, target_cols] and xg_compact [N, global_cols], and
+ *   compares every other kept padded column t in (n_b, T - trim) bitwise with the representative column n_b; a difference, or tables
+ *   with n_b + e'_b != T - trim, sets *flag = 1 (flag: host-visible int32, written in the error case only).  The trimmed columns
+ *   are not read.
+ * nrm_pwattn_fwd_ragged: nrm_pwattn_fwd without a z store for candidate rows t, v [N, D] (row c belongs to impression cand_imp[c]),
+ *   history rows h, u [B, H, D], scores s [N, H].  fp32 arithmetic only: mma other than NRM_MMA_F32 is refused.  max_count = the
+ *   longest list (max over b of cand_off[b + 1] - cand_off[b]).
+ * nrm_pool_bmm_ragged: out[c, :] = sum_j s[c, j] h[cand_imp[c], j, :] for s [N, H], h [B, H, D], out [N, D].
+ * nrm_ensemble_rank_ragged: nrm_ensemble_rank for compact logits: model m's entry c lies at logits[m][c * col_stride[m]]
+ *   (col_stride NULL = 1); impression b owns the entries cand_off[b] .. cand_off[b + 1] - 1, the last of which stands for pad_mult[b]
+ *   padded columns where pad_mult[b] > 0:
+ *     p_j = exp(l_j - mx) / (sum over live i of exp(l_i - mx) + e' exp(l_pad - mx)),  mx = max over the live and the pad logit,
+ *   then the mean over the models, the second softmax over the live values where e' > 0, rank and metrics exactly as
+ *   nrm_ensemble_rank, written to the SAME dense outputs score / rank [B, T] (0 on padding columns), live [B], metrics [B, 3]. */
+int nrm_compact_gather(const void* x_target, int target_cols, int target_is_f64, const void* x_global, int global_cols, int global_is_f64,
+                       const int* cand_off, const int* pad_mult, int B, int T, int trim, int N,
+                       void* xt_compact, void* xg_compact, int* flag, nrm_stream_t stream);
+int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
+                          const float* w2, const float* b2, float* s, const int* cand_imp, const int* cand_off,
+                          int B, int N, int max_count, int H, int D, int mma, nrm_stream_t stream);
+int nrm_pool_bmm_ragged(const float* s, const float* h, float* out, const int* cand_off, int B, int N, int max_count, int H, int D,
+                        nrm_stream_t stream);
+int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,
+                             const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

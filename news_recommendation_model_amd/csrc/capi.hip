@@ -12,6 +12,7 @@
 #include "pool_loss.hpp"
 #include "frontend.hpp"
 #include "scoring.hpp"
+#include "compact.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -106,6 +107,35 @@ int nrm_pwattn_fwd(const float* t, const float* h, const float* u, const float* 
         return fail(NRM_EINVAL, "nrm_pwattn_fwd: D=%d is too wide for the bf16 forward (one 16-column slice of W_p must fit the LDS)", D);
     p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
     return check_hip(nrm::pwattn_fwd_launch(p, pl, mma, (hipStream_t)stream), "pwattn_fwd");
+}
+
+int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
+                          const float* w2, const float* b2, float* s, const int* cand_imp, const int* cand_off,
+                          int B, int N, int max_count, int H, int D, int mma, nrm_stream_t stream) {
+    if (int rc = check_mma("nrm_pwattn_fwd_ragged", mma)) return rc;
+    if (mma != NRM_MMA_F32)
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: mma=%d: the ragged forward has fp32 arithmetic only (NRM_MMA_F32); the bf16 / bf16x3 "
+                                "forms exist for dense candidate lists (nrm_pwattn_fwd)", mma);
+    if (B < 0 || N < 0 || max_count < 0 || max_count > N || H <= 0 || D <= 0)
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: B=%d N=%d max_count=%d H=%d D=%d (B, N >= 0, 0 <= max_count <= N, H, D > 0)", B, N, max_count, H, D);
+    if (D % 4) return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: D=%d must be a multiple of 4", D);
+    if (D > 1024) return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: D=%d > 1024 not supported", D);
+    if ((long)N * H >= (1L << 31) || (long)N * D >= (1L << 29) || (long)B * H * D >= (1L << 29))
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: N*H=%ld exceeds 2^31 rows or a [N,D]/[B,H,D] operand exceeds 2^31 bytes", (long)N * H);
+    if (!t || !h || !u || !v || !packed_wp || !w2 || !b2 || !s || !cand_imp || !cand_off) return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: null pointer");
+    if (N == 0 || B == 0) return NRM_OK;
+    const nrm::FwdPlan pl = nrm::pwattn_fwd_plan(D);
+    nrm::FwdParams p;
+    p.t = t; p.h = h; p.u = u; p.v = v; p.wp = packed_wp; p.w2 = w2; p.b2 = b2; p.z = nullptr; p.s = s;
+    p.M = (long)N * H; p.T = 1; p.H = H; p.D = D;
+    p.ldt = D; p.ldh = D; p.ldu = D; p.ldv = D;
+    p.wp_bytes = (unsigned)(nrm_pwattn_packed_floats(D) * 4);
+    p.t_bytes = (unsigned)((long)N * D * 4);
+    p.h_bytes = (unsigned)((long)B * H * D * 4);
+    p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
+    nrm::RaggedTabs rg;
+    rg.cand_imp = cand_imp; rg.cand_off = cand_off; rg.B = B; rg.N = N; rg.max_count = max_count;
+    return check_hip(nrm::pwattn_fwd_ragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_ragged");
 }
 
 int nrm_pwattn_bwd_dz(float* z_inout, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,
@@ -440,6 +470,16 @@ int nrm_pool_bmm(const float* W, long wsb, long wsi, long wsj, const float* X, i
                                           (hipStream_t)stream), "pool_bmm");
 }
 
+int nrm_pool_bmm_ragged(const float* s, const float* h, float* out, const int* cand_off, int B, int N, int max_count, int H, int D,
+                        nrm_stream_t stream) {
+    if (!s || !h || !out || !cand_off) return fail(NRM_EINVAL, "nrm_pool_bmm_ragged: null pointer");
+    if (B < 0 || N < 0 || max_count < 0 || max_count > N || H <= 0 || D <= 0 || D % 4 || B > 65535)
+        return fail(NRM_EINVAL, "nrm_pool_bmm_ragged: B=%d N=%d max_count=%d H=%d D=%d", B, N, max_count, H, D);
+    if (!al16(h) || !al16(out) || (long)H * D * 4 >= (1L << 31) || (long)N * H >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_pool_bmm_ragged: h and out must be 16-byte aligned, H*D*4 and N*H below 2^31");
+    return check_hip(nrm::bmm_rows_ragged_launch(s, H, h, (long)H * D, D, out, D, cand_off, B, N, max_count, H, D, (hipStream_t)stream), "pool_bmm_ragged");
+}
+
 int nrm_pool_rowdot(const float* g, int ldg, const float* h, float* ds, int B, int T, int H, int D, float* zero_out, int zero_n,
                     nrm_stream_t stream) {
     if (!g || !h || !ds) return fail(NRM_EINVAL, "nrm_pool_rowdot: null pointer");
@@ -538,6 +578,39 @@ int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const 
         lg.ptr[m] = logits[m]; lg.row_stride[m] = row_stride[m]; lg.col_stride[m] = cs;
     }
     return check_hip(nrm::ensemble_rank_launch(lg, M, empty, label, B, T, score, rank, live, metrics, (hipStream_t)stream), "ensemble_rank");
+}
+
+int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,
+                             const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream) {
+    if (!logits || !cand_off || !pad_mult || !score || !rank || !live) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: null pointer");
+    if (M < 1 || M > nrm::ENSEMBLE_MAX_MODELS) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: M=%d models (1 .. %d)", M, nrm::ENSEMBLE_MAX_MODELS);
+    if (B < 0 || T <= 0 || N < 0) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: B=%d T=%d N=%d", B, T, N);
+    if (T > nrm::ENSEMBLE_MAX_CANDIDATES)
+        return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: T=%d candidates exceed the cap of %d (nrm_ensemble_rank_max_candidates)", T, nrm::ENSEMBLE_MAX_CANDIDATES);
+    if ((label == nullptr) != (metrics == nullptr)) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: label and metrics must be given together or both be NULL");
+    nrm::EnsembleLogits lg = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m] && N > 0) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: logits[%d] is a null pointer", m);
+        const long cs = col_stride ? col_stride[m] : 1;
+        if (cs < 1) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: model %d has entry stride %ld (need >= 1)", m, cs);
+        lg.ptr[m] = logits[m]; lg.row_stride[m] = 0; lg.col_stride[m] = cs;
+    }
+    return check_hip(nrm::ensemble_rank_ragged_launch(lg, M, cand_off, pad_mult, N, label, B, T, score, rank, live, metrics, (hipStream_t)stream),
+                     "ensemble_rank_ragged");
+}
+
+int nrm_compact_gather(const void* x_target, int target_cols, int target_is_f64, const void* x_global, int global_cols, int global_is_f64,
+                       const int* cand_off, const int* pad_mult, int B, int T, int trim, int N,
+                       void* xt_compact, void* xg_compact, int* flag, nrm_stream_t stream) {
+    if (B < 0 || T <= 0 || trim < 0 || trim > T || N < 0 || target_cols <= 0 || global_cols <= 0)
+        return fail(NRM_EINVAL, "nrm_compact_gather: B=%d T=%d trim=%d N=%d target_cols=%d global_cols=%d", B, T, trim, N, target_cols, global_cols);
+    if ((long)N > (long)B * (T - trim)) return fail(NRM_EINVAL, "nrm_compact_gather: N=%d compact rows exceed the B*(T - trim)=%ld kept cells", N, (long)B * (T - trim));
+    if (!cand_off || !pad_mult || !flag || !x_target || !x_global || (N > 0 && (!xt_compact || !xg_compact))) return fail(NRM_EINVAL, "nrm_compact_gather: null pointer");
+    nrm::CompactGatherParams p;
+    p.xt = (const unsigned*)x_target; p.xg = (const unsigned*)x_global; p.xt_c = (unsigned*)xt_compact; p.xg_c = (unsigned*)xg_compact;
+    p.wt = target_cols * (target_is_f64 ? 2 : 1); p.wg = global_cols * (global_is_f64 ? 2 : 1);
+    p.cand_off = cand_off; p.pad_mult = pad_mult; p.B = B; p.T = T; p.Tp = T - trim; p.N = N; p.flag = flag;
+    return check_hip(nrm::compact_gather_launch(p, (hipStream_t)stream), "compact_gather");
 }
 
 // ------------------------------------------------------------------------------------------- embedding front end

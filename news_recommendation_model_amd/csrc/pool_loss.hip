@@ -23,11 +23,15 @@ namespace nrm {
 // J = 200 history rows in 50 dependent load -> MFMA rounds, 93 us for 0.1 GFLOP -- the four waves of a workgroup share ONE task,
 // each takes a quarter of the reduction range and waves 1-3 hand their partial tiles to wave 0 through the LDS.  Either way the
 // operands of round j0 + 4 are requested before the MFMAs of round j0.
-template <bool JSPLIT>
+// RAGGED (compact scoring: pooled[c,:] = sum_h s[c,h] h[cand_imp[c],h,:]): impression b owns the rows cand_off[b] .. cand_off[b + 1] - 1 of
+// W and out (row strides wsi / ldo, no batch stride), I is the LONGEST list (it sizes the task grid) and a task past the end of
+// its impression's list leaves at once.  The offsets are clamped to [0, N].
+template <bool JSPLIT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__ W, long wsb, long wsi, long wsj,
                                                        const float* __restrict__ X, long xsb, int ldx,
                                                        float* __restrict__ out, long osb, int ldo,
-                                                       int B, int I, int J, int D, int accumulate) {
+                                                       int B, int I, int J, int D, int accumulate,
+                                                       const int* __restrict__ cand_off, int N) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) f32x4 part[JSPLIT ? 3 * 16 * 64 : 1];
     const int lane = threadIdx.x & 63;
@@ -41,6 +45,14 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
     const int b = (int)(task / ((long)nslab * nig));
     const int d0 = slab * 64, i0 = ig * 64;
     constexpr unsigned OOB = 0x80000000u;
+    if (RAGGED) {
+        const int c0 = min(max(cand_off[b], 0), N);
+        I = min(max(cand_off[b + 1], c0), N) - c0;                      // this impression's rows
+        if (i0 >= I) return;                                            // (uniform per task: JSPLIT workgroups leave together)
+        wsb = 0; osb = 0;
+        W += (long)c0 * wsi;
+        out += (long)c0 * ldo;
+    }
     const float* Wb = W + b * wsb;
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(X) + b * xsb, 0, ((J - 1) * ldx + D) * 4, 0x00020000);
@@ -199,10 +211,26 @@ hipError_t bmm_rows_launch(const float* W, long wsb, long wsi, long wsj, const f
     const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && J >= 32);
     if (jsplit)
         hipLaunchKernelGGL(bmm_rows_kernel<true>, dim3((unsigned)tasks), dim3(256), 0, st,
-                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate);
+                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate, nullptr, 0);
     else
         hipLaunchKernelGGL(bmm_rows_kernel<false>, dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st,
-                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate);
+                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate, nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t bmm_rows_ragged_launch(const float* S, int lds, const float* X, long xsb, int ldx, float* out, int ldo, const int* cand_off,
+                                  int B, int N, int max_count, int J, int D, hipStream_t st) {
+    if (B <= 0 || N <= 0 || max_count <= 0) return hipSuccess;
+    const long tasks = (long)B * ((D + 63) / 64) * ((max_count + 63) / 64);
+    if ((tasks + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    const char* env = getenv("NRM_POOL_JSPLIT");
+    const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && J >= 32);          // the dense rule
+    if (jsplit)
+        hipLaunchKernelGGL((bmm_rows_kernel<true, true>), dim3((unsigned)tasks), dim3(256), 0, st,
+                           S, 0L, (long)lds, 1L, X, xsb, ldx, out, 0L, ldo, B, max_count, J, D, 0, cand_off, N);
+    else
+        hipLaunchKernelGGL((bmm_rows_kernel<false, true>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st,
+                           S, 0L, (long)lds, 1L, X, xsb, ldx, out, 0L, ldo, B, max_count, J, D, 0, cand_off, N);
     return hipGetLastError();
 }
 

@@ -5,6 +5,9 @@
 namespace nrm {
 hipError_t bmm_rows_launch(const float* W, long wsb, long wsi, long wsj, const float* X, long xsb, int ldx,
                            float* out, long osb, int ldo, int B, int I, int J, int D, int accumulate, hipStream_t st);
+// ragged pool of the compact scoring path: out[c,:] = sum_j S[c,j] X[b(c),j,:], impression b owns the rows cand_off[b] .. cand_off[b + 1] - 1
+hipError_t bmm_rows_ragged_launch(const float* S, int lds, const float* X, long xsb, int ldx, float* out, int ldo, const int* cand_off,
+                                  int B, int N, int max_count, int J, int D, hipStream_t st);
 hipError_t rowdot_launch(const float* g, long gsb, int ldg, const float* h, long hsb, int ldh, float* ds,
                          int B, int T, int H, int D, float* zero_out, int zero_n, hipStream_t st);
 hipError_t loss_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,

@@ -23,9 +23,20 @@ struct FwdParams {
     int kchunks;         // K-chunks of the packed W_p: ceil(D/16) (fp32 operands) or ceil(D/32) (bf16 operands)
     int nchunks;         // number of N-chunks (each NT*16 output columns)
 };
+// Ragged candidate lists (inference, compact scoring): candidate rows t / v are [N, D] and belong to impression cand_imp[c]; the
+// candidates of impression b are the rows cand_off[b] .. cand_off[b + 1] - 1.  Passed as a kernel argument of its own behind the
+// dense parameter block; the dense instantiations never read it.
+struct RaggedTabs {
+    const int* cand_imp;   // [N]
+    const int* cand_off;   // [B + 1]
+    int B, N;
+    int max_count;         // longest candidate list (host side: task grids)
+};
 struct FwdPlan { int NT, MT, nchunks, rows, kchunks; };
 FwdPlan pwattn_fwd_plan(int D);
 hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st);
+// fp32 arithmetic, no z store; p.M = N * H, p.T is not read
+hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st);
 hipError_t pack_wp_launch(const float* w, int ldw, int D, const FwdPlan& pl, int mma, float* packed, hipStream_t st);
 // resident-W forward (pwattn_fwd_rw.hip): mma = 0 (fp32 MFMA), 1 (bf16 operands) or 2 (bf16x3: hi + lo split).  The output
 // columns are cut into nsplit slices of nts 16-column tiles whose whole image stays resident in LDS (persistent workgroups).
@@ -33,6 +44,7 @@ struct RwPlan { int nts, nsplit, rows, k32, wimg; };      // rows = padded rows 
 RwPlan pwattn_rw_plan(int D, int mma);
 bool pwattn_fwd_uses_rw(int D, int mma);                  // which forward (and which packed layout) a call takes
 hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st);
+hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);     // fp32, D <= 128 (one resident slice)
 hipError_t pack_wp_bf16_launch(const float* w, int ldw, int D, int mma, float* packed, hipStream_t st);
 
 // ---- backward (pwattn_bwd.hip)

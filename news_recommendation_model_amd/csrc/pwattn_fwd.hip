@@ -61,8 +61,11 @@ __global__ void pack_wp_kernel(const float* __restrict__ w, int ldw, int D, int 
 // from image row (m / H) - bt0 (a broadcast: <= 2 distinct addresses per 16-lane read group for H >= 16).  Three LDS-DMA
 // pieces per workgroup and chunk fewer, 35 KB instead of 43 KB of LDS at 13x1: FOUR workgroups per CU instead of three
 // (launch bounds 4 waves per SIMD: 121 VGPRs).  Used for H >= 16 (pwattn_fwd_launch); shorter histories keep the per-row image.
-template <int NT, int MT, bool SAVE_Z, int WPE = 2, bool CT = false, int NW = 4>
-__global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParams p) {
+// RAGGED (compact scoring): the flattened rows are (c, h) over the N compact candidates and the impression of candidate c is
+// rg.cand_imp[c] instead of c / T -- the only two places the dense form derives it; the compact image is indexed by the flat
+// candidate already.  A table entry outside [0, B) is clamped: a wrong row is read, never a foreign address.
+template <int NT, int MT, bool SAVE_Z, int WPE = 2, bool CT = false, int NW = 4, bool RAGGED = false>
+__global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParams p, const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)      // buffer-descriptor types/builtins exist in the device pass only;
                                          // without the guard the host pass silently drops the kernel stub
     constexpr int BM = NW * MT * 16;      // data rows per workgroup (NW waves x MT row tiles of 16)
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
         const int m = m0 + (wave * MT + j) * 16 + rl;
         const unsigned mm = m < M ? (unsigned)m : 0u;
         const unsigned bt = mm / (unsigned)H;
-        const unsigned b = bt / (unsigned)T;
+        const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
         const unsigned hr = b * H + (mm - bt * H);
         const unsigned slot = (unsigned)((lane & 3) ^ swz4(rl));
         voff_t[j] = (!CT && m < M) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
         const int m = m0 + (wave * MT + jt) * 16 + r16;
         const unsigned mm = m < M ? (unsigned)m : 0u;
         const unsigned bt = mm / (unsigned)H;
-        const unsigned b = bt / (unsigned)T;
+        const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
         const unsigned hr = b * H + (mm - bt * H);
         voff_u[jt] = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
         voff_v[jt] = m < M ? (bt * p.ldv + 4 * q) * 4u : OOB;
@@ -312,8 +315,18 @@ static hipError_t launch_fwd_t(const FwdParams& p, hipStream_t st) {
     const long nblk = (p.M + BM - 1) / BM;
     if (nblk <= 0) return hipSuccess;
     if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
-    if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p);
-    else     hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p);
+    if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, RaggedTabs{});
+    else     hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, RaggedTabs{});
+    return hipGetLastError();
+}
+
+template <int NT, int MT, int WPE = 2, bool CT = false>
+static hipError_t launch_fwd_ragged_t(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
+    constexpr int BM = 4 * MT * 16;
+    const long nblk = (p.M + BM - 1) / BM;
+    if (nblk <= 0) return hipSuccess;
+    if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, 4, true>), dim3((unsigned)nblk), dim3(256), 0, st, p, rg);
     return hipGetLastError();
 }
 
@@ -346,6 +359,25 @@ hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hip
         case 16: return launch_fwd_t<16, 1>(p, st);        // (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms)
         case 20: return launch_fwd_t<20, 1>(p, st);
         case 25: return launch_fwd_t<25, 1>(p, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+// Ragged candidate lists: the plan of the dense forward for the same D and H (same tiles, same image choice); widths whose whole
+// W_p is one resident slice (D <= 128) take the resident-W forms, as the dense forward does -- the packed image is the same.
+hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
+    if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_ragged_launch(p, rg, st);
+    switch (pl.NT) {
+        case 4:  return launch_fwd_ragged_t<4, 4>(p, rg, st);
+        case 6:  return launch_fwd_ragged_t<6, 4>(p, rg, st);
+        case 8:  return launch_fwd_ragged_t<8, 3>(p, rg, st);
+        case 10: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<10, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<10, 1, 3>(p, rg, st);
+        case 12: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<12, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<12, 1, 3>(p, rg, st);
+        case 13: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<13, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<13, 1, 3>(p, rg, st);
+        case 14: return launch_fwd_ragged_t<14, 2>(p, rg, st);
+        case 16: return launch_fwd_ragged_t<16, 1>(p, rg, st);
+        case 20: return launch_fwd_ragged_t<20, 1>(p, rg, st);
+        case 25: return launch_fwd_ragged_t<25, 1>(p, rg, st);
     }
     return hipErrorInvalidValue;
 }

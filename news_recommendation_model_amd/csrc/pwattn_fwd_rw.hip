@@ -91,8 +91,10 @@ RwPlan pwattn_rw_plan(int D, int mma) {
 }
 
 // packed[c][img][row][32 bf16] (pack_wp_bf16_kernel) with rows = plan.rows
-template <int NTS, bool SAVE_Z, int MMA>
-__global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_kernel(const FwdParams p, const RwPlan pl, int wgs_per_split) {
+// RAGGED (compact scoring, fp32): rows are (c, h) over the N compact candidates, the impression of candidate c is rg.cand_imp[c].
+template <int NTS, bool SAVE_Z, int MMA, bool RAGGED = false>
+__global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_kernel(const FwdParams p, const RwPlan pl, int wgs_per_split,
+                                                                                    const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int WIMG = MMA == 2 ? 2 : 1;
     constexpr int SROWS = NTS * 16;                                    // W rows (= output columns) of a slice
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
         const int m = tile * 16 + r16;
         const unsigned mm = m < M ? (unsigned)m : 0u;
         const unsigned bt = mm / (unsigned)H;
-        const unsigned hr = (bt / (unsigned)T) * H + (mm - bt * H);
+        const unsigned hr = (RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T) * H + (mm - bt * H);
         const unsigned voff_t = m < M ? (bt * p.ldt + 4 * q) * 4u : OOB;
         const unsigned voff_h = m < M ? (hr * p.ldh + 4 * q) * 4u : OOB;
         const unsigned voff_u = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
@@ -406,8 +408,11 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_kernel(const FwdParams
 // floats per lane), its u tile and the fc2 weights in registers and walks the candidates: 4 t loads (two chunks ahead, across step
 // boundaries), NTS v loads and NTS z stores per step.  Same arithmetic per element as the kernel above (accumulators start at u, v
 // is added in the epilogue: (u + P W_p^T) + v instead of (u + v) + P W_p^T -- one fp32 rounding apart).
-template <int NTS, bool SAVE_Z, int KCH>
-__global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdParams p, const RwPlan pl, int wgs, int tsplit) {
+// RAGGED (compact scoring): a task's candidates are the compact rows rg.cand_off[b] .. rg.cand_off[b + 1] - 1 instead of b T .. b T + T - 1,
+// and the tsplit cut is made per impression (parts of ceil(count_b / tsplit) candidates; a short list leaves its last parts empty).
+// The offsets are clamped to [0, N] and made wave-uniform before they enter a buffer descriptor.
+template <int NTS, bool SAVE_Z, int KCH, bool RAGGED = false>
+__global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdParams p, const RwPlan pl, int wgs, int tsplit, const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(KCH % 2 == 0 && NTS == KCH, "whole width in one slice: D = 16 KCH = 16 NTS");
     constexpr int SROWS = NTS * 16;
@@ -432,8 +437,8 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
     const int rslot = 4 * (q ^ swz4(r16));
     const float b2 = p.b2[0];
     const int nht = (H + 15) >> 4;
-    const int tlen = (T + tsplit - 1) / tsplit;
-    const int ntask = (int)(p.M / ((long)T * H)) * nht * tsplit;         // B * nht * tsplit
+    const int tlen = RAGGED ? 0 : (T + tsplit - 1) / tsplit;
+    const int ntask = (RAGGED ? rg.B : (int)(p.M / ((long)T * H))) * nht * tsplit;         // B * nht * tsplit
     f32x4 wreg[NTS];                                                     // fc2 weights of this lane's four columns of every tile
 #pragma unroll
     for (int it = 0; it < NTS; ++it)
@@ -443,11 +448,19 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
         const int tp = task % tsplit;
         const int rest = task / tsplit;
         const int b = rest / nht, h0 = (rest - b * nht) * 16;
-        const int t_lo = tp * tlen, t_hi = min(T, t_lo + tlen);
+        // first compact candidate and length of impression b's list (dense: b T and T)
+        int cbase = 0, cnt = T;
+        if (RAGGED) {
+            cbase = __builtin_amdgcn_readfirstlane(min(max(rg.cand_off[b], 0), rg.N));
+            cnt = __builtin_amdgcn_readfirstlane(min(max(rg.cand_off[b + 1], cbase), rg.N)) - cbase;
+        }
+        const int tl = RAGGED ? (cnt + tsplit - 1) / tsplit : tlen;
+        const int t_lo = tp * tl, t_hi = min(RAGGED ? cnt : T, t_lo + tl);
         if (t_lo >= t_hi) continue;
         const bool rok = h0 + r16 < H;
-        const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t) + (size_t)b * T * p.ldt, 0, (unsigned)(T * p.ldt * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v) + (size_t)b * T * p.ldv, 0, (unsigned)(T * p.ldv * 4), 0x00020000);
+        const size_t trow = RAGGED ? (size_t)cbase : (size_t)b * T;    // first candidate row of the task's impression
+        const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t) + trow * p.ldt, 0, (unsigned)(cnt * p.ldt * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v) + trow * p.ldv, 0, (unsigned)(cnt * p.ldv * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h) + (size_t)b * H * p.ldh, 0, (unsigned)(H * p.ldh * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u) + (size_t)b * H * p.ldu, 0, (unsigned)(H * p.ldu * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
@@ -505,7 +518,7 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
                 }
             }
             // epilogue: z = acc + v ; optional z store ; GELU ; fc2 dot
-            const int m = (b * T + t) * H + h0 + r16;
+            const int m = ((RAGGED ? cbase : b * T) + t) * H + h0 + r16;
             float s_part = 0.f;
 #pragma unroll
             for (int it = 0; it < NTS; ++it) {
@@ -547,7 +560,7 @@ static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, hipSt
         /* per launch: the attribute is per device, and a process may launch on more than one */                        \
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);  \
         if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs);                                                         \
+        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, RaggedTabs{});                                           \
     }
     if (mma == 2)      { if (p.z) NRM_RW(true, 2) else NRM_RW(false, 2) }
     else if (mma == 1) { if (p.z) NRM_RW(true, 1) else NRM_RW(false, 1) }
@@ -606,9 +619,66 @@ static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, hipStrea
     if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
     const size_t shm = (size_t)pl.k32 * NTS * 1024;
     const dim3 grid((unsigned)wgs), block(512);
-    if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit);
-    else     hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit);
+    if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
+    else     hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
     return hipGetLastError();
+}
+
+// ragged walk: the same grid rule with the MEAN list length in T's place (the cut itself is per impression, in the kernel)
+template <int NTS>
+static hipError_t launch_walk_f32_ragged(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, hipStream_t st) {
+    const int nht = (p.H + 15) / 16;
+    const long base = (long)rg.B * nht;
+    if (base <= 0 || rg.N <= 0) return hipSuccess;
+    int wgs = 2 * rw_cus();
+    const int mean = (rg.N + rg.B - 1) / rg.B;
+    int tsplit = 1;
+    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
+    else while (base * tsplit < 2L * wgs * 8 && mean / (tsplit + 1) >= 4) ++tsplit;
+    if (tsplit < 1) tsplit = 1;
+    if (tsplit > rg.max_count) tsplit = rg.max_count > 0 ? rg.max_count : 1;
+    const long ntask = base * tsplit;
+    if (ntask > 0x7fffffffL) return hipErrorInvalidValue;
+    if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
+    const size_t shm = (size_t)pl.k32 * NTS * 1024;
+    hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), dim3((unsigned)wgs), dim3(512), shm, st, p, pl, wgs, tsplit, rg);
+    return hipGetLastError();
+}
+
+template <int NTS>
+static hipError_t launch_rw_ragged(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, hipStream_t st) {
+    const int ntile = (int)((p.M + 15) / 16);
+    if (ntile <= 0) return hipSuccess;
+    int wgs = rw_cus();
+    if ((long)wgs * FB_WAVES > ntile) wgs = (ntile + FB_WAVES - 1) / FB_WAVES;
+    const size_t shm = (size_t)pl.k32 * NTS * 1024;
+    auto k = pwattn_fwd_rw_kernel<NTS, false, 0, true>;
+    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)wgs), dim3(FB_WAVES * 64), shm, st, p, pl, wgs, rg);
+    return hipGetLastError();
+}
+
+// fp32 only, widths that are one resident slice (pwattn_fwd_uses_rw(D, 0)): the walk where the dense forward walks (D = 64; D = 128 with
+// NRM_FWD_WALK_F32=1), the tile-by-tile form otherwise
+hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
+    const RwPlan pl = pwattn_rw_plan(p.D, 0);
+    if (pl.nsplit != 1) return hipErrorInvalidValue;
+    if (p.D == pl.nts * 16) {
+        const char* e = getenv("NRM_FWD_WALK_F32");
+        if ((e ? e[0] == '1' : true) && p.D == 64) return launch_walk_f32_ragged<4>(p, pl, rg, st);
+        if (e && e[0] == '1' && p.D == 128) return launch_walk_f32_ragged<8>(p, pl, rg, st);
+    }
+    switch (pl.nts) {
+        case 1:  return launch_rw_ragged<1>(p, pl, rg, st);
+        case 2:  return launch_rw_ragged<2>(p, pl, rg, st);
+        case 3:  return launch_rw_ragged<3>(p, pl, rg, st);
+        case 4:  return launch_rw_ragged<4>(p, pl, rg, st);
+        case 5:  return launch_rw_ragged<5>(p, pl, rg, st);
+        case 6:  return launch_rw_ragged<6>(p, pl, rg, st);
+        case 8:  return launch_rw_ragged<8>(p, pl, rg, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st) {

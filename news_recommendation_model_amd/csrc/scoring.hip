@@ -26,18 +26,35 @@ __device__ __forceinline__ double wave_sum64d(double v) {
 }
 
 // REG: T <= 64, the lane's one element stays in a register and the rank loop reads the others with v_readlane.
-template <bool REG>
+// RAGGED (compact scoring path): model m's logits are ONE compact vector; impression b owns its entries cand_off[b] .. cand_off[b + 1] - 1:
+// the n live candidates and, where pad_mult[b] = e' > 0 padded columns are kept, one representative padded candidate behind them.
+// All e' padded columns of a row have the same logit (same all-zero input rows, same history), so
+//   p_j = exp(l_j - mx) / (sum_{i < n} exp(l_i - mx) + e' exp(l_pad - mx)),   mx = max over the live and the pad logit
+// is the first softmax over all T = n + e' columns; everything after it (mean, second softmax where e' > 0, rank, metrics) and the dense
+// [B, T] outputs are those of the dense form.  Offsets and counts are clamped to the arrays.
+template <bool REG, bool RAGGED = false>
 __global__ __launch_bounds__(256) void ensemble_rank_kernel(const EnsembleLogits lg, int M, const int* __restrict__ empty,
                                                             const float* __restrict__ label, int B, int T,
                                                             float* __restrict__ score, int* __restrict__ rank,
-                                                            int* __restrict__ live, float* __restrict__ metrics) {
+                                                            int* __restrict__ live, float* __restrict__ metrics,
+                                                            const int* __restrict__ cand_off, const int* __restrict__ pad_mult, int N) {
     extern __shared__ __attribute__((aligned(16))) float rows[];       // [4][T] when !REG
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int b = blockIdx.x * 4 + wave;
     if (b >= B) return;                                                // (no workgroup barrier below: waves are independent)
-    const int e = empty ? empty[b] : 0;
-    const int n = e <= 0 ? T : (e >= T ? 0 : T - e);                   // live candidates, always within [0, T]
+    int e = 0, c0 = 0, cnt = 0;                                        // RAGGED: padded columns kept, first compact entry, entries
+    if (RAGGED) {
+        c0 = min(max(cand_off[b], 0), N);
+        cnt = min(min(max(cand_off[b + 1], c0), N) - c0, T);
+        e = max(pad_mult[b], 0);
+    } else {
+        e = empty ? empty[b] : 0;
+    }
+    const bool has_pad = RAGGED ? e > 0 : false;
+    const int n = RAGGED ? (has_pad ? max(cnt - 1, 0) : cnt)
+                         : (e <= 0 ? T : (e >= T ? 0 : T - e));        // live candidates, always within [0, T]
+#define NRM_AGAIN (RAGGED ? has_pad : n < T)                           /* the row keeps padding: second softmax over the live slice */
     float* row = rows + (REG ? 0 : wave * T);
     float* s_out = score + (long)b * T;
     int* r_out = rank + (long)b * T;
@@ -47,9 +64,32 @@ __global__ __launch_bounds__(256) void ensemble_rank_kernel(const EnsembleLogits
     // ---- mean over the models of softmax over all T columns
     float acc = 0.f;                                                   // REG: the lane's element of the sum
     for (int m = 0; m < M; ++m) {
-        const float* x = lg.ptr[m] + (long)b * lg.row_stride[m];
         const long cs = lg.col_stride[m];
-        if (REG) {
+        const float* x = RAGGED ? lg.ptr[m] + (long)c0 * cs : lg.ptr[m] + (long)b * lg.row_stride[m];
+        if (RAGGED) {
+            const float mult = (float)e;                               // weight of the representative padded entry (index n)
+            if (REG) {
+                const float xj = lane < cnt ? x[lane * cs] : NEG_INF;
+                const float mx = wave_max64(xj);
+                const float ex = lane < cnt ? expf(xj - mx) : 0.f;
+                const float sum = wave_sum64(lane == n ? ex * mult : ex);          // (lane == n < cnt only where has_pad)
+                acc += lane < n ? ex / sum : 0.f;
+            } else {
+                float mx = NEG_INF;
+                for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, x[j * cs]);
+                mx = wave_max64(mx);
+                float sum = 0.f;
+                for (int j = lane; j < cnt; j += 64) {
+                    const float ex = expf(x[j * cs] - mx);
+                    sum += j == n ? ex * mult : ex;
+                }
+                sum = wave_sum64(sum);
+                for (int j = lane; j < T; j += 64) {
+                    const float pj = j < n ? expf(x[j * cs] - mx) / sum : 0.f;
+                    row[j] = m ? row[j] + pj : pj;
+                }
+            }
+        } else if (REG) {
             const float xj = lane < T ? x[lane * cs] : NEG_INF;
             const float mx = wave_max64(xj);
             const float ex = lane < T ? expf(xj - mx) : 0.f;
@@ -73,7 +113,7 @@ __global__ __launch_bounds__(256) void ensemble_rank_kernel(const EnsembleLogits
     float sc = 0.f;                                                    // REG: the lane's score
     if (REG) {
         const float o = acc / models;
-        if (n < T) {
+        if (NRM_AGAIN) {
             const float mx = wave_max64(lane < n ? o : NEG_INF);
             const float ex = lane < n ? expf(o - mx) : 0.f;
             const float sum = wave_sum64(ex);
@@ -83,7 +123,7 @@ __global__ __launch_bounds__(256) void ensemble_rank_kernel(const EnsembleLogits
         }
         if (lane < T) s_out[lane] = sc;
     } else {
-        if (n < T) {
+        if (NRM_AGAIN) {
             float mx = NEG_INF;
             for (int j = lane; j < n; j += 64) {
                 const float o = row[j] / models;
@@ -170,15 +210,31 @@ __global__ __launch_bounds__(256) void ensemble_rank_kernel(const EnsembleLogits
     }
 }
 
+#undef NRM_AGAIN
+
 hipError_t ensemble_rank_launch(const EnsembleLogits& logits, int M, const int* empty, const float* label, int B, int T,
                                 float* score, int* rank, int* live, float* metrics, hipStream_t st) {
     if (B <= 0) return hipSuccess;
     const dim3 grid((B + 3) / 4), block(256);
     if (T <= 64)
-        hipLaunchKernelGGL(ensemble_rank_kernel<true>, grid, block, 0, st, logits, M, empty, label, B, T, score, rank, live, metrics);
+        hipLaunchKernelGGL(ensemble_rank_kernel<true>, grid, block, 0, st, logits, M, empty, label, B, T, score, rank, live, metrics,
+                           nullptr, nullptr, 0);
     else
         hipLaunchKernelGGL(ensemble_rank_kernel<false>, grid, block, 4 * (size_t)T * sizeof(float), st, logits, M, empty, label, B, T,
-                           score, rank, live, metrics);
+                           score, rank, live, metrics, nullptr, nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t ensemble_rank_ragged_launch(const EnsembleLogits& logits, int M, const int* cand_off, const int* pad_mult, int N,
+                                       const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    const dim3 grid((B + 3) / 4), block(256);
+    if (T <= 64)
+        hipLaunchKernelGGL((ensemble_rank_kernel<true, true>), grid, block, 0, st, logits, M, nullptr, label, B, T, score, rank, live, metrics,
+                           cand_off, pad_mult, N);
+    else
+        hipLaunchKernelGGL((ensemble_rank_kernel<false, true>), grid, block, 4 * (size_t)T * sizeof(float), st, logits, M, nullptr, label, B, T,
+                           score, rank, live, metrics, cand_off, pad_mult, N);
     return hipGetLastError();
 }
 

@@ -18,4 +18,9 @@ struct EnsembleLogits {
 hipError_t ensemble_rank_launch(const EnsembleLogits& logits, int M, const int* empty, const float* label, int B, int T,
                                 float* score, int* rank, int* live, float* metrics, hipStream_t st);
 
+// ragged form (compact scoring): model m's compact logits at logits.ptr[m] + c * col_stride[m] (row_stride is not read), impression b owns the
+// entries cand_off[b] .. cand_off[b + 1] - 1, the last of them standing for pad_mult[b] padded columns where pad_mult[b] > 0
+hipError_t ensemble_rank_ragged_launch(const EnsembleLogits& logits, int M, const int* cand_off, const int* pad_mult, int N,
+                                       const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, hipStream_t st);
+
 }  // namespace nrm

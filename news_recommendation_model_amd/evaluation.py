@@ -10,6 +10,8 @@
   rank_row(scores)              test.py:118-126: 1-based rank of every candidate, highest score first.
   predict_ranked(models, batch) test.py:58-70 + :118-126 with the whole tail after the forwards -- softmax per model, mean,
                                 second softmax, rank, optionally MRR / nDCG -- as ONE launch (C ABI nrm_ensemble_rank).
+  predict_ranked_compact(models, batch)  predict_ranked() without the padding: each impression's live candidates and ONE representative
+                                padded candidate go through the forwards (ragged kernels), the tail counts the representative e' times.
   validate_ranked(models, batches)   validate() plus MRR, nDCG@5, nDCG@10.
   write_predictions / zip_predictions   test.py:76-132: one "<impression id> [r1,r2,...]" line per impression, zipped.
   score_dataset(models, head_path, out_dir)   test.py's model_test + write_submission_file over a processed test set.
@@ -209,6 +211,40 @@ def predict_ranked(models, batch, with_metrics=False):
 
 
 @torch.no_grad()
+def predict_ranked_compact(models, batch, with_metrics=False, force_compact=False):
+    """predict_ranked() on ragged candidate lists, same return contract: (scores [B, T'] fp32, rank [B, T'] int32, live [B] int32
+    [, metrics [B, 3]]).  The padded candidates of one impression all have the same inputs and therefore the same logit, so each
+    impression sends its ``n_b`` live candidates plus -- where it keeps ``e'_b > 0`` padded columns after the common trim -- ONE
+    representative padded candidate through the models (``N = sum_b (n_b + [e'_b > 0])`` rows instead of ``B * T'``), and the
+    ragged scoring tail lets that candidate's ``exp`` enter the first softmax ``e'_b`` times (``compact.compact_scores_reference``).
+    The scores agree with predict_ranked's to fp32 rounding of the logits, not bitwise; ranks of nearly tied scores may differ.
+
+    The plan is built on the host from ``empty_num`` where it lives: a DataLoader's CPU tensor costs no device synchronisation and
+    one pinned upload of the index tables; a device-resident ``empty_num`` costs ONE synchronise (its copy to the host).
+    A batch in which no row keeps padding after the trim (``N = B * T'``) is handed to predict_ranked itself -- the choice is
+    made from the input; ``force_compact`` keeps the ragged kernels even then (tests, measurements).  The gather launch checks
+    that the kept padded rows of every impression are bitwise alike and raises ``ops.pad_error_flag`` otherwise:
+    ``ops.check_pad_errors(device)`` turns it into a ValueError (score_dataset does after its last batch).
+    Inference only; a model whose attention arithmetic is bf16 / bf16x3 is refused (RuntimeError)."""
+    from . import compact
+    xh, xt, xg = batch["x_history"], batch["x_target"], batch["x_global"]
+    ops._require_gpu(xh, xt, xg)
+    plan = compact.build_plan(batch["empty_num"], xt.shape[1])
+    if plan.B != xt.shape[0]:
+        raise ValueError(f"predict_ranked_compact: empty_num has {plan.B} entries for {xt.shape[0]} impressions")
+    if plan.N == 0 or (plan.dense and not force_compact):
+        return predict_ranked(models, batch, with_metrics=with_metrics)
+    tabs = plan.upload(xt.device)
+    xt_c, xg_c = ops.compact_gather(xt, xg, tabs["cand_off"], tabs["pad_mult"], plan.trim, plan.N)
+    logits = [m.eval().forward_compact(xh, xt_c, xg_c, plan) for m in models]
+    label = None
+    if with_metrics:
+        label = batch["label"][:, :plan.Tp].to(xt.device, non_blocking=True)
+    scores, rank, live, metrics = ops.ensemble_rank_ragged(logits, tabs["cand_off"], tabs["pad_mult"], label, plan.Tp)
+    return (scores, rank, live, metrics) if with_metrics else (scores, rank, live)
+
+
+@torch.no_grad()
 def validate_ranked(models, batches):
     """validate() with the ranking metrics: {"auc", "top1", "mrr", "ndcg5", "ndcg10"}, means over the impressions of an iterable
     of device batches (with labels).  AUC and top-1 come from ``row_auc`` on predict_ranked's scores; the sums are kept on the
@@ -291,10 +327,13 @@ def iter_dataset_batches(head_path, batch_size):
         yield data_io.collate(pending)
 
 
-def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions"):
+def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions", compact=False):
     """test.py's ``model_test`` + ``write_submission_file`` for a processed test set: -> path of ``<out_dir>/<name>.zip`` holding
     ``predictions.txt``.  Every batch goes through predict_ranked (ranks computed on the device) and write_predictions (one
-    device-to-host copy); nothing but the current batch and subvolume is held."""
+    device-to-host copy); nothing but the current batch and subvolume is held.
+    ``compact=True`` scores through predict_ranked_compact (no forward work on padded candidates); a batch whose padded rows are not
+    all alike raises ValueError after the last batch.  The default stays the dense path: the two are two correct fp32 evaluations
+    whose nearly tied scores may rank differently, so which one writes a submission is the caller's decision."""
     import os
     dev = next(models[0].parameters()).device
     os.makedirs(out_dir, exist_ok=True)
@@ -303,9 +342,11 @@ def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions")
     for batch in iter_dataset_batches(head_path, batch_size):
         tb = {k: torch.from_numpy(batch[k]).to(dev, non_blocking=True) for k in ("x_history", "x_target", "x_global")}
         tb["empty_num"] = torch.from_numpy(batch["empty_num"])         # stays on the host: the trim costs no synchronisation
-        _scores, rank, live = predict_ranked(models, tb)
+        _scores, rank, live = (predict_ranked_compact if compact else predict_ranked)(models, tb)
         write_predictions(txt_path, batch["impression_id"], rank, live, append=True)
     ops.check_index_errors(dev)
+    if compact:
+        ops.check_pad_errors(dev)
     return zip_predictions(txt_path, os.path.join(out_dir, f"{name}.zip"))
 
 

@@ -264,6 +264,51 @@ class UserModel(nn.Module):
             gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)     # the gate multiplies the RAW concat
         return self.out_mlp(self.mlp(gated)).reshape(B, T)
 
+    def forward_compact(self, x_history, xt_compact, xg_compact, plan):
+        """Inference on ragged candidate lists (compact scoring path): ``xt_compact`` [N, cols] and
+        ``xg_compact`` [N, 3] are the plan's rows of x_target / x_global (``ops.compact_gather``), ``plan`` a
+        ``compact.CompactPlan``; -> logits [N] fp32 (a strided view of the last GEMM's output).  The logit of a compact candidate
+        is the one forward() gives its source cell: everything but the two attentions and the pool is row-wise and runs on the N
+        rows unchanged, and eval-mode BatchNorm uses the running statistics.  Eval mode only: in training mode BatchNorm's
+        batch statistics would see N rows where the reference sees B * T.  fp32 attention arithmetic only."""
+        if self.training:
+            raise RuntimeError("UserModel.forward_compact is inference only: call .eval() first (training-mode BatchNorm takes its "
+                               "statistics over the rows of the launch, and the compact path drops the padded ones)")
+        inv = self.invariant_interest_model
+        ops._require_gpu(x_history, xt_compact, xg_compact)
+        B, H, N = x_history.shape[0], x_history.shape[1], xt_compact.shape[0]
+        if plan.B != B or plan.N != N or xg_compact.shape[0] != N:
+            raise RuntimeError(f"forward_compact: plan for {plan.B} impressions / {plan.N} rows, got {B} / {N} target and {xg_compact.shape[0]} global rows")
+        if B * H == 0 or N == 0:
+            raise RuntimeError("cannot reshape tensor of 0 elements (empty batch / history / candidate list)")
+        for att in (inv.label_attention, inv.text_img_attention):
+            mlp = getattr(att, "mlp", None)
+            if not (type(att) is PointwiseAttentionExpanded and isinstance(mlp, MLP) and isinstance(mlp.activation, nn.GELU)
+                    and mlp.activation.approximate == "none"):
+                raise RuntimeError("forward_compact: the ragged attention implements the reference default (PointwiseAttentionExpanded, exact GELU) only")
+        tabs = plan.upload(x_history.device)
+        with torch.no_grad():
+            sen = inv.sentiment_embedding[0]
+            tables = (inv.category_embedding[0].weight, sen.weight, sen.bias, inv.type_embedding[0].weight, inv.year_embedding[0].weight,
+                      inv.month_embedding[0].weight, inv.day_embedding[0].weight, inv.hour_embedding[0].weight)
+            d = inv._dims
+            lab_h, ti_h = ops.frontend(x_history, True, d.n_subcat, d.pca_vector, *tables)             # [B,H,D_l+2], [B,H,P]
+            lab_t, ti_t = ops.frontend(xt_compact.unsqueeze(0), False, d.n_subcat, d.pca_vector, *tables)      # [1,N,D_l], [1,N,P]
+            lab_h = ops.linear(lab_h, inv.w1.weight, inv.w1.bias)
+            pooled = []
+            for att, t, h in ((inv.label_attention, lab_t[0], lab_h), (inv.text_img_attention, ti_t[0], ti_h)):
+                m = att.mlp
+                pooled.append(ops.attend_pool_ragged(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, tabs["cand_imp"],
+                                                     tabs["cand_off"], plan.max_count, mma=att.mma))
+            eu_L = self.instant_interest_model(xg_compact)
+            rows = ops.concat_last((pooled[0], pooled[1], eu_L, lab_t[0], ti_t[0]))                 # [N, width]
+            g = self.gate
+            if isinstance(g.activation, nn.GELU) and g.activation.approximate == "none":
+                gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias)
+            else:
+                gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)
+            return self.out_mlp(self.mlp(gated)).reshape(N)
+
     def loss(self, id, out, label, alpha=0.95):
         # any number of candidates: one wave per impression, in registers up to T = 256, re-reading the row beyond (csrc/pool_loss.hip)
         return ops.softmax_bce_loss(out, self.delta, label, id, alpha)

@@ -64,6 +64,10 @@ SIGNATURES = {
     "nrm_row_auc": (_c_i, [_c_fp] * 3 + [_c_i, _c_i] + [_c_fp] * 3),
     "nrm_ensemble_rank_max_candidates": (_c_i, []),
     "nrm_ensemble_rank": (_c_i, [_c_fp] * 3 + [_c_i, _c_fp, _c_fp, _c_i, _c_i] + [_c_fp] * 5),      # the first three: HOST arrays
+    "nrm_compact_gather": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp]),
+    "nrm_pwattn_fwd_ragged": (_c_i, [_c_fp] * 10 + [_c_i] * 6 + [_c_fp]),
+    "nrm_pool_bmm_ragged": (_c_i, [_c_fp] * 4 + [_c_i] * 5 + [_c_fp]),
+    "nrm_ensemble_rank_ragged": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i] + [_c_fp] * 5),     # the first two: HOST arrays
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,
                                  _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp]),

@@ -1828,6 +1828,168 @@ ensemble_rank = _op("ensemble_rank", "(Tensor[] logits, Tensor? empty, Tensor? l
                     _ensemble_rank_impl, _ensemble_rank_fake)
 
 
+# ------------------------------------------------------------------------------------------------ compact scoring path (inference)
+# Ragged candidate lists (compact.build_plan): N compact candidate rows instead of B * T'.  Tables are int32 device tensors:
+# cand_off [B + 1], cand_imp [N], pad_mult [B].  Everything row-wise between these ops (front end, dense layers, gate, MLPs) is the
+# ordinary op on N rows.
+_pad_error_flag = {}
+
+
+def pad_error_flag(device):
+    """int32 flag in pinned host memory, set to 1 by ``compact_gather`` when a padded candidate row that the batch keeps differs
+    from its row's representative (the compact path's identity needs them all alike) or the plan's tables do not add up.  Same
+    mechanics as ``index_error_flag``: written by the device in the error case only, readable at any time; one per device."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    key = str(device)
+    if key not in _pad_error_flag:
+        _pad_error_flag[key] = torch.zeros(1, dtype=torch.int32).pin_memory()
+    return _pad_error_flag[key]
+
+
+def check_pad_errors(device="cuda"):
+    """Wait for the device, then turn a raised padding flag into a ValueError (and clear it)."""
+    device = torch.device(device)
+    flag = pad_error_flag(device)
+    torch.cuda.synchronize(device if device.index is not None else None)
+    if int(flag[0]):
+        flag.zero_()
+        raise ValueError("compact scoring: a padded candidate row differs from the other padded rows of its impression (or the "
+                         "plan does not match the batch): the padded logits are not all alike, score this data with the dense path")
+
+
+def _tab(t):
+    return t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
+
+
+def _compact_gather_impl(x_target, x_global, cand_off, pad_mult, trim, N):
+    """x_target [B, T, ct], x_global [B, T, cg] (float64 or float32, kept) -> (xt [N, ct], xg [N, cg]): the plan's rows, one launch,
+    which also checks the kept padded columns against their representative (``pad_error_flag``)."""
+    _require_gpu(x_target, x_global, cand_off, pad_mult)
+    fix = lambda x: (x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)).contiguous()      # noqa: E731
+    xt, xg = fix(x_target), fix(x_global)
+    B, T = xt.shape[0], xt.shape[1]
+    if xt.dim() != 3 or xg.dim() != 3 or tuple(xg.shape[:2]) != (B, T) or tuple(cand_off.shape) != (B + 1,) or tuple(pad_mult.shape) != (B,):
+        raise RuntimeError(f"compact_gather: x_target {tuple(xt.shape)}, x_global {tuple(xg.shape)}, cand_off {tuple(cand_off.shape)}, "
+                           f"pad_mult {tuple(pad_mult.shape)} do not agree")
+    out_t = torch.empty(N, xt.shape[2], dtype=xt.dtype, device=xt.device)
+    out_g = torch.empty(N, xg.shape[2], dtype=xg.dtype, device=xt.device)
+    if B * T == 0:
+        return out_t, out_g
+    native.call("nrm_compact_gather", native.ptr(xt), xt.shape[2], 1 if xt.dtype == torch.float64 else 0,
+                native.ptr(xg), xg.shape[2], 1 if xg.dtype == torch.float64 else 0, native.ptr(_tab(cand_off)), native.ptr(_tab(pad_mult)),
+                B, T, int(trim), int(N), native.ptr(out_t), native.ptr(out_g), native.ptr(pad_error_flag(xt.device)), native.stream_ptr())
+    return out_t, out_g
+
+
+def _compact_gather_fake(x_target, x_global, cand_off, pad_mult, trim, N):
+    f = lambda x: x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32      # noqa: E731
+    return (x_target.new_empty((N, x_target.shape[2]), dtype=f(x_target)), x_global.new_empty((N, x_global.shape[2]), dtype=f(x_global)))
+
+
+compact_gather = _op("compact_gather", "(Tensor x_target, Tensor x_global, Tensor cand_off, Tensor pad_mult, int trim, int N) -> (Tensor, Tensor)",
+                     _compact_gather_impl, _compact_gather_fake)
+
+
+def _attend_pool_ragged_fwd_impl(t, h, w1, b1, w2, b2, cand_imp, cand_off, max_count, mma):
+    """Ragged attention + pool as one node (inference only, no z): t [N, D] compact candidate rows, h [B, H, D] ->
+    (pooled [N, D], s [N, H]) with s[c, :] the pointwise attention scores of candidate c against the history of impression
+    cand_imp[c] and pooled[c, :] = sum_h s[c, h] h[cand_imp[c], h, :].  fp32 arithmetic only."""
+    _require_gpu(t, h, w1, b1, w2, b2, cand_imp, cand_off)
+    if mma != MMA_F32:
+        raise RuntimeError("compact scoring: the ragged attention forward has fp32 arithmetic only; this attention is set to "
+                           f"{ {MMA_BF16: 'bf16', MMA_BF16X3: 'bf16x3'}.get(mma, mma)} -- score with the dense path, or set the attention "
+                           "arithmetic to 'f32'")
+    N, D = t.shape
+    B, H = h.shape[0], h.shape[1]
+    if h.shape[2] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or tuple(cand_imp.shape) != (N,) or tuple(cand_off.shape) != (B + 1,):
+        raise RuntimeError(f"ragged attention: target {tuple(t.shape)}, history {tuple(h.shape)}, fc1 {tuple(w1.shape)}, cand_imp "
+                           f"{tuple(cand_imp.shape)}, cand_off {tuple(cand_off.shape)} do not agree (feature width must be a multiple of 4)")
+    w1_arg = w1
+    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
+    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
+    s = torch.empty(N, H, dtype=torch.float32, device=t.device)
+    pooled = torch.empty(N, D, dtype=torch.float32, device=t.device)
+    if N == 0 or B * H == 0:
+        return pooled.zero_(), s.zero_()
+    cand_imp, cand_off = _tab(cand_imp), _tab(cand_off)
+    own = w1 if w1 is w1_arg else None
+    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
+    u, _ = _gemm_nt(h.reshape(B * H, D), w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)     # [B*H, D]
+    v, _ = _gemm_nt(t, w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)                      # [N, D]
+    st = native.stream_ptr()
+    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
+    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
+    _count_flops("contraction", 2.0 * N * H * D * D)
+    native.call("nrm_pwattn_fwd_ragged", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v), native.ptr(packed), native.ptr(w2v),
+                native.ptr(b2), native.ptr(s), native.ptr(cand_imp), native.ptr(cand_off), B, N, int(max_count), H, D, mma, st,
+                tag="pwattn_fwd_ragged")
+    native.call("nrm_pool_bmm_ragged", native.ptr(s), native.ptr(h), native.ptr(pooled), native.ptr(cand_off), B, N, int(max_count), H, D, st)
+    return pooled, s
+
+
+attend_pool_ragged_fwd = _op("attend_pool_ragged_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
+                             "Tensor cand_imp, Tensor cand_off, int max_count, int mma) -> (Tensor, Tensor)", _attend_pool_ragged_fwd_impl,
+                             lambda t, h, w1, b1, w2, b2, ci, co, mc, mma: (t.new_empty(tuple(t.shape), dtype=torch.float32),
+                                                                            t.new_empty((t.shape[0], h.shape[1]), dtype=torch.float32)))
+
+
+def attend_pool_ragged(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias, cand_imp, cand_off, max_count, mma=None):
+    """[N, D] compact candidate rows x [B, H, D] -> pooled [N, D] (inference; feature widths that are not a multiple of 4 are
+    zero-padded as in ``pointwise_attention_scores``).  A bf16 / bf16x3 attention arithmetic is refused."""
+    D = target.shape[-1]
+    args = (target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
+    _require_gpu(*args)
+    if D % 4:
+        P = _pad4(D) - D
+        pad = torch.nn.functional.pad
+        blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]
+        args = (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
+                pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
+    with torch.no_grad():
+        return attend_pool_ragged_fwd(*args, cand_imp, cand_off, int(max_count), resolve_mma(mma))[0][:, :D]
+
+
+def _ensemble_rank_ragged_impl(logits, cand_off, pad_mult, label, T):
+    """The scoring tail on compact logits (C ABI nrm_ensemble_rank_ragged): ``logits`` = one [N] fp32 vector per model (read by stride
+    where it lies), impression b owns the entries cand_off[b] .. cand_off[b + 1] - 1, the last of which stands for pad_mult[b] padded
+    columns; outputs are the dense ones of ``ensemble_rank`` for T columns."""
+    import ctypes
+    logits = list(logits)
+    _require_gpu(*logits, cand_off, pad_mult, label)
+    if not logits or any(x.dim() != 1 or x.shape != logits[0].shape for x in logits):
+        raise RuntimeError(f"ensemble_rank_ragged: needs 1 .. 8 logit vectors of one [N] shape, got {[tuple(x.shape) for x in logits]}")
+    N, B = logits[0].shape[0], pad_mult.shape[0]
+    xs = [x if (x.dtype == torch.float32 and (N <= 1 or x.stride(0) >= 1)) else _f32c(x) for x in logits]
+    M, dev = len(xs), xs[0].device
+    if tuple(cand_off.shape) != (B + 1,):
+        raise RuntimeError(f"ensemble_rank_ragged: cand_off has shape {tuple(cand_off.shape)}, expected ({B + 1},)")
+    if label is not None and tuple(label.shape) != (B, T):
+        raise RuntimeError(f"ensemble_rank_ragged: label has shape {tuple(label.shape)}, expected ({B}, {T})")
+    score = torch.empty(B, T, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, T, dtype=torch.int32, device=dev)
+    live = torch.empty(B, dtype=torch.int32, device=dev)
+    metrics = torch.empty(B if label is not None else 0, 3, dtype=torch.float32, device=dev)
+    y = _f32c(label) if label is not None else None
+    ptrs = (ctypes.c_void_p * M)(*[x.data_ptr() for x in xs])
+    cols = (ctypes.c_long * M)(*[x.stride(0) if N > 1 else 1 for x in xs])
+    native.call("nrm_ensemble_rank_ragged", ptrs, cols, M, native.ptr(_tab(cand_off)), native.ptr(_tab(pad_mult)), N,
+                native.ptr(y) if y is not None else None, B, int(T), native.ptr(score), native.ptr(rank), native.ptr(live),
+                native.ptr(metrics) if y is not None else None, native.stream_ptr())
+    return score, rank, live, metrics
+
+
+def _ensemble_rank_ragged_fake(logits, cand_off, pad_mult, label, T):
+    x, B = logits[0], pad_mult.shape[0]
+    return (x.new_empty((B, T), dtype=torch.float32), x.new_empty((B, T), dtype=torch.int32), x.new_empty((B,), dtype=torch.int32),
+            x.new_empty((B if label is not None else 0, 3), dtype=torch.float32))
+
+
+ensemble_rank_ragged = _op("ensemble_rank_ragged", "(Tensor[] logits, Tensor cand_off, Tensor pad_mult, Tensor? label, int T) -> "
+                           "(Tensor score, Tensor rank, Tensor live, Tensor metrics)", _ensemble_rank_ragged_impl, _ensemble_rank_ragged_fake)
+
+
 def _adam_step_impl(param, grad, exp_avg, exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, zero_grad):
     """train.py:48,73-75 over one flat buffer: Adam(lr, weight_decay) + optional zero_grad in one launch; the step
     counter lives in ``state`` on the device (hipGraph-capturable)."""
@@ -1844,4 +2006,5 @@ adam_step = _op("adam_step", "(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp
 OPS = ("pwattn_fwd", "pwattn_bwd", "linear_fwd", "linear_bwd", "small_linear_relu_fwd", "small_linear_relu_bwd", "mlp_gelu_fwd", "mlp_gelu_bwd", "batch_norm_stats", "batch_norm_apply",
        "batch_norm_bwd", "gate_block_fwd", "gate_block_bwd", "concat_cols",
        "weighted_pool_fwd", "weighted_pool_bwd", "attend_pool_fwd", "attend_pool_bwd", "softmax_bce_loss", "frontend_fwd", "frontend_bwd",
-       "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "adam_step")
+       "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
+       "adam_step")
