@@ -88,6 +88,20 @@ int nrm_pwattn_pack_wp(const float* fc1_weight, int ld, int D, int mma, float* p
     return check_hip(nrm::pack_wp_launch(fc1_weight + 3 * (long)D, ld, D, pl, mma, packed, (hipStream_t)stream), "pack_wp");
 }
 
+// parameter block of the dense and the ragged forward: `cand` candidate rows in t / v (B T dense; N ragged, with T = 1), B H rows in h / u
+static nrm::FwdParams fwd_params(const float* t, const float* h, const float* u, const float* v, const float* packed_wp, const float* w2,
+                                 const float* b2, float* z, float* s, long cand, int T, int B, int H, int D, const nrm::FwdPlan& pl) {
+    nrm::FwdParams p;
+    p.t = t; p.h = h; p.u = u; p.v = v; p.wp = packed_wp; p.w2 = w2; p.b2 = b2; p.z = z; p.s = s;
+    p.M = cand * H; p.T = T; p.H = H; p.D = D;
+    p.ldt = D; p.ldh = D; p.ldu = D; p.ldv = D;
+    p.wp_bytes = (unsigned)(nrm_pwattn_packed_floats(D) * 4);
+    p.t_bytes = (unsigned)(cand * D * 4);
+    p.h_bytes = (unsigned)((long)B * H * D * 4);
+    p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
+    return p;
+}
+
 int nrm_pwattn_fwd(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
                    const float* w2, const float* b2, float* z, float* s,
                    int B, int T, int H, int D, int mma, nrm_stream_t stream) {
@@ -96,16 +110,9 @@ int nrm_pwattn_fwd(const float* t, const float* h, const float* u, const float* 
     if (!t || !h || !u || !v || !packed_wp || !w2 || !b2 || !s) return fail(NRM_EINVAL, "nrm_pwattn_fwd: null pointer");
     if (B == 0) return NRM_OK;
     const nrm::FwdPlan pl = nrm::pwattn_fwd_plan(D);
-    nrm::FwdParams p;
-    p.t = t; p.h = h; p.u = u; p.v = v; p.wp = packed_wp; p.w2 = w2; p.b2 = b2; p.z = z; p.s = s;
-    p.M = (long)B * T * H; p.T = T; p.H = H; p.D = D;
-    p.ldt = D; p.ldh = D; p.ldu = D; p.ldv = D;
-    p.wp_bytes = (unsigned)(nrm_pwattn_packed_floats(D) * 4);
-    p.t_bytes = (unsigned)((long)B * T * D * 4);
-    p.h_bytes = (unsigned)((long)B * H * D * 4);
     if (mma != NRM_MMA_F32 && !nrm::pwattn_fwd_uses_rw(D, mma))
         return fail(NRM_EINVAL, "nrm_pwattn_fwd: D=%d is too wide for the bf16 forward (one 16-column slice of W_p must fit the LDS)", D);
-    p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
+    const nrm::FwdParams p = fwd_params(t, h, u, v, packed_wp, w2, b2, z, s, (long)B * T, T, B, H, D, pl);
     return check_hip(nrm::pwattn_fwd_launch(p, pl, mma, (hipStream_t)stream), "pwattn_fwd");
 }
 
@@ -125,14 +132,7 @@ int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const 
     if (!t || !h || !u || !v || !packed_wp || !w2 || !b2 || !s || !cand_imp || !cand_off) return fail(NRM_EINVAL, "nrm_pwattn_fwd_ragged: null pointer");
     if (N == 0 || B == 0) return NRM_OK;
     const nrm::FwdPlan pl = nrm::pwattn_fwd_plan(D);
-    nrm::FwdParams p;
-    p.t = t; p.h = h; p.u = u; p.v = v; p.wp = packed_wp; p.w2 = w2; p.b2 = b2; p.z = nullptr; p.s = s;
-    p.M = (long)N * H; p.T = 1; p.H = H; p.D = D;
-    p.ldt = D; p.ldh = D; p.ldu = D; p.ldv = D;
-    p.wp_bytes = (unsigned)(nrm_pwattn_packed_floats(D) * 4);
-    p.t_bytes = (unsigned)((long)N * D * 4);
-    p.h_bytes = (unsigned)((long)B * H * D * 4);
-    p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
+    const nrm::FwdParams p = fwd_params(t, h, u, v, packed_wp, w2, b2, nullptr, s, N, 1, B, H, D, pl);
     nrm::RaggedTabs rg;
     rg.cand_imp = cand_imp; rg.cand_off = cand_off; rg.B = B; rg.N = N; rg.max_count = max_count;
     return check_hip(nrm::pwattn_fwd_ragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_ragged");

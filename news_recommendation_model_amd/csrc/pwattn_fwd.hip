@@ -309,24 +309,17 @@ FwdPlan pwattn_fwd_plan(int D) {
     return pl;
 }
 
-template <int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>
-static hipError_t launch_fwd_t(const FwdParams& p, hipStream_t st) {
+// RAGGED: fp32 arithmetic, no z store (the only ragged instantiations there are)
+template <bool RAGGED, int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>
+static hipError_t launch_fwd_t(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
     constexpr int BM = NW * MT * 16;
     const long nblk = (p.M + BM - 1) / BM;
     if (nblk <= 0) return hipSuccess;
     if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
-    if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, RaggedTabs{});
-    else     hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, RaggedTabs{});
-    return hipGetLastError();
-}
-
-template <int NT, int MT, int WPE = 2, bool CT = false>
-static hipError_t launch_fwd_ragged_t(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
-    constexpr int BM = 4 * MT * 16;
-    const long nblk = (p.M + BM - 1) / BM;
-    if (nblk <= 0) return hipSuccess;
-    if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, 4, true>), dim3((unsigned)nblk), dim3(256), 0, st, p, rg);
+    const dim3 grid((unsigned)nblk), block(NW * 64);
+    if constexpr (RAGGED) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true>), grid, block, 0, st, p, rg);
+    else if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), grid, block, 0, st, p, rg);
+    else          hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), grid, block, 0, st, p, rg);
     return hipGetLastError();
 }
 
@@ -340,46 +333,42 @@ static bool fwd_compact_t(int H, int block_rows = 64) {
     return H >= 16;
 }
 
+// the chunk-streaming kernel for the plan's tiles, dense or ragged
+template <bool RAGGED>
+static hipError_t fwd_dispatch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
+#define NRM_FWD(...) launch_fwd_t<RAGGED, __VA_ARGS__>(p, rg, st)
+    switch (pl.NT) {
+        case 4:  return NRM_FWD(4, 4);
+        case 6:  return NRM_FWD(6, 4);
+        case 8:  return NRM_FWD(8, 3);
+        case 10: return fwd_compact_t(p.H) ? NRM_FWD(10, 1, 4, true) : NRM_FWD(10, 1, 3);
+        case 12: return fwd_compact_t(p.H) ? NRM_FWD(12, 1, 4, true) : NRM_FWD(12, 1, 3);
+        case 13:
+            if (!fwd_compact_t(p.H, NRM_FWD_NW8 && !RAGGED ? 128 : 64)) return NRM_FWD(13, 1, 3);
+#if NRM_FWD_NW8
+            if constexpr (!RAGGED) return NRM_FWD(13, 1, 4, true, 8);   // tuning: 128-row workgroups of 8 waves, two per CU (dense only)
+            else
+#endif
+            return NRM_FWD(13, 1, 4, true);
+        case 14: return NRM_FWD(14, 2);
+        case 16: return NRM_FWD(16, 1);        // (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms)
+        case 20: return NRM_FWD(20, 1);
+        case 25: return NRM_FWD(25, 1);
+    }
+#undef NRM_FWD
+    return hipErrorInvalidValue;
+}
+
 hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st) {
     if (pwattn_fwd_uses_rw(p.D, mma)) return pwattn_fwd_rw_launch(p, mma, st);
-    switch (pl.NT) {
-        case 4:  return launch_fwd_t<4, 4>(p, st);
-        case 6:  return launch_fwd_t<6, 4>(p, st);
-        case 8:  return launch_fwd_t<8, 3>(p, st);
-        case 10: return fwd_compact_t(p.H) ? launch_fwd_t<10, 1, 4, true>(p, st) : launch_fwd_t<10, 1, 3>(p, st);
-        case 12: return fwd_compact_t(p.H) ? launch_fwd_t<12, 1, 4, true>(p, st) : launch_fwd_t<12, 1, 3>(p, st);
-        case 13:
-            if (!fwd_compact_t(p.H, NRM_FWD_NW8 ? 128 : 64)) return launch_fwd_t<13, 1, 3>(p, st);
-#if NRM_FWD_NW8
-            return launch_fwd_t<13, 1, 4, true, 8>(p, st);            // tuning: 128-row workgroups of 8 waves, two per CU
-#else
-            return launch_fwd_t<13, 1, 4, true>(p, st);
-#endif
-        case 14: return launch_fwd_t<14, 2>(p, st);
-        case 16: return launch_fwd_t<16, 1>(p, st);        // (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms)
-        case 20: return launch_fwd_t<20, 1>(p, st);
-        case 25: return launch_fwd_t<25, 1>(p, st);
-    }
-    return hipErrorInvalidValue;
+    return fwd_dispatch<false>(p, pl, RaggedTabs{}, st);
 }
 
 // Ragged candidate lists: the plan of the dense forward for the same D and H (same tiles, same image choice); widths whose whole
 // W_p is one resident slice (D <= 128) take the resident-W forms, as the dense forward does -- the packed image is the same.
 hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
     if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_ragged_launch(p, rg, st);
-    switch (pl.NT) {
-        case 4:  return launch_fwd_ragged_t<4, 4>(p, rg, st);
-        case 6:  return launch_fwd_ragged_t<6, 4>(p, rg, st);
-        case 8:  return launch_fwd_ragged_t<8, 3>(p, rg, st);
-        case 10: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<10, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<10, 1, 3>(p, rg, st);
-        case 12: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<12, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<12, 1, 3>(p, rg, st);
-        case 13: return fwd_compact_t(p.H) ? launch_fwd_ragged_t<13, 1, 4, true>(p, rg, st) : launch_fwd_ragged_t<13, 1, 3>(p, rg, st);
-        case 14: return launch_fwd_ragged_t<14, 2>(p, rg, st);
-        case 16: return launch_fwd_ragged_t<16, 1>(p, rg, st);
-        case 20: return launch_fwd_ragged_t<20, 1>(p, rg, st);
-        case 25: return launch_fwd_ragged_t<25, 1>(p, rg, st);
-    }
-    return hipErrorInvalidValue;
+    return fwd_dispatch<true>(p, pl, rg, st);
 }
 
 // bf16 forms: always the resident-W forward (pwattn_fwd_rw.hip).  fp32: only where the WHOLE W_p fits one LDS slice

@@ -541,8 +541,10 @@ static int rw_cus() {       // of the CURRENT device (a process may drive severa
     return cus > 0 ? cus : 256;
 }
 
+// The launchers take the dense and the ragged (compact scoring) form alike: rg != nullptr selects the RAGGED instantiation, which exists
+// for fp32 arithmetic without a z store only.
 template <int NTS>
-static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, hipStream_t st) {
+static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const RaggedTabs* rg, hipStream_t st) {
     const int ntile = (int)((p.M + 15) / 16);
     if (ntile <= 0) return hipSuccess;
     int wgs = rw_cus() / pl.nsplit;                                     // one persistent workgroup per CU, CUs shared evenly by the slices
@@ -554,37 +556,47 @@ static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, hipSt
         if (e != hipSuccess) return e;
     }
     const dim3 grid((unsigned)(wgs * pl.nsplit)), block(FB_WAVES * 64);
-#define NRM_RW(SZ, M_)                                                                                                   \
+#define NRM_RW(SZ, M_, RG)                                                                                               \
     {                                                                                                                    \
-        auto k = pwattn_fwd_rw_kernel<NTS, SZ, M_>;                                                                      \
+        auto k = pwattn_fwd_rw_kernel<NTS, SZ, M_, RG>;                                                                  \
         /* per launch: the attribute is per device, and a process may launch on more than one */                        \
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);  \
         if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, RaggedTabs{});                                           \
+        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, RG ? *rg : RaggedTabs{});                                \
     }
-    if (mma == 2)      { if (p.z) NRM_RW(true, 2) else NRM_RW(false, 2) }
-    else if (mma == 1) { if (p.z) NRM_RW(true, 1) else NRM_RW(false, 1) }
-    else               { if (p.z) NRM_RW(true, 0) else NRM_RW(false, 0) }
+    if (rg)            NRM_RW(false, 0, true)
+    else if (mma == 2) { if (p.z) NRM_RW(true, 2, false) else NRM_RW(false, 2, false) }
+    else if (mma == 1) { if (p.z) NRM_RW(true, 1, false) else NRM_RW(false, 1, false) }
+    else               { if (p.z) NRM_RW(true, 0, false) else NRM_RW(false, 0, false) }
 #undef NRM_RW
     return hipGetLastError();
 }
 
 int pwattn_fwd_rw_diag_flags() { return NRM_DIAG_RW ? 4 : 0; }
 
+// Grid rule of the walks.  `base` tasks (impression x 16 history rows) are cut along the candidates into `tsplit` parts until two rounds
+// of 8-wave workgroups are filled, while a part of a list of `len` candidates keeps at least `min_part` of them; NRM_FWD_TSPLIT overrides
+// the cut (read per launch), `clamp` bounds it.  In: wgs = the workgroups the chip takes; out: tsplit, and wgs shrunk to the tasks there are.
+static hipError_t walk_grid(long base, int len, int min_part, int clamp, int& wgs, int& tsplit) {
+    tsplit = 1;
+    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
+    else while (base * tsplit < 2L * wgs * 8 && len / (tsplit + 1) >= min_part) ++tsplit;
+    if (tsplit < 1) tsplit = 1;
+    if (tsplit > clamp) tsplit = clamp > 0 ? clamp : 1;
+    const long ntask = base * tsplit;
+    if (ntask > 0x7fffffffL) return hipErrorInvalidValue;             // the kernels count tasks in an int
+    if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
+    return hipSuccess;
+}
+
 template <int NTS, int KCH>
 static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hipStream_t st) {
     const int B = (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
     const long base = (long)B * nht;
     if (base <= 0) return hipSuccess;
-    int wgs = rw_cus() / pl.nsplit;
+    int wgs = rw_cus() / pl.nsplit, tsplit;
     if (wgs < 1) wgs = 1;
-    int tsplit = 1;
-    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
-    else while (base * tsplit < 2L * wgs * 8 && p.T / (tsplit + 1) >= 8) ++tsplit;
-    if (tsplit < 1) tsplit = 1;
-    if (tsplit > p.T) tsplit = p.T;
-    const long ntask = base * tsplit;
-    if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
+    if (hipError_t e = walk_grid(base, p.T, 8, p.T, wgs, tsplit)) return e;
     const size_t shm = (size_t)pl.k32 * pl.wimg * NTS * 1024;
     if (pl.nsplit > 1) {
         hipError_t e = hipMemsetAsync(p.s, 0, (size_t)p.M * sizeof(float), st);
@@ -604,108 +616,68 @@ static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hip
     return hipGetLastError();
 }
 
+// ragged: the same grid rule with the MEAN list length in T's place (the cut itself is per impression, in the kernel)
 template <int NTS>
-static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, hipStream_t st) {
-    const int B = (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
+static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const RaggedTabs* rg, hipStream_t st) {
+    const int B = rg ? rg->B : (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
     const long base = (long)B * nht;
-    if (base <= 0) return hipSuccess;
-    int wgs = 2 * rw_cus();                                             // two workgroups of 8 waves per CU
-    int tsplit = 1;
-    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
-    else while (base * tsplit < 2L * wgs * 8 && p.T / (tsplit + 1) >= 4) ++tsplit;
-    if (tsplit < 1) tsplit = 1;
-    if (tsplit > p.T) tsplit = p.T;
-    const long ntask = base * tsplit;
-    if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
+    if (base <= 0 || (rg && rg->N <= 0)) return hipSuccess;
+    int wgs = 2 * rw_cus(), tsplit;                                     // two workgroups of 8 waves per CU
+    if (hipError_t e = walk_grid(base, rg ? (rg->N + rg->B - 1) / rg->B : p.T, 4, rg ? rg->max_count : p.T, wgs, tsplit)) return e;
     const size_t shm = (size_t)pl.k32 * NTS * 1024;
     const dim3 grid((unsigned)wgs), block(512);
-    if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
-    else     hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
+    if (rg)       hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
+    else if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
+    else          hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
     return hipGetLastError();
 }
 
-// ragged walk: the same grid rule with the MEAN list length in T's place (the cut itself is per impression, in the kernel)
-template <int NTS>
-static hipError_t launch_walk_f32_ragged(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, hipStream_t st) {
-    const int nht = (p.H + 15) / 16;
-    const long base = (long)rg.B * nht;
-    if (base <= 0 || rg.N <= 0) return hipSuccess;
-    int wgs = 2 * rw_cus();
-    const int mean = (rg.N + rg.B - 1) / rg.B;
-    int tsplit = 1;
-    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
-    else while (base * tsplit < 2L * wgs * 8 && mean / (tsplit + 1) >= 4) ++tsplit;
-    if (tsplit < 1) tsplit = 1;
-    if (tsplit > rg.max_count) tsplit = rg.max_count > 0 ? rg.max_count : 1;
-    const long ntask = base * tsplit;
-    if (ntask > 0x7fffffffL) return hipErrorInvalidValue;
-    if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
-    const size_t shm = (size_t)pl.k32 * NTS * 1024;
-    hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), dim3((unsigned)wgs), dim3(512), shm, st, p, pl, wgs, tsplit, rg);
-    return hipGetLastError();
+// Which fp32 walk, if any, a width takes (NRM_FWD_WALK_F32=0|1 forces, read per launch): its NTS, or 0 for the tile-by-tile form
+static int walk_f32_nts(int D) {
+    const char* e = getenv("NRM_FWD_WALK_F32");
+    if ((e ? e[0] == '1' : true) && D == 64) return 4;
+    // D = 128: h + u + accumulators + v take 196 VGPRs (two waves per SIMD): not the default, NRM_FWD_WALK_F32=1 selects it
+    if (e && e[0] == '1' && D == 128) return 8;
+    return 0;
 }
 
-template <int NTS>
-static hipError_t launch_rw_ragged(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, hipStream_t st) {
-    const int ntile = (int)((p.M + 15) / 16);
-    if (ntile <= 0) return hipSuccess;
-    int wgs = rw_cus();
-    if ((long)wgs * FB_WAVES > ntile) wgs = (ntile + FB_WAVES - 1) / FB_WAVES;
-    const size_t shm = (size_t)pl.k32 * NTS * 1024;
-    auto k = pwattn_fwd_rw_kernel<NTS, false, 0, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)wgs), dim3(FB_WAVES * 64), shm, st, p, pl, wgs, rg);
-    return hipGetLastError();
+// the bf16 walks: NRM_FWD_WALK=0 keeps the tile-by-tile form (read once, at the first dense launch)
+static bool fwd_walk_enabled() {
+    static const bool on = [] { const char* e = getenv("NRM_FWD_WALK"); return !(e && e[0] == '0'); }();
+    return on;
 }
 
-// fp32 only, widths that are one resident slice (pwattn_fwd_uses_rw(D, 0)): the walk where the dense forward walks (D = 64; D = 128 with
-// NRM_FWD_WALK_F32=1), the tile-by-tile form otherwise
-hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
-    const RwPlan pl = pwattn_rw_plan(p.D, 0);
-    if (pl.nsplit != 1) return hipErrorInvalidValue;
-    if (p.D == pl.nts * 16) {
-        const char* e = getenv("NRM_FWD_WALK_F32");
-        if ((e ? e[0] == '1' : true) && p.D == 64) return launch_walk_f32_ragged<4>(p, pl, rg, st);
-        if (e && e[0] == '1' && p.D == 128) return launch_walk_f32_ragged<8>(p, pl, rg, st);
-    }
-    switch (pl.nts) {
-        case 1:  return launch_rw_ragged<1>(p, pl, rg, st);
-        case 2:  return launch_rw_ragged<2>(p, pl, rg, st);
-        case 3:  return launch_rw_ragged<3>(p, pl, rg, st);
-        case 4:  return launch_rw_ragged<4>(p, pl, rg, st);
-        case 5:  return launch_rw_ragged<5>(p, pl, rg, st);
-        case 6:  return launch_rw_ragged<6>(p, pl, rg, st);
-        case 8:  return launch_rw_ragged<8>(p, pl, rg, st);
-    }
-    return hipErrorInvalidValue;
-}
-
-hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st) {
+// rg != nullptr: ragged candidate lists -- fp32 only, widths that are one resident slice (pwattn_fwd_uses_rw(D, 0)); p.T = 1 and
+// p.M = N H, so the walk where the dense forward walks, the tile-by-tile form otherwise
+static hipError_t rw_dispatch(const FwdParams& p, int mma, const RaggedTabs* rg, hipStream_t st) {
     const RwPlan pl = pwattn_rw_plan(p.D, mma);
-    static const bool walk = [] { const char* e = getenv("NRM_FWD_WALK"); return !(e && e[0] == '0'); }();
-    // fp32: the walk for the widths that are one resident slice of whole 16-column tiles (NRM_FWD_WALK_F32=0|1 forces per launch)
-    if (mma == 0 && pl.nsplit == 1 && p.D == pl.nts * 16 && p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31)) {
-        const char* e = getenv("NRM_FWD_WALK_F32");
-        if ((e ? e[0] == '1' : true) && p.D == 64) return launch_walk_f32<4>(p, pl, st);
-        // D = 128: h + u + accumulators + v take 196 VGPRs (two waves per SIMD): not the default, NRM_FWD_WALK_F32=1 selects it
-        if (e && e[0] == '1' && p.D == 128) return launch_walk_f32<8>(p, pl, st);
+    if (rg && pl.nsplit != 1) return hipErrorInvalidValue;
+    const bool walk = !rg && fwd_walk_enabled();
+    const bool walkable = p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31);
+    // fp32: the walk for the widths that are one resident slice of whole 16-column tiles
+    if (mma == 0 && pl.nsplit == 1 && p.D == pl.nts * 16 && walkable) {
+        const int nts = walk_f32_nts(p.D);
+        if (nts == 4) return launch_walk_f32<4>(p, pl, rg, st);
+        if (nts == 8) return launch_walk_f32<8>(p, pl, rg, st);
     }
-    if (walk && mma != 0 && p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31)) {
+    if (walk && mma != 0 && walkable) {
         if (p.D == 256 && pl.nts == 8) return launch_walk<8, 8>(p, pl, mma, st);
         if (p.D == 128 && pl.nts == 8) return launch_walk<8, 4>(p, pl, mma, st);
         if (p.D == 64 && pl.nts == 4) return launch_walk<4, 2>(p, pl, mma, st);
     }
     switch (pl.nts) {
-        case 1:  return launch_rw<1>(p, pl, mma, st);
-        case 2:  return launch_rw<2>(p, pl, mma, st);
-        case 3:  return launch_rw<3>(p, pl, mma, st);
-        case 4:  return launch_rw<4>(p, pl, mma, st);
-        case 5:  return launch_rw<5>(p, pl, mma, st);
-        case 6:  return launch_rw<6>(p, pl, mma, st);
-        case 8:  return launch_rw<8>(p, pl, mma, st);
+        case 1:  return launch_rw<1>(p, pl, mma, rg, st);
+        case 2:  return launch_rw<2>(p, pl, mma, rg, st);
+        case 3:  return launch_rw<3>(p, pl, mma, rg, st);
+        case 4:  return launch_rw<4>(p, pl, mma, rg, st);
+        case 5:  return launch_rw<5>(p, pl, mma, rg, st);
+        case 6:  return launch_rw<6>(p, pl, mma, rg, st);
+        case 8:  return launch_rw<8>(p, pl, mma, rg, st);
     }
     return hipErrorInvalidValue;
 }
+
+hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st) { return rw_dispatch(p, mma, nullptr, st); }
+hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) { return rw_dispatch(p, 0, &rg, st); }
 
 }  // namespace nrm
