@@ -174,6 +174,21 @@ typedef struct nrm_slab_desc {
 } nrm_slab_desc;
 int nrm_slab_reduce_multi(const nrm_slab_desc* descs, int n, nrm_stream_t stream);
 
+/* ---- head fold (additive entry points, the ABI version is unchanged; reference models/user_model.py:34, out_mlp(mlp(gated))): mlp.fc2 (w_m2 [Q, R], b_m2 [Q]) feeds out_mlp.fc1
+ * (w_o1 [P, Q], b_o1 [P]) with no nonlinearity in between, so  z2 = a1 W'^T + b',  W' = w_o1 w_m2 [P, R],  b' = w_o1 b_m2 + b_o1.
+ * nrm_head_fold forms W' on the fp32 MFMA pipe and writes it straight into nrm_gemm_nt's packed layout in both orientations:
+ * packed_fwd = the image of W' (nrm_gemm_packed_floats(P, R, NRM_MMA_F32) floats: z2 = nrm_gemm_nt(a1, packed_fwd, N = P, K = R)),
+ * packed_bwd = the image of W'^T (nrm_gemm_packed_floats(R, P, ...): da1 = nrm_gemm_nt(dz2, packed_bwd, N = R, K = P)), and
+ * bias = b' [P].  The weights are contiguous, Q % 4 == 0, w_o1 16-byte aligned; b_o1 / b_m2 may be NULL. */
+int nrm_head_fold(const float* w_o1, const float* b_o1, const float* w_m2, const float* b_m2, int P, int Q, int R,
+                  float* packed_fwd, float* packed_bwd, float* bias, nrm_stream_t stream);
+/* the gradients of the four folded tensors from the (reduced) dwp = dz2^T a1 [P, ldp] and dbp = colsum(dz2) [P]:
+ * dw_o1 = dwp w_m2^T + dbp (x) b_m2 [P, Q] (out_mlp.fc1 saw mlp.fc2's output including its bias; b_m2 may be NULL),
+ * dw_m2 = w_o1^T dwp [Q, R], db_o1 = dbp, db_m2 = w_o1^T dbp [Q]; contiguous outputs, overwritten; a NULL output is not computed.
+ * ldp % 4 == 0, 16-byte aligned rows. */
+int nrm_head_fold_bwd(const float* dwp, int ldp, const float* dbp, const float* w_o1, const float* w_m2, const float* b_m2,
+                      int P, int Q, int R, float* dw_o1, float* dw_m2, float* db_o1, float* db_m2, nrm_stream_t stream);
+
 /* ---- BatchNorm1d over rows (reference models/user_model.py:18,32), N % 4 == 0, ld % 4 == 0.
  * nrm_colreduce mode 0: s0 += sum_r x;  1: s0 += sum_r (x-mean)^2;  2: s0 += sum_r dy, s1 += sum_r dy*(x-mean)*rstd */
 int nrm_colreduce(int mode, const float* x, const float* dy, const float* mean, const float* rstd,

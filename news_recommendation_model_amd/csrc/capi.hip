@@ -396,6 +396,30 @@ int nrm_slab_reduce_multi(const nrm_slab_desc* descs, int n, nrm_stream_t stream
     return check_hip(nrm::slab_reduce_multi_launch(ps.data(), n, (hipStream_t)stream), "slab_reduce_multi");
 }
 
+// head fold: W' = W_o1 W_m2, b' = W_o1 b_m2 + b_o1 (head.hip)
+int nrm_head_fold(const float* w_o1, const float* b_o1, const float* w_m2, const float* b_m2, int P, int Q, int R,
+                  float* packed_fwd, float* packed_bwd, float* bias, nrm_stream_t stream) {
+    if (!w_o1 || !w_m2 || !packed_fwd || !packed_bwd || !bias) return fail(NRM_EINVAL, "nrm_head_fold: null pointer");
+    if (P <= 0 || Q <= 0 || R <= 0 || Q % 4 || !al16(w_o1))
+        return fail(NRM_EINVAL, "nrm_head_fold: P=%d Q=%d R=%d (Q a multiple of 4, w_o1 16-byte aligned)", P, Q, R);
+    const nrm::GemmNtPlan pf = nrm::gemm_nt_plan(P), pb = nrm::gemm_nt_plan(R);
+    nrm::HeadFoldParams p = {};
+    p.wo = w_o1; p.wm = w_m2; p.bo = b_o1; p.bm = b_m2; p.img_f = packed_fwd; p.img_b = packed_bwd; p.bias = bias;
+    p.P = P; p.Q = Q; p.R = R; p.rows_f = pf.rows; p.kch_f = (R + 15) / 16; p.rows_b = pb.rows; p.kch_b = (P + 15) / 16;
+    return check_hip(nrm::head_fold_launch(p, (hipStream_t)stream), "head_fold");
+}
+
+int nrm_head_fold_bwd(const float* dwp, int ldp, const float* dbp, const float* w_o1, const float* w_m2, const float* b_m2,
+                      int P, int Q, int R, float* dw_o1, float* dw_m2, float* db_o1, float* db_m2, nrm_stream_t stream) {
+    if (!dwp || !dbp || !w_o1 || !w_m2) return fail(NRM_EINVAL, "nrm_head_fold_bwd: null pointer");
+    if (P <= 0 || Q <= 0 || R <= 0 || ldp % 4 || ldp < R || !al16(dwp))
+        return fail(NRM_EINVAL, "nrm_head_fold_bwd: P=%d Q=%d R=%d ldp=%d (ldp a multiple of 4 covering R, 16-byte aligned rows)", P, Q, R, ldp);
+    nrm::HeadSplitParams p = {};
+    p.dwp = dwp; p.ldp = ldp; p.dbp = dbp; p.wo = w_o1; p.wm = w_m2; p.bm = b_m2; p.dwo = dw_o1; p.dwm = dw_m2; p.dbo = db_o1; p.dbm = db_m2;
+    p.P = P; p.Q = Q; p.R = R;
+    return check_hip(nrm::head_fold_bwd_launch(p, (hipStream_t)stream), "head_fold_bwd");
+}
+
 // ------------------------------------------------------------------------------------------- BatchNorm
 static int check_bn(const char* fn, int R, int N, int ld) {
     if (R < 0 || N <= 0 || N % 4 || ld % 4 || ld < N) return fail(NRM_EINVAL, "%s: R=%d N=%d ld=%d (N, ld multiples of 4)", fn, R, N, ld);

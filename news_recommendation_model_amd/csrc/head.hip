@@ -303,4 +303,175 @@ hipError_t small_linear_relu_bwd_launch(const void* x, int x_is_f64, const float
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Head fold (reference models/user_model.py:34: out_mlp(mlp(gated))): no nonlinearity sits between mlp.fc2 [Q, R] and
+// out_mlp.fc1 [P, Q], so the step evaluates  z2 = a1 W'^T + b'  with  W' = W_o1 W_m2 [P, R],  b' = W_o1 b_m2 + b_o1  and never
+// forms the Q-wide intermediate.  Both kernels are weight-sized: fp32 MFMA 16 x 16 tiles, operands straight from global memory.
+//
+//   head_fold_kernel      one workgroup per 16 x 16 tile of W'; its four waves take every fourth 16-wide chunk of the reduction
+//                         over Q (a chain of Q/64 chunk rounds per wave instead of Q/16), the partial tiles meet in LDS, and the
+//                         tile goes straight into gemm_nt's packed operand layout (pack_rows_kernel) TWICE: as rows of W' (the
+//                         forward) and as rows of W'^T (da1 = dz2 W').  Tiles of the images' zero padding are written too.
+//   head_fold_bwd_kernel  dW_o1 = dW' W_m2^T + db' (x) b_m2 [P, Q],  dW_m2 = W_o1^T dW' [Q, R]: one wave per 16 x 16 output tile (reduction over
+//                         R / P: 26 chunks at the flagship widths), plus db_o1 = db', db_m2 = W_o1^T db' on the last workgroups.
+__global__ __launch_bounds__(256) void head_fold_kernel(const HeadFoldParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ float part[4][16][17];
+    __shared__ float bpart[4][16];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    const int ti = blockIdx.x % p.ti, tj = blockIdx.x / p.ti;
+    const int i0 = ti * 16, j0 = tj * 16;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bs = 0.f;
+    if (i0 < p.P && j0 < p.R) {                                        // (workgroup-uniform) else: a tile of the padding
+        const int nch = (p.Q + 15) >> 4;
+        const int i = i0 + r16, j = j0 + r16;
+        const bool iok = i < p.P, jok = j < p.R;
+        const float* arow = p.wo + (size_t)(iok ? i : 0) * p.Q;
+        const bool want_b = tj == 0 && p.bm != nullptr;
+        // lane (r16, q) holds k = 16 c + 4 q + e in operand e: MFMA e of a chunk reduces over k = e, 4 + e, 8 + e, 12 + e
+        // four chunks per round: their 4 + 16 loads are in flight together (chunks past the end load nothing: k >= Q)
+        for (int c = wave; c < nch; c += 16) {
+            f32x4 a[4];
+            float b[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = 16 * (c + 4 * u) + 4 * q;
+                a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (iok && k < p.Q) a[u] = *reinterpret_cast<const f32x4*>(arow + k);      // Q % 4 == 0: the float4 is inside the row or past it
+#pragma unroll
+                for (int e = 0; e < 4; ++e) b[u][e] = (jok && k + e < p.Q) ? p.wm[(size_t)(k + e) * p.R + j] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = mfma16(a[u][e], b[u][e], acc);
+                const int k = 16 * (c + 4 * u) + 4 * q;
+                if (want_b && iok && k < p.Q) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bs = fmaf(a[u][e], p.bm[k + e], bs);
+                }
+            }
+        }
+    }
+    // lane holds W'[i0 + 4 q + e][j0 + r16] (this wave's share of the reduction)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) part[wave][4 * q + e][r16] = acc[e];
+    bs = sum_rows4(bs);
+    if (q == 0) bpart[wave][r16] = bs;
+    __syncthreads();
+    const int a = tid >> 4, b = tid & 15;
+    float v = (part[0][a][b] + part[1][a][b]) + (part[2][a][b] + part[3][a][b]);
+    if (i0 + a >= p.P || j0 + b >= p.R) v = 0.f;                       // the images' padding is exactly zero
+    part[0][a][b] = v;
+    __syncthreads();
+    {   // rows of W': packed[c = tj][row = i][16]
+        const int row = i0 + a;
+        if (row < p.rows_f && tj < p.kch_f)
+            p.img_f[((size_t)tj * p.rows_f + row) * 16 + 4 * ((b >> 2) ^ swz4(row)) + (b & 3)] = v;
+    }
+    {   // rows of W'^T: packed[c = ti][row = j][16]
+        const int row = j0 + a;
+        if (row < p.rows_b && ti < p.kch_b)
+            p.img_b[((size_t)ti * p.rows_b + row) * 16 + 4 * ((b >> 2) ^ swz4(row)) + (b & 3)] = part[0][b][a];
+    }
+    if (tj == 0 && tid < 16 && i0 + tid < p.P)
+        p.bias[i0 + tid] = ((bpart[0][tid] + bpart[1][tid]) + (bpart[2][tid] + bpart[3][tid])) + (p.bo ? p.bo[i0 + tid] : 0.f);
+#endif
+}
+
+hipError_t head_fold_launch(HeadFoldParams p, hipStream_t st) {
+    p.ti = p.rows_f / 16;                                              // rows_f >= 16 kch_b, rows_b >= 16 kch_f: the grid covers both images
+    p.tj = p.rows_b / 16;
+    if (p.ti < p.kch_b || p.tj < p.kch_f) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(head_fold_kernel, dim3((unsigned)(p.ti * p.tj)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void head_fold_bwd_kernel(const HeadSplitParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    if ((int)blockIdx.x >= p.mm_blocks) {                               // vector leg
+        const int c = ((int)blockIdx.x - p.mm_blocks) * 256 + tid;
+        if (p.dbm && c < p.Q) {
+            float s = 0.f;
+#pragma unroll 4
+            for (int i = 0; i < p.P; ++i) s = fmaf(p.wo[(size_t)i * p.Q + c], p.dbp[i], s);
+            p.dbm[c] = s;
+        }
+        if (p.dbo && c < p.P) p.dbo[c] = p.dbp[c];
+        return;
+    }
+    const int id = blockIdx.x * 4 + wave;
+    if (id >= p.na + p.nb) return;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int tq = (p.Q + 15) >> 4, tr = (p.R + 15) >> 4;
+    if (id < p.na) {
+        // dW_o1[i, c] = sum_j dW'[i, j] W_m2[c, j]
+        const int c0 = (id % tq) * 16, i0 = (id / tq) * 16;
+        const int i = i0 + r16, c = c0 + r16;
+        const bool iok = i < p.P, cok = c < p.Q;
+        const float* arow = p.dwp + (size_t)(iok ? i : 0) * p.ldp;
+        const float* brow = p.wm + (size_t)(cok ? c : 0) * p.R;
+        for (int k0 = 0; k0 < p.R; k0 += 16) {
+            const int k = k0 + 4 * q;
+            f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+            float b[4];
+            if (iok && k < p.R) a = *reinterpret_cast<const f32x4*>(arow + k);      // ldp = pad4(R): the float4 stays inside the row
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool kok = k + e < p.R;
+                a[e] = kok ? a[e] : 0.f;
+                b[e] = (cok && kok) ? brow[k + e] : 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = mfma16(a[e], b[e], acc);
+        }
+        // out_mlp.fc1 saw mlp.fc2's output INCLUDING its bias: dW_o1 = dz2^T (a1 W_m2^T + b_m2) = dW' W_m2^T + db' (x) b_m2
+        const float bmc = (p.bm && cok) ? p.bm[c] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (i0 + 4 * q + e < p.P && cok) p.dwo[(size_t)(i0 + 4 * q + e) * p.Q + c] = fmaf(p.dbp[i0 + 4 * q + e], bmc, acc[e]);
+    } else {
+        // dW_m2[c, j] = sum_i W_o1[i, c] dW'[i, j]
+        const int t = id - p.na;
+        const int j0 = (t % tr) * 16, c0 = (t / tr) * 16;
+        const int c = c0 + r16, j = j0 + r16;
+        const bool cok = c < p.Q, jok = j < p.R;
+        for (int k0 = 0; k0 < p.P; k0 += 16) {
+            const int k = k0 + 4 * q;
+            float a[4], b[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool kok = k + e < p.P;
+                a[e] = (cok && kok) ? p.wo[(size_t)(k + e) * p.Q + c] : 0.f;
+                b[e] = (jok && kok) ? p.dwp[(size_t)(k + e) * p.ldp + j] : 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = mfma16(a[e], b[e], acc);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + 4 * q + e < p.Q && jok) p.dwm[(size_t)(c0 + 4 * q + e) * p.R + j] = acc[e];
+    }
+#endif
+}
+
+hipError_t head_fold_bwd_launch(HeadSplitParams p, hipStream_t st) {
+    const int tp = (p.P + 15) / 16, tq = (p.Q + 15) / 16, tr = (p.R + 15) / 16;
+    p.na = p.dwo ? tp * tq : 0;
+    p.nb = p.dwm ? tq * tr : 0;
+    p.mm_blocks = (p.na + p.nb + 3) / 4;
+    const int nv = (p.dbm || p.dbo) ? ((p.Q > p.P ? p.Q : p.P) + 255) / 256 : 0;
+    if (p.mm_blocks + nv == 0) return hipSuccess;
+    hipLaunchKernelGGL(head_fold_bwd_kernel, dim3((unsigned)(p.mm_blocks + nv)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
 }  // namespace nrm

@@ -21,4 +21,25 @@ hipError_t small_linear_relu_fwd_launch(const void* x, int x_is_f64, const float
                                         int ldy, hipStream_t st);
 hipError_t small_linear_relu_bwd_launch(const void* x, int x_is_f64, const float* w, const float* b, const float* dy, int lddy,
                                         long R, int K, int N, float* dwb, hipStream_t st);
+// head fold (head.hip): W' = W_o1 W_m2 into both packed gemm_nt images, and the split of its gradient
+struct HeadFoldParams {
+    const float* wo; const float* wm;     // W_o1 [P, Q], W_m2 [Q, R], contiguous; Q % 4 == 0, W_o1 16-byte aligned
+    const float* bo; const float* bm;     // b_o1 [P], b_m2 [Q], or nullptr
+    float* img_f; float* img_b;           // packed rows of W' ([P x R]) and of W'^T ([R x P])
+    float* bias;                          // b' [P]
+    int P, Q, R;
+    int rows_f, kch_f, rows_b, kch_b;     // padded rows / 16-column chunks of the two images (gemm_nt_plan)
+    int ti, tj;                           // filled by head_fold_launch
+};
+hipError_t head_fold_launch(HeadFoldParams p, hipStream_t st);
+struct HeadSplitParams {
+    const float* dwp; int ldp;            // dW' [P, ldp], ldp % 4 == 0, 16-byte aligned rows, columns [R, ldp) ignored
+    const float* dbp;                     // db' [P]
+    const float* wo; const float* wm;
+    const float* bm;                      // b_m2 [Q] or nullptr
+    float* dwo; float* dwm; float* dbo; float* dbm;      // outputs (contiguous, overwritten); nullptr: not wanted
+    int P, Q, R;
+    int na, nb, mm_blocks;                // filled by head_fold_bwd_launch
+};
+hipError_t head_fold_bwd_launch(HeadSplitParams p, hipStream_t st);
 }  // namespace nrm

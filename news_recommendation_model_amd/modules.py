@@ -243,6 +243,32 @@ class UserModel(nn.Module):
         self.bce_loss = nn.BCELoss()
         self.softmax = nn.Softmax(dim=1)
 
+    def _tail(self, gated):
+        """out_mlp(mlp(gated)) (:34).  mlp.fc2 feeds out_mlp.fc1 with no nonlinearity in between: where the folded node applies
+        (ops.head_tail) the rows are never widened to mlp's output width and narrowed again."""
+        if gated.dim() == 2 and gated.shape[0] > 0 and self.head_fold_applies(gated.shape[1]):
+            m, o = self.mlp, self.out_mlp
+            return ops.head_tail(gated, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, o.fc1.weight, o.fc1.bias,
+                                 o.fc2.weight, o.fc2.bias)
+        return self.out_mlp(self.mlp(gated))
+
+    def head_fold_applies(self, width):
+        """Whether rows of ``width`` columns take the folded tail: fp32 dense arithmetic (and not NRM_HEAD_FOLD=0), both MLPs plain
+        ``MLP`` with exact GELU over plain ``nn.Linear`` layers, no forward or backward hook on either MLP or its layers, widths
+        the kernels take.  Never a matter of the row count: two runs of one model take the same path whatever their batch sizes."""
+        if not ops.head_fold_enabled():
+            return False
+        for mod in (self.mlp, self.out_mlp):
+            if type(mod) is not MLP or type(mod.fc1) is not nn.Linear or type(mod.fc2) is not nn.Linear:
+                return False
+            if not isinstance(mod.activation, nn.GELU) or mod.activation.approximate != "none":
+                return False
+            for layer in (mod, mod.fc1, mod.fc2, mod.activation):
+                if layer._forward_hooks or layer._forward_pre_hooks or layer._backward_hooks or layer._backward_pre_hooks:
+                    return False
+        m, o = self.mlp, self.out_mlp
+        return ops.head_fold_shapes_ok(width, m.fc1.weight, m.fc2.weight, m.fc2.bias, o.fc1.weight, o.fc1.bias, o.fc2.weight)
+
     def forward(self, x_history, x_target, x_global):
         inv = self.invariant_interest_model
         if type(inv) is UserInvariantInterestModel and not (inv._forward_hooks or inv._forward_pre_hooks):
@@ -262,7 +288,7 @@ class UserModel(nn.Module):
             gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias)
         else:
             gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)     # the gate multiplies the RAW concat
-        return self.out_mlp(self.mlp(gated)).reshape(B, T)
+        return self._tail(gated).reshape(B, T)
 
     def forward_compact(self, x_history, xt_compact, xg_compact, plan):
         """Inference on ragged candidate lists (compact scoring path): ``xt_compact`` [N, cols] and
@@ -307,7 +333,7 @@ class UserModel(nn.Module):
                 gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias)
             else:
                 gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)
-            return self.out_mlp(self.mlp(gated)).reshape(N)
+            return self._tail(gated).reshape(N)
 
     def loss(self, id, out, label, alpha=0.95):
         # any number of candidates: one wave per impression, in registers up to T = 256, re-reading the row beyond (csrc/pool_loss.hip)

@@ -49,6 +49,8 @@ SIGNATURES = {
     "nrm_gemm_tn": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_i, _c_fp, _c_i, _c_fp, _c_fp, _c_l, _c_i, _c_fp]),
     "nrm_gemm_pack_multi": (_c_i, [_c_fp, _c_i, _c_fp]),
     "nrm_slab_reduce_multi": (_c_i, [_c_fp, _c_i, _c_fp]),
+    "nrm_head_fold": (_c_i, [_c_fp] * 4 + [_c_i] * 3 + [_c_fp] * 4),
+    "nrm_head_fold_bwd": (_c_i, [_c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i] + [_c_fp] * 5),
     "nrm_colreduce": (_c_i, [_c_i] + [_c_fp] * 6 + [_c_i] * 3 + [_c_fp]),
     "nrm_bn_apply": (_c_i, [_c_fp] * 6 + [_c_i] * 3 + [_c_fp]),
     "nrm_bn_backward": (_c_i, [_c_fp] * 9 + [_c_i] * 4 + [_c_fp]),

@@ -194,12 +194,12 @@ def repack_persistent(owners=None):
         if mine is not None and id(owner) not in mine:
             continue
         live.append((ent, owner))
-    if not live:
-        return 0
-    arr = (native.PackDesc * len(live))(*[_pack_desc_of(ent, owner) for ent, owner in live])
-    native.call("nrm_gemm_pack_multi", _ctypes_ref(arr), len(live), native.stream_ptr())
-    for ent, owner in live:
-        ent.version, ent.epoch = owner._version, _packs.epoch
+    if live:
+        arr = (native.PackDesc * len(live))(*[_pack_desc_of(ent, owner) for ent, owner in live])
+        native.call("nrm_gemm_pack_multi", _ctypes_ref(arr), len(live), native.stream_ptr())
+        for ent, owner in live:
+            ent.version, ent.epoch = owner._version, _packs.epoch
+    _refold_persistent(mine)
     return len(live)
 
 
@@ -208,6 +208,7 @@ def invalidate_packed_weights():
     does not see (``param.data.copy_(...)``, a raw-pointer update): in-place ops on the parameter itself, ``load_state_dict``,
     ``.to()`` and ``torch.optim`` steps are noticed on their own, ``trainer.FlatAdam`` refreshes the images itself."""
     _packs.entries.clear()
+    _folds.clear()
     _packs.epoch += 1
     _packs.generation += 1
 
@@ -254,14 +255,17 @@ def _dense_mma(M, K, mma):
 
 
 def _gemm_nt(x, w_src, row_stride, col_stride, n_out, k_red, bias, epilogue, z=None, m=None, src2=None, sign2=0.0, owner=None,
-             mma=None):
+             mma=None, packed=None):
     """y[M, n_out] = epilogue(x[M, k_red] * Wlogical^T), Wlogical[r, c] = w_src[r*row_stride + c*col_stride]
     (+ sign2 * src2[same]); ``owner`` = the parameter w_src is a view of (its packed image is then cached); ``mma``: arithmetic
-    of the products (None = the dense default)."""
+    of the products (None = the dense default).  ``packed``: a ready fp32 image of Wlogical (the head fold's) instead of w_src."""
     st = native.stream_ptr()
     M = x.shape[0]
-    mma = _dense_mma(M, k_red, mma)
-    packed = _pack(w_src, row_stride, col_stride, n_out, k_red, src2, sign2, owner, mma)
+    if packed is not None:
+        mma = MMA_F32
+    else:
+        mma = _dense_mma(M, k_red, mma)
+        packed = _pack(w_src, row_stride, col_stride, n_out, k_red, src2, sign2, owner, mma)
     ldy = _pad4(n_out)
     y = torch.empty(M, ldy, dtype=torch.float32, device=x.device)
     if epilogue in (EPI_GELU, EPI_MUL):
@@ -329,11 +333,16 @@ def verify_deferred_targets(params):
     if not pend:
         return
     by_ptr = {p.data_ptr(): p for p in params}
+    targets = []
     for rec in pend:
-        p = by_ptr.get(rec["target"])
+        targets.append((rec["target"], rec["keep"][0]))
+        if rec.get("post") is not None:                 # the head fold's split writes four gradients after the flush
+            targets.extend(rec["post"]["targets"])
+    for target, storage in targets:
+        p = by_ptr.get(target)
         if p is None or not p.requires_grad:            # a frozen weight (its gradient was dropped by autograd) or an unknown one
             continue
-        if p.grad is None or p.grad.untyped_storage().data_ptr() != rec["keep"][0].data_ptr():
+        if p.grad is None or p.grad.untyped_storage().data_ptr() != storage.data_ptr():
             _deferred["pending"] = []
             _join_wgrad_stream()
             raise RuntimeError(
@@ -357,6 +366,9 @@ def flush_slab_reductions():
         if rec["vec"] is not None:
             d.vec, d.vec_out = rec["vec"].data_ptr(), rec["vec_out"]
     native.call("nrm_slab_reduce_multi", descs, len(pend), native.stream_ptr())
+    for rec in pend:
+        if rec.get("post") is not None:                 # reads what the launch above reduced
+            _head_fold_split(rec["post"])
 
 
 def _slab_reduce(ws, nsplit, nj, ldws, ni, out, out_is, out_js, out2=None, out2_is=0, out2_js=0, sign2=0.0,
@@ -1033,6 +1045,237 @@ def mlp_gelu(x, fc1_weight, fc1_bias, fc2_weight, fc2_bias, mul=None):
     m2 = mul.reshape(-1, mul.shape[-1]) if mul is not None else None
     y = mlp_gelu_fwd(x.reshape(-1, x.shape[-1]), fc1_weight, fc1_bias, fc2_weight, fc2_bias, m2)[0]
     return y.reshape(*lead, fc2_weight.shape[0])
+
+
+# ------------------------------------------------------------------------------------------------ head tail (fc2 folded into fc1)
+# out_mlp(mlp(x)) of models/user_model.py:34 with  W' = W_o1 W_m2,  b' = W_o1 b_m2 + b_o1  (no nonlinearity sits between mlp.fc2
+# and out_mlp.fc1; dW_o1 = dW' W_m2^T + db' (x) b_m2: fc1 saw fc2's bias too):  a1 = gelu(x W_m1^T + b_m1),  a2 = gelu(a1 W'^T + b'),  y = a2 W_o2^T + b_o2.  The four folded tensors stay
+# separate parameters; W' lives only as a pair of packed GEMM operands (nrm_head_fold) that follow the weights like every other
+# packed image (_PackedWeights), and its gradient dW' = dz2^T a1 is split into the four parameters' gradients by nrm_head_fold_bwd.
+class _FoldEntry:
+    __slots__ = ("img_f", "img_b", "bias", "owners", "ptrs", "versions", "epoch", "dims")
+
+
+_folds = {}
+
+
+def head_fold_enabled():
+    """NRM_HEAD_FOLD=0 restores the two-MLP evaluation (read per call: tests and A/B runs switch inside one process)."""
+    return _os.environ.get("NRM_HEAD_FOLD") != "0" and _default_dense_mma == MMA_F32
+
+
+def _fold_launch(ent, wo, bo, wm, bm):
+    P, Q, R = ent.dims
+    _count_flops("dense", 2.0 * P * Q * R)
+    native.call("nrm_head_fold", native.ptr(wo), native.ptr(bo) if bo is not None else None, native.ptr(wm),
+                native.ptr(bm) if bm is not None else None, P, Q, R, native.ptr(ent.img_f), native.ptr(ent.img_b),
+                native.ptr(ent.bias), native.stream_ptr())
+    ent.versions = tuple(t._version for t in (wo, bo, wm, bm) if t is not None)
+    ent.epoch = _packs.epoch
+
+
+def _fold_owners(ent):
+    """The live (wo, bo, wm, bm) of an entry, or None when one of them is gone or was re-seated."""
+    ts = tuple(r() if r is not None else None for r in ent.owners)
+    for t, r, ptr in zip(ts, ent.owners, ent.ptrs):
+        if r is not None and (t is None or t.data_ptr() != ptr):
+            return None
+    return ts
+
+
+def _head_fold_image(wo, bo, wm, bm):
+    """The fold entry (img_f: packed W', img_b: packed W'^T, bias: b') of out_mlp.fc1 = (wo, bo) over mlp.fc2 = (wm, bm):
+    folded again when a version counter or the pack epoch moved, reused untouched otherwise."""
+    import weakref
+    ts = (wo, bo, wm, bm)
+    key = tuple(t.data_ptr() if t is not None else 0 for t in ts)
+    ent = _folds.get(key)
+    if ent is not None:
+        live = _fold_owners(ent)
+        if live is None or any(a is not b for a, b in zip(live, ts)):
+            ent = None                                               # the addresses now belong to other tensors
+    if ent is not None and ent.epoch == _packs.epoch and ent.versions == tuple(t._version for t in ts if t is not None):
+        return ent
+    if ent is None:
+        lib = native.load()
+        (P, Q), R = wo.shape, wm.shape[1]
+        ent = _FoldEntry()
+        ent.dims = (int(P), int(Q), int(R))
+        ent.img_f = torch.empty(lib.nrm_gemm_packed_floats(P, R, MMA_F32), dtype=torch.float32, device=wo.device)
+        ent.img_b = torch.empty(lib.nrm_gemm_packed_floats(R, P, MMA_F32), dtype=torch.float32, device=wo.device)
+        ent.bias = torch.zeros(_pad4(P), dtype=torch.float32, device=wo.device)
+        ent.owners = tuple(weakref.ref(t) if t is not None else None for t in ts)
+        ent.ptrs = key
+        _folds[key] = ent
+        for t in (wo, wm):
+            weakref.finalize(t, _drop_fold, key, id(ent))            # the entry goes when its weights go
+    _fold_launch(ent, *ts)
+    return ent
+
+
+def _drop_fold(key, ident):
+    if id(_folds.get(key)) == ident:                                 # (the address may belong to a later entry by now)
+        _folds.pop(key, None)
+
+
+def _refold_persistent(mine):
+    """repack_persistent's share of the fold images: those whose tensors all belong to ``mine`` (ids; None = everyone's) are
+    folded again now -- inside a captured step this is where the image follows the optimizer -- the others lazily (epoch)."""
+    for key, ent in list(_folds.items()):
+        ts = _fold_owners(ent)
+        if ts is None:
+            _folds.pop(key, None)
+            continue
+        if mine is not None and not all(id(t) in mine for t in ts if t is not None):
+            continue
+        _fold_launch(ent, *ts)
+
+
+def _head_fold_split(rec):
+    """dW' / db' (reduced) -> the gradients of the four folded tensors (nrm_head_fold_bwd): one launch."""
+    P, Q, R = rec["dims"]
+    _count_flops("dense", 2.0 * P * Q * R * ((rec["dwo"] is not None) + (rec["dwm"] is not None)))
+    import ctypes
+    c = lambda v: ctypes.c_void_p(v) if v is not None else None          # noqa: E731  (destinations travel as raw addresses)
+    native.call("nrm_head_fold_bwd", native.ptr(rec["dwp"]), rec["dwp"].stride(0), native.ptr(rec["dbp"]), native.ptr(rec["wo"]),
+                native.ptr(rec["wm"]), native.ptr(rec["bm"]) if rec["bm"] is not None else None, P, Q, R, c(rec["dwo"]), c(rec["dwm"]), c(rec["dbo"]), c(rec["dbm"]), native.stream_ptr())
+
+
+def _head_fold_grads(dz2, a1, wo, bo, wm, bm, need_wo, need_bo, need_wm, need_bm):
+    """(dW_o1, db_o1, dW_m2, db_m2) -- None where not needed -- from dz2 [M, P] and a1 [M, R]: dW' = dz2^T a1 by the split-M GEMM and
+    its slab reduction, then the split.  Inside ``deferred_slab_reductions()`` the reduction is one of the step's deferred sets and
+    the split runs right behind that flush; the returned buffers are filled only then."""
+    (P, Q), R = wo.shape, wm.shape[1]
+    dev = dz2.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+    out = (f(P, Q) if need_wo else None, f(P) if need_bo else None, f(Q, R) if need_wm else None, f(Q) if need_bm else None)
+    ctx = _wgrad_stream(dz2, a1)
+    with ctx as side:
+        dwp = f(P, _pad4(R))                                             # zeroed by the GEMM launch itself, padding included
+        ws, cs, nsplit, ldws = _gemm_tn_slabs(dz2, a1, True, zero_out=dwp, mma=MMA_F32)
+        dbp = f(P)
+        _slab_reduce(ws, nsplit, R, ldws, P, dwp, dwp.stride(0), 1, vec=cs, vec_out=dbp)
+        if side:
+            for t in (dwp, ws, cs, dbp):
+                t.record_stream(ctx.main)
+    rec = dict(dims=(int(P), int(Q), int(R)), dwp=dwp, dbp=dbp, wo=wo, wm=wm, bm=bm,
+               **{k: (t.data_ptr() if t is not None else None) for k, t in zip(("dwo", "dbo", "dwm", "dbm"), out)})
+    if _deferred["on"]:
+        # (of the destinations only pointers and storages are kept: see the note on deferred records above)
+        rec["keep"] = tuple(t.untyped_storage() for t in out if t is not None)
+        rec["targets"] = [(p.data_ptr(), t.untyped_storage()) for p, t in zip((wo, bo, wm, bm), out) if p is not None and t is not None]
+        _deferred["pending"][-1]["post"] = rec
+    else:
+        _head_fold_split(rec)
+    return out
+
+
+def _head_tail_fwd_impl(x, w1, b1, wm, bm, wo, bo, w3, b3):
+    _require_gpu(x, w1, wm, wo, w3)
+    x = _rows(x)
+    o1, o3 = w1, w3
+    w1, w3 = _f32c(w1), _f32c(w3)
+    o1, o3 = (w1 if w1 is o1 else None), (w3 if w3 is o3 else None)
+    (N1, K1), (Q, R), (P, Q2), (N3, K3) = w1.shape, wm.shape, wo.shape, w3.shape
+    if x.shape[1] != K1 or R != N1 or Q2 != Q or K3 != P:
+        raise RuntimeError(f"head tail: input has {x.shape[1]} features; layers {K1}->{N1}, {R}->{Q}, {Q2}->{P}, {K3}->{N3} do not chain")
+    a1, z1 = _gemm_nt(x, w1, K1, 1, N1, K1, _f32c(b1) if b1 is not None else None, EPI_GELU, owner=o1)
+    ent = _head_fold_image(wo, bo, wm, bm)
+    a2, z2 = _gemm_nt(a1, None, 0, 0, P, R, ent.bias, EPI_GELU, packed=ent.img_f)
+    y, _ = _gemm_nt(a2, w3, K3, 1, N3, K3, _f32c(b3) if b3 is not None else None, EPI_BIAS, owner=o3)
+    return y, a1, z1, a2, z2
+
+
+def _head_tail_fwd_fake(x, w1, b1, wm, bm, wo, bo, w3, b3):
+    M, N1, P, N3 = x.shape[0], w1.shape[0], wo.shape[0], w3.shape[0]
+    return (_padded_empty(x, M, N3), _padded_empty(x, M, N1), _padded_empty(x, M, N1), _padded_empty(x, M, P), _padded_empty(x, M, P))
+
+
+head_tail_fwd = _op("head_tail_fwd", "(Tensor x, Tensor w1, Tensor? b1, Tensor wm, Tensor? bm, Tensor wo, Tensor? bo, Tensor w3, Tensor? b3) "
+                    "-> (Tensor, Tensor, Tensor, Tensor, Tensor)", _head_tail_fwd_impl, _head_tail_fwd_fake)
+
+
+def _head_tail_bwd_impl(dy, x, w1, wm, bm, wo, bo, w3, a1, z1, a2, z2, has_b1, has_b3, need_dx, need_wm, need_bm, need_wo, need_bo):
+    """dW_o2 / db_o2, dz2 = (dY W_o2) * gelu'(z2), the fold's four gradients from dW' = dz2^T a1, dz1 = (dz2 W') * gelu'(z1) against
+    the packed W'^T, then dW_m1 / db_m1 and dX: the GELU derivatives ride in the GEMM epilogues (NRM_EPI_DGELU) as in mlp_gelu_bwd."""
+    _require_gpu(dy, x, w1, wm, wo, w3)
+    o1, o3 = w1, w3
+    p1, p3 = w1, w3
+    x, w1, w3 = _rows(x), _f32c(w1), _f32c(w3)
+    o1, o3 = (w1 if w1 is o1 else None), (w3 if w3 is o3 else None)
+    (N1, K1), (Q, R), P, (N3, K3) = w1.shape, wm.shape, wo.shape[0], w3.shape
+    dy = _rows(dy)
+    dev = x.device
+    e = lambda: torch.empty((0,), dtype=torch.float32, device=dev)      # noqa: E731
+    dw3, db3 = _gemm_tn(dy, a2, has_b3, target=p3)
+    dz2, _ = _gemm_nt(dy, w3, 1, K3, K3, N3, None, EPI_DGELU, z=z2, owner=o3)
+    dwo = dbo = dwm = dbm = None
+    if need_wm or need_bm or need_wo or need_bo:
+        dwo, dbo, dwm, dbm = _head_fold_grads(dz2, a1, wo, bo, wm, bm, need_wo, need_bo, need_wm, need_bm)
+    ent = _head_fold_image(wo, bo, wm, bm)
+    dz1, _ = _gemm_nt(dz2, None, 0, 0, R, P, None, EPI_DGELU, z=z1, packed=ent.img_b)
+    dw1, db1 = _gemm_tn(dz1, x, has_b1, target=p1)
+    dx = _gemm_nt(dz1, w1, 1, K1, K1, N1, None, EPI_BIAS, owner=o1)[0] if need_dx else e()
+    opt = lambda t: t if t is not None else e()                          # noqa: E731
+    return dx, dw1, (db1 if has_b1 else e()), opt(dwm), opt(dbm), opt(dwo), opt(dbo), dw3, (db3 if has_b3 else e())
+
+
+def _head_tail_bwd_fake(dy, x, w1, wm, bm, wo, bo, w3, a1, z1, a2, z2, has_b1, has_b3, need_dx, need_wm, need_bm, need_wo, need_bo):
+    M, (N1, K1), (Q, R), P, (N3, K3) = x.shape[0], w1.shape, wm.shape, wo.shape[0], w3.shape
+    f = lambda *shape: x.new_empty(shape, dtype=torch.float32)          # noqa: E731
+    return (_padded_empty(x, M, K1) if need_dx else f(0), f(N1, K1), f(N1) if has_b1 else f(0), f(Q, R) if need_wm else f(0),
+            f(Q) if need_bm else f(0), f(P, Q) if need_wo else f(0), f(P) if need_bo else f(0), f(N3, K3), f(N3) if has_b3 else f(0))
+
+
+head_tail_bwd = _op("head_tail_bwd", "(Tensor dy, Tensor x, Tensor w1, Tensor wm, Tensor? bm, Tensor wo, Tensor? bo, Tensor w3, Tensor a1, "
+                    "Tensor z1, Tensor a2, Tensor z2, bool has_b1, bool has_b3, bool need_dx, bool need_wm, bool need_bm, bool need_wo, "
+                    "bool need_bo) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+                    _head_tail_bwd_impl, _head_tail_bwd_fake)
+
+
+def _head_tail_setup(ctx, inputs, output):
+    x, w1, b1, wm, bm, wo, bo, w3, b3 = inputs
+    y, a1, z1, a2, z2 = output
+    ctx.set_materialize_grads(False)
+    ctx.has = (b1 is not None, bm is not None, bo is not None, b3 is not None)
+    ctx.save_for_backward(x, w1, wm, wo, w3, a1, z1, a2, z2, *[b for b in (bm, bo) if b is not None])
+
+
+def _head_tail_backward(ctx, dy, _da1, _dz1, _da2, _dz2):
+    if dy is None:
+        return (None,) * 9
+    x, w1, wm, wo, w3, a1, z1, a2, z2, *rest = ctx.saved_tensors
+    has_b1, has_bm, has_bo, has_b3 = ctx.has
+    bm = rest.pop(0) if has_bm else None
+    bo = rest.pop(0) if has_bo else None
+    need = ctx.needs_input_grad
+    need_wm, need_bm, need_wo, need_bo = need[3], has_bm and need[4], need[5], has_bo and need[6]
+    dx, dw1, db1, dwm, dbm, dwo, dbo, dw3, db3 = head_tail_bwd(dy, x, w1, wm, bm, wo, bo, w3, a1, z1, a2, z2, has_b1, has_b3, need[0],
+                                                               need_wm, need_bm, need_wo, need_bo)
+    return ((dx if need[0] else None), dw1, (db1 if has_b1 else None), (dwm if need_wm else None), (dbm if need_bm else None),
+            (dwo if need_wo else None), (dbo if need_bo else None), dw3, (db3 if has_b3 else None))
+
+
+torch.library.register_autograd("nrm::head_tail_fwd", _head_tail_backward, setup_context=_head_tail_setup, lib=_LIB)
+
+
+def head_fold_shapes_ok(x_cols, w1, wm, bm, wo, bo, w3):
+    """Whether the folded tail takes these layers: fp32 contiguous weights that chain, both folded biases present, the input and
+    the folded width multiples of 4 (as for gate_block; the hidden widths may be anything)."""
+    ts = (w1, wm, bm, wo, bo, w3)
+    if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() for t in ts):
+        return False
+    if w1.dim() != 2 or wm.dim() != 2 or wo.dim() != 2 or w3.dim() != 2:
+        return False
+    return (x_cols == w1.shape[1] and x_cols % 4 == 0 and wm.shape[1] == w1.shape[0] and wo.shape[1] == wm.shape[0]
+            and wm.shape[0] % 4 == 0 and w3.shape[1] == wo.shape[0] and bm.shape[0] == wm.shape[0] and bo.shape[0] == wo.shape[0])
+
+
+def head_tail(x, w1, b1, wm, bm, wo, bo, w3, b3):
+    """out_mlp(mlp(x)) for 2-D rows x with mlp = (w1, b1 -> GELU -> wm, bm) and out_mlp = (wo, bo -> GELU -> w3, b3), both with the
+    default exact GELU: one autograd node, mlp.fc2 folded into out_mlp.fc1 (callers check head_fold_shapes_ok first)."""
+    _require_gpu(x, w1, wm, wo, w3)
+    return head_tail_fwd(x, w1, b1, wm, bm, wo, bo, w3, b3)[0]
 
 
 # ------------------------------------------------------------------------------------------------ BatchNorm1d
@@ -2003,7 +2246,7 @@ adam_step = _op("adam_step", "(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp
                 "float lr, float beta1, float beta2, float eps, float weight_decay, bool zero_grad) -> ()",
                 _adam_step_impl, lambda *a: None)
 
-OPS = ("pwattn_fwd", "pwattn_bwd", "linear_fwd", "linear_bwd", "small_linear_relu_fwd", "small_linear_relu_bwd", "mlp_gelu_fwd", "mlp_gelu_bwd", "batch_norm_stats", "batch_norm_apply",
+OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd", "linear_bwd", "small_linear_relu_fwd", "small_linear_relu_bwd", "mlp_gelu_fwd", "mlp_gelu_bwd", "batch_norm_stats", "batch_norm_apply",
        "batch_norm_bwd", "gate_block_fwd", "gate_block_bwd", "concat_cols",
        "weighted_pool_fwd", "weighted_pool_bwd", "attend_pool_fwd", "attend_pool_bwd", "softmax_bce_loss", "frontend_fwd", "frontend_bwd",
        "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
