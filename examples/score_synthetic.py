@@ -5,6 +5,7 @@ ensemble of two seeded models -- forwards, then ONE launch for softmax / mean / 
 
     python examples/score_synthetic.py --impressions 200 --batch 80
     python examples/score_synthetic.py --compact      (no forward work on padded candidates: evaluation.predict_ranked_compact)
+    python examples/score_synthetic.py --compact-history      (nor on padded history rows: predict_ranked_compact(history=True))
 """
 import argparse
 import os
@@ -29,6 +30,8 @@ def main():
     ap.add_argument("--emb", type=int, default=64)
     ap.add_argument("--out-dir", default=None)
     ap.add_argument("--compact", action="store_true", help="score ragged lists: live candidates + one representative padded candidate per impression")
+    ap.add_argument("--compact-history", action="store_true",
+                    help="--compact, and drop the trailing all-zero history rows as well (one representative padded history row per impression)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
@@ -49,7 +52,7 @@ def main():
                                            subvolume_item_num=max(1, N // 3))
     models = [trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=s, user_num=user_num)) for s in (1, 5)]
     # the one-line replacement of test.py's model_test + write_submission_file:
-    zip_path = evaluation.score_dataset(models, head, out_dir, batch_size=args.batch, compact=args.compact)
+    zip_path = evaluation.score_dataset(models, head, out_dir, batch_size=args.batch, compact=args.compact, compact_history=args.compact_history)
     with zipfile.ZipFile(zip_path) as z:
         lines = z.read("predictions.txt").decode("utf-8").splitlines()
     assert len(lines) == N

@@ -355,6 +355,37 @@ int nrm_pool_bmm_ragged(const float* s, const float* h, float* out, const int* c
 int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,
                              const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream);
 
+/* ---- history compaction (inference): the compact scoring path, ragged in the history too
+ * The reference's ETL writes every history as history_max_num rows and leaves the rows past the user's own all-zero; the model does
+ * not mask them (user_invariant_interest_model.py:77-78, 83-87: they are scored and pooled like any other row).  With
+ * L_b = 1 + the last history row of impression b that holds any non-zero bit, the rows j >= L_b have the same front-end row, the same
+ * u row and, for any candidate c, the same score, so K_b = L_b + [L_b < H] rows are kept -- the live ones and ONE representative
+ * padded row -- and pooled[c, :] = sum_{j < L_b} s[c, j] h[b, j, :] + (H - L_b) s[c, L_b] h[b, L_b, :].  Tables (int32, device):
+ * hist_off [B + 1] prefix sums of K_b, hist_mult [B] = H - L_b, tile_pre [B + 1] prefix sums of count_b ceil(K_b / 16) (count_b =
+ * cand_off[b + 1] - cand_off[b]); the scores of a compact candidate are ceil(K_b / 16) whole 16-row tiles of s [16 Mt], Mt = tile_pre[B].
+ * Every entry replaces work of user_invariant_interest_model.py:77-78, 83-87 on the padded rows.  Table entries are clamped to the arrays.
+ *
+ * nrm_history_len: hist_len[b] = L_b of x_history [B, H, cols] (float64 or float32, read as the front end reads them).  The test is
+ *   bitwise: a row holding -0.0 or a NaN is live, and an all-zero row below a live one is kept.  One pass; clears hist_len first.
+ * nrm_history_gather: xh_compact[hist_off[b] + j, :] = x_history[b, j, :] for j < K_b (bitwise); R = hist_off[B], k_max = max K_b.
+ * nrm_history_tiles: tile_tab [Mt] x 4 int32 (16-byte aligned) = per score tile {compact candidate, first row of the tile in h / u,
+ *   valid rows of the tile, impression}; built on the device from the [B + 1] tables, one thread per candidate.
+ * nrm_pwattn_fwd_hragged: nrm_pwattn_fwd_ragged for history rows h, u [R, D] and scores s [16 Mt]; rows of a tile past its valid ones
+ *   are written as 0.  fp32 arithmetic only: mma other than NRM_MMA_F32 is refused.
+ * nrm_pool_bmm_hragged: out[c, :] = sum_{j < K_b} w_j s[c, j] h[hist_off[b] + j, :], w_j = 1 except w_{K_b - 1} = hist_mult[b] where
+ *   hist_mult[b] > 0; s is read, never changed. */
+int nrm_history_len(const void* x_history, int cols, int is_f64, int B, int H, int* hist_len, nrm_stream_t stream);
+int nrm_history_gather(const void* x_history, int cols, int is_f64, const int* hist_off, int B, int H, int R, int k_max, void* xh_compact,
+                       nrm_stream_t stream);
+int nrm_history_tiles(const int* cand_imp, const int* cand_off, const int* hist_off, const int* tile_pre, int B, int N, int R, int Mt,
+                      void* tile_tab, nrm_stream_t stream);
+int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
+                           const float* w2, const float* b2, float* s, const int* cand_imp, const int* cand_off, const int* hist_off,
+                           const int* tile_pre, const void* tile_tab, int B, int N, int max_count, int R, int Mt, int k_max, int D, int mma,
+                           nrm_stream_t stream);
+int nrm_pool_bmm_hragged(const float* s, const float* h, float* out, const int* cand_off, const int* hist_off, const int* hist_mult,
+                         const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D, nrm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

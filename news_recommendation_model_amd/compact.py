@@ -24,9 +24,27 @@ class CompactPlan:
       cand_imp [N]       impression of each compact row
       src [N]            source cell ``b * T + t`` of each compact row in the flattened [B * T] input rows
       max_count          longest list, ``max_b (cand_off[b + 1] - cand_off[b])`` (0 for an empty plan)
+
+    With ``build_plan(..., history_len=, H=)`` the plan also drops the trailing all-zero history rows; without it
+    these fields are None:
+      H                  history rows of the input
+      hist_len [B]       ``L_b``: 1 + the last live history row, clamped to [0, H]
+      hist_mult [B]      ``H - L_b``: how many equal rows the representative padded row (row ``L_b``) stands for
+      hist_off [B + 1]   prefix sums of ``K_b = L_b + [L_b < H]``, the rows kept per impression
+      R                  kept history rows, ``sum_b K_b``
+      hist_src [R]       source row ``b * H + j`` of each kept row in the flattened [B * H] history rows
+      k_max              longest kept history
+      tile_pre [B + 1]   prefix sums of ``count_b * ceil(K_b / 16)``: the scores of a compact candidate are whole 16-row tiles
+      Mt                 ``tile_pre[B]``: 16-row score tiles of the batch
+      history_dense      every ``L_b = H``: nothing to drop
     """
 
-    __slots__ = ("B", "T", "trim", "Tp", "N", "live", "pad_mult", "cand_off", "cand_imp", "src", "max_count", "device_tables")
+    __slots__ = ("B", "T", "trim", "Tp", "N", "live", "pad_mult", "cand_off", "cand_imp", "src", "max_count", "device_tables",
+                 "H", "hist_len", "hist_mult", "hist_off", "R", "hist_src", "k_max", "tile_pre", "Mt", "history_dense")
+
+    @property
+    def has_history(self):
+        return self.hist_off is not None
 
     @property
     def dense(self):
@@ -41,20 +59,32 @@ class CompactPlan:
         if self.device_tables is not None and self.device_tables["cand_off"].device == torch.device(device):
             return self.device_tables
         B, N = self.B, self.N
-        host = torch.empty(2 * B + 1 + N, dtype=torch.int32)
+        parts = [self.cand_off, self.pad_mult, self.cand_imp]
+        if self.has_history:                        # the [B]-sized history tables ride in the same copy, behind today's
+            parts += [self.hist_off, self.hist_mult, self.tile_pre]
+        host = torch.empty(sum(len(p) for p in parts), dtype=torch.int32)
         if torch.cuda.is_available():
             host = host.pin_memory()
-        host.numpy()[:] = np.concatenate([self.cand_off, self.pad_mult, self.cand_imp])
+        host.numpy()[:] = np.concatenate(parts)
         dev = host.to(device, non_blocking=True)
-        self.device_tables = {"cand_off": dev[:B + 1], "pad_mult": dev[B + 1:2 * B + 1], "cand_imp": dev[2 * B + 1:],
+        self.device_tables = {"cand_off": dev[:B + 1], "pad_mult": dev[B + 1:2 * B + 1], "cand_imp": dev[2 * B + 1:2 * B + 1 + N],
                               "_host": host}        # (the pinned source lives as long as the copy may run)
+        if self.has_history:
+            o = 2 * B + 1 + N
+            t = self.device_tables
+            t.update(hist_off=dev[o:o + B + 1], hist_mult=dev[o + B + 1:o + 2 * B + 1], tile_pre=dev[o + 2 * B + 1:o + 3 * B + 2])
+            if dev.is_cuda:                         # the per-tile table (Mt x 16 bytes) is built ON the device from the [B + 1] tables
+                from . import ops
+                t["tile_tab"] = ops.history_tiles(t["cand_imp"], t["cand_off"], t["hist_off"], t["tile_pre"], self.R, self.Mt)
         return self.device_tables
 
 
-def build_plan(empty_num, T):
+def build_plan(empty_num, T, history_len=None, H=None):
     """``empty_num`` [B]: trailing all-padding candidates per row (the DataLoader's HOST tensor or array: no device work;
     a device-resident tensor is read with ``.cpu()``, which costs one synchronise per batch); ``T``: candidate columns of the
-    batch.  Entries are clamped to [0, T], as the scoring tail clamps them."""
+    batch.  Entries are clamped to [0, T], as the scoring tail clamps them.
+    ``history_len`` [B] (with ``H``, the history rows of the batch): ``L_b`` as ``ops.history_len`` measures it on the device, a host
+    array (entries clamped to [0, H]); the plan then carries the history tables as well."""
     if hasattr(empty_num, "detach"):
         empty_num = empty_num.detach().cpu().numpy()
     empty = np.clip(np.asarray(empty_num).reshape(-1).astype(np.int64), 0, int(T))
@@ -80,6 +110,32 @@ def build_plan(empty_num, T):
     plan.src = (cand_imp * T + within).astype(np.int32)
     plan.max_count = int(count.max()) if B else 0
     plan.device_tables = None
+    for k in ("H", "hist_len", "hist_mult", "hist_off", "R", "hist_src", "k_max", "tile_pre", "Mt", "history_dense"):
+        setattr(plan, k, None)
+    if history_len is not None:
+        if H is None or int(H) < 0:
+            raise ValueError(f"build_plan: history_len needs H >= 0, got H={H}")
+        if hasattr(history_len, "detach"):
+            history_len = history_len.detach().cpu().numpy()
+        H = int(H)
+        L = np.clip(np.asarray(history_len).reshape(-1).astype(np.int64), 0, H)
+        if L.shape[0] != B:
+            raise ValueError(f"build_plan: history_len has {L.shape[0]} entries for {B} impressions")
+        K = L + (L < H)                                          # the live rows and ONE representative padded row
+        hist_off = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(K, out=hist_off[1:])
+        tile_pre = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(count * ((K + 15) // 16), out=tile_pre[1:])
+        R, Mt = int(hist_off[B]), int(tile_pre[B])
+        if B * H >= 2 ** 31 or 16 * Mt >= 2 ** 31:
+            raise ValueError("build_plan: more than 2^31 history or score rows")
+        imp = np.repeat(np.arange(B, dtype=np.int64), K)
+        plan.H, plan.R, plan.Mt = H, R, Mt
+        plan.hist_len, plan.hist_mult = L.astype(np.int32), (H - L).astype(np.int32)
+        plan.hist_off, plan.tile_pre = hist_off.astype(np.int32), tile_pre.astype(np.int32)
+        plan.hist_src = (imp * H + np.arange(R, dtype=np.int64) - hist_off[imp]).astype(np.int32)
+        plan.k_max = int(K.max()) if B else 0
+        plan.history_dense = bool((L == H).all())
     return plan
 
 

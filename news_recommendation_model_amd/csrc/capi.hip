@@ -138,6 +138,35 @@ int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const 
     return check_hip(nrm::pwattn_fwd_ragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_ragged");
 }
 
+int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
+                           const float* w2, const float* b2, float* s, const int* cand_imp, const int* cand_off, const int* hist_off,
+                           const int* tile_pre, const void* tile_tab, int B, int N, int max_count, int R, int Mt, int k_max, int D, int mma,
+                           nrm_stream_t stream) {
+    if (int rc = check_mma("nrm_pwattn_fwd_hragged", mma)) return rc;
+    if (mma != NRM_MMA_F32)
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: mma=%d: the ragged forward has fp32 arithmetic only (NRM_MMA_F32); the bf16 / bf16x3 "
+                                "forms exist for dense candidate lists (nrm_pwattn_fwd)", mma);
+    if (B < 0 || N < 0 || max_count < 0 || max_count > N || R < 0 || Mt < 0 || k_max < 0 || k_max > R || D <= 0)
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: B=%d N=%d max_count=%d R=%d Mt=%d k_max=%d D=%d (B, N, R, Mt >= 0, 0 <= max_count <= N, "
+                                "0 <= k_max <= R, D > 0)", B, N, max_count, R, Mt, k_max, D);
+    if (D % 4) return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: D=%d must be a multiple of 4", D);
+    if (D > 1024) return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: D=%d > 1024 not supported", D);
+    if (16L * Mt >= (1L << 31) || (long)N * D >= (1L << 29) || (long)R * D >= (1L << 29))
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: 16*Mt=%ld exceeds 2^31 rows or a [N,D]/[R,D] operand exceeds 2^31 bytes", 16L * Mt);
+    if (!t || !h || !u || !v || !packed_wp || !w2 || !b2 || !s || !cand_imp || !cand_off || !hist_off || !tile_pre || !tile_tab)
+        return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: null pointer");
+    if ((uintptr_t)tile_tab & 15) return fail(NRM_EINVAL, "nrm_pwattn_fwd_hragged: tile_tab must be 16-byte aligned");
+    if (N == 0 || B == 0 || Mt == 0 || R == 0) return NRM_OK;
+    const nrm::FwdPlan pl = nrm::pwattn_fwd_plan(D);
+    nrm::FwdParams p = fwd_params(t, h, u, v, packed_wp, w2, b2, nullptr, s, N, 1, B, 1, D, pl);
+    p.M = 16L * Mt;
+    p.h_bytes = (unsigned)((long)R * D * 4);
+    nrm::RaggedTabs rg;
+    rg.cand_imp = cand_imp; rg.cand_off = cand_off; rg.B = B; rg.N = N; rg.max_count = max_count;
+    rg.hist_off = hist_off; rg.tile_pre = tile_pre; rg.tile_tab = (const int4*)tile_tab; rg.R = R; rg.Mt = Mt; rg.k_max = k_max;
+    return check_hip(nrm::pwattn_fwd_hragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_hragged");
+}
+
 int nrm_pwattn_bwd_dz(float* z_inout, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,
                       int B, int T, int H, int D, int dz_format, nrm_stream_t stream) {
     if (int rc = check_dims("nrm_pwattn_bwd_dz", B, T, H, D)) return rc;
@@ -602,6 +631,46 @@ int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const 
         lg.ptr[m] = logits[m]; lg.row_stride[m] = row_stride[m]; lg.col_stride[m] = cs;
     }
     return check_hip(nrm::ensemble_rank_launch(lg, M, empty, label, B, T, score, rank, live, metrics, (hipStream_t)stream), "ensemble_rank");
+}
+
+int nrm_pool_bmm_hragged(const float* s, const float* h, float* out, const int* cand_off, const int* hist_off, const int* hist_mult,
+                         const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D, nrm_stream_t stream) {
+    if (!s || !h || !out || !cand_off || !hist_off || !hist_mult || !tile_pre) return fail(NRM_EINVAL, "nrm_pool_bmm_hragged: null pointer");
+    if (B < 0 || N < 0 || max_count < 0 || max_count > N || R < 0 || Mt < 0 || k_max < 0 || k_max > R || D <= 0 || D % 4)
+        return fail(NRM_EINVAL, "nrm_pool_bmm_hragged: B=%d N=%d max_count=%d R=%d Mt=%d k_max=%d D=%d", B, N, max_count, R, Mt, k_max, D);
+    if (((uintptr_t)h | (uintptr_t)out) & 15 || (long)R * D * 4 >= (1L << 31) || 16L * Mt >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_pool_bmm_hragged: h and out must be 16-byte aligned, R*D*4 and 16*Mt below 2^31");
+    if (R == 0 || Mt == 0) return NRM_OK;
+    return check_hip(nrm::bmm_rows_hragged_launch(s, h, D, out, D, cand_off, hist_off, hist_mult, tile_pre, B, N, max_count, R, Mt, k_max, D,
+                                                  (hipStream_t)stream), "pool_bmm_hragged");
+}
+
+int nrm_history_len(const void* x_history, int cols, int is_f64, int B, int H, int* hist_len, nrm_stream_t stream) {
+    if (B < 0 || H < 0 || cols <= 0) return fail(NRM_EINVAL, "nrm_history_len: B=%d H=%d cols=%d", B, H, cols);
+    const long words = (long)cols * (is_f64 ? 2 : 1);
+    if ((long)H * words >= (1L << 31)) return fail(NRM_EINVAL, "nrm_history_len: H*cols=%ld words of one impression exceed 2^31", (long)H * words);
+    if ((B > 0 && !hist_len) || (B > 0 && H > 0 && !x_history)) return fail(NRM_EINVAL, "nrm_history_len: null pointer");
+    if ((uintptr_t)x_history & 3) return fail(NRM_EINVAL, "nrm_history_len: x_history must be 4-byte aligned");
+    return check_hip(nrm::history_len_launch((const unsigned*)x_history, B, H, (int)words, hist_len, (hipStream_t)stream), "history_len");
+}
+
+int nrm_history_gather(const void* x_history, int cols, int is_f64, const int* hist_off, int B, int H, int R, int k_max, void* xh_compact,
+                       nrm_stream_t stream) {
+    if (B < 0 || H < 0 || cols <= 0 || R < 0 || k_max < 0 || k_max > H || (long)R > (long)B * H)
+        return fail(NRM_EINVAL, "nrm_history_gather: B=%d H=%d cols=%d R=%d k_max=%d (0 <= k_max <= H, R <= B*H)", B, H, cols, R, k_max);
+    if ((long)cols * 2 >= (1L << 31)) return fail(NRM_EINVAL, "nrm_history_gather: cols=%d", cols);
+    if (!hist_off || (R > 0 && (!x_history || !xh_compact))) return fail(NRM_EINVAL, "nrm_history_gather: null pointer");
+    return check_hip(nrm::history_gather_launch((const unsigned*)x_history, (unsigned*)xh_compact, cols * (is_f64 ? 2 : 1), hist_off, B, H, R, k_max,
+                                                (hipStream_t)stream), "history_gather");
+}
+
+int nrm_history_tiles(const int* cand_imp, const int* cand_off, const int* hist_off, const int* tile_pre, int B, int N, int R, int Mt,
+                      void* tile_tab, nrm_stream_t stream) {
+    if (B < 0 || N < 0 || R < 0 || Mt < 0) return fail(NRM_EINVAL, "nrm_history_tiles: B=%d N=%d R=%d Mt=%d", B, N, R, Mt);
+    if (16L * Mt >= (1L << 31)) return fail(NRM_EINVAL, "nrm_history_tiles: 16*Mt=%ld exceeds 2^31 rows", 16L * Mt);
+    if (!cand_imp || !cand_off || !hist_off || !tile_pre || (Mt > 0 && !tile_tab)) return fail(NRM_EINVAL, "nrm_history_tiles: null pointer");
+    if ((uintptr_t)tile_tab & 15) return fail(NRM_EINVAL, "nrm_history_tiles: tile_tab must be 16-byte aligned");
+    return check_hip(nrm::history_tiles_launch(cand_imp, cand_off, hist_off, tile_pre, B, N, R, Mt, (int4*)tile_tab, (hipStream_t)stream), "history_tiles");
 }
 
 int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,

@@ -7,6 +7,7 @@
 // front end's index flag: written only in the error case, read by the host whenever it likes, no synchronisation on the hot path.
 // The trimmed columns are never read, as the reference never reads them.
 // One wave per (impression, kept column); rows are independent: a wave reads its own cell and its row's representative only.
+#include <cstdint>
 #include "compact.hpp"
 
 namespace nrm {
@@ -40,6 +41,120 @@ hipError_t compact_gather_launch(const CompactGatherParams& p, hipStream_t st) {
     if (cells <= 0) return hipSuccess;
     if ((cells + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_gather_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// ---- history compaction (section 5d)
+// History length: ONE pass over x_history as a flat array of 32-bit words.  A thread reads 16-byte vectors 256 apart (a wave reads 1 KiB of
+// consecutive words: neighbouring rows of an impression side by side), keeps (impression, 1 + last live row) of what it saw and hands it
+// over with a vector atomic max -- one per wave where the whole wave saw one impression, one per lane otherwise.  The test is on the BITS:
+// -0.0 and NaN count as live.  hist_len is cleared by the launcher.
+constexpr int HL_VECS = 8;                  // 16-byte vectors per thread
+__global__ __launch_bounds__(256) void history_len_kernel(const unsigned* __restrict__ x, long nvec, long nwords, int H, int words, int B,
+                                                          int* __restrict__ hist_len) {
+    int cur_b = -1, cur_l = 0;
+    auto flush = [&]() { if (cur_b >= 0 && cur_b < B && cur_l > 0) atomicMax(hist_len + cur_b, cur_l); };
+    auto note = [&](int b, int j) {
+        if (b != cur_b) { flush(); cur_b = b; cur_l = 0; }
+        cur_l = max(cur_l, j + 1);
+    };
+    const long rowlen = (long)H * words;
+    const long v0 = (long)blockIdx.x * (256 * HL_VECS) + threadIdx.x;
+    for (int i = 0; i < HL_VECS; ++i) {
+        const long v = v0 + (long)i * 256;
+        if (v >= nvec) break;
+        const uint4 w4 = reinterpret_cast<const uint4*>(x)[v];
+        if ((w4.x | w4.y | w4.z | w4.w) == 0u) continue;
+        const long g = v * 4;
+        int b = (int)(g / rowlen);
+        const int rem = (int)(g - (long)b * rowlen);      // H * words < 2^31 (checked by the entry point)
+        int j = rem / words, c = rem - j * words;
+        const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (w[k]) note(b, j);
+            if (++c == words) { c = 0; if (++j == H) { j = 0; ++b; } }
+        }
+    }
+    // the words past the last whole vector (fewer than four): thread 0 of block 0
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long g = nvec * 4; g < nwords; ++g)
+            if (x[g]) { const int b = (int)(g / rowlen); note(b, (int)((g - (long)b * rowlen) / words)); }
+    const int b0 = __shfl(cur_b, 0);
+    if (__all(cur_b == b0 || cur_b < 0)) {                 // one impression in the whole wave: reduce, one atomic
+        int l = cur_b < 0 ? 0 : cur_l;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) l = max(l, __shfl_xor(l, o));
+        int bb = cur_b;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bb = max(bb, __shfl_xor(bb, o));
+        if ((threadIdx.x & 63) == 0 && bb >= 0 && bb < B && l > 0) atomicMax(hist_len + bb, l);
+    } else {
+        flush();
+    }
+}
+
+hipError_t history_len_launch(const unsigned* x, int B, int H, int words, int* hist_len, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(hist_len, 0, (size_t)B * sizeof(int), st)) return e;
+    const long nwords = (long)B * H * words;
+    if (nwords <= 0) return hipSuccess;
+    const long nvec = ((uintptr_t)x & 15) ? 0 : nwords / 4;          // an unaligned view: word by word (never the DataLoader's tensors)
+    if (nvec == 0) {
+        hipLaunchKernelGGL(history_len_kernel, dim3(1), dim3(256), 0, st, x, 0L, nwords, H, words, B, hist_len);
+        return hipGetLastError();
+    }
+    const long nblk = (nvec + 256 * HL_VECS - 1) / (256 * HL_VECS);
+    if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(history_len_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x, nvec, nwords, H, words, B, hist_len);
+    return hipGetLastError();
+}
+
+// One wave per (impression, kept row): row j < K_b of impression b goes to compact row hist_off[b] + j, as compact_gather_kernel places a
+// candidate.  Table entries are clamped to the arrays.
+__global__ __launch_bounds__(256) void history_gather_kernel(const unsigned* __restrict__ x, unsigned* __restrict__ xh_c, int words,
+                                                             const int* __restrict__ hist_off, int B, int H, int R, int k_max) {
+    const int lane = threadIdx.x & 63;
+    const long cell = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= (long)B * k_max) return;
+    const int b = (int)(cell / k_max), j = (int)(cell - (long)b * k_max);
+    const int r0 = min(max(hist_off[b], 0), R);
+    const int K = min(min(max(hist_off[b + 1], r0), R) - r0, H);
+    if (j >= K) return;
+    const long src = ((long)b * H + j) * words, dst = ((long)r0 + j) * words;
+    for (int w = lane; w < words; w += 64) xh_c[dst + w] = x[src + w];
+}
+
+hipError_t history_gather_launch(const unsigned* x, unsigned* xh_c, int words, const int* hist_off, int B, int H, int R, int k_max, hipStream_t st) {
+    const long cells = (long)B * k_max;
+    if (cells <= 0 || R <= 0) return hipSuccess;
+    if ((cells + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(history_gather_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, x, xh_c, words, hist_off, B, H, R, k_max);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void history_tiles_kernel(const int* __restrict__ cand_imp, const int* __restrict__ cand_off,
+                                                            const int* __restrict__ hist_off, const int* __restrict__ tile_pre, int B, int N,
+                                                            int R, int Mt, int4* __restrict__ tile_tab) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    const int b = min(max(cand_imp[c], 0), B - 1);
+    const int r0 = min(max(hist_off[b], 0), R);
+    const int K = min(max(hist_off[b + 1], r0), R) - r0;
+    const int nt = (K + 15) >> 4;
+    const long first = (long)tile_pre[b] + (long)(c - cand_off[b]) * nt;
+    for (int jt = 0; jt < nt; ++jt) {
+        const long tile = first + jt;
+        if (tile >= 0 && tile < Mt) tile_tab[tile] = make_int4(c, r0 + 16 * jt, min(16, K - 16 * jt), b);
+    }
+}
+
+hipError_t history_tiles_launch(const int* cand_imp, const int* cand_off, const int* hist_off, const int* tile_pre, int B, int N, int R, int Mt,
+                                int4* tile_tab, hipStream_t st) {
+    if (N <= 0 || B <= 0 || Mt <= 0) return hipSuccess;
+    // a table that does not add up leaves tiles unwritten: {0, 0, 0, 0} = no valid row
+    if (hipError_t e = hipMemsetAsync(tile_tab, 0, (size_t)Mt * sizeof(int4), st)) return e;
+    hipLaunchKernelGGL(history_tiles_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cand_imp, cand_off, hist_off, tile_pre, B, N, R, Mt, tile_tab);
     return hipGetLastError();
 }
 

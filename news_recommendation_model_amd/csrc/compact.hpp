@@ -15,4 +15,15 @@ struct CompactGatherParams {
 };
 hipError_t compact_gather_launch(const CompactGatherParams& p, hipStream_t st);
 
+// ---- history compaction: the trailing all-zero history rows of an impression are dropped like its padded candidates
+// hist_len[b] = 1 + the last row of x_history [B, H, words] (32-bit words: a float64 column is two) that holds any non-zero BIT, 0 if none
+hipError_t history_len_launch(const unsigned* x, int B, int H, int words, int* hist_len, hipStream_t st);
+// xh_c[hist_off[b] + j, :] = x[b, j, :] for j < hist_off[b + 1] - hist_off[b] (bitwise); k_max = the longest kept history (it sizes the grid)
+hipError_t history_gather_launch(const unsigned* x, unsigned* xh_c, int words, const int* hist_off, int B, int H, int R, int k_max, hipStream_t st);
+// Per-tile table of the history-ragged attention: the score rows of compact candidate c (impression b = cand_imp[c], K_b kept history rows)
+// are nt_b = ceil(K_b / 16) whole 16-row tiles, tile_pre[b] + (c - cand_off[b]) nt_b + jt; entry = {c, first row of the tile in h_c / u,
+// valid rows of the tile, b}.  One thread per candidate writes its nt_b entries.
+hipError_t history_tiles_launch(const int* cand_imp, const int* cand_off, const int* hist_off, const int* tile_pre, int B, int N, int R, int Mt,
+                                int4* tile_tab, hipStream_t st);
+
 }  // namespace nrm

@@ -26,12 +26,17 @@ namespace nrm {
 // RAGGED (compact scoring: pooled[c,:] = sum_h s[c,h] h[cand_imp[c],h,:]): impression b owns the rows cand_off[b] .. cand_off[b + 1] - 1 of
 // W and out (row strides wsi / ldo, no batch stride), I is the LONGEST list (it sizes the task grid) and a task past the end of
 // its impression's list leaves at once.  The offsets are clamped to [0, N].
-template <bool JSPLIT, bool RAGGED = false>
+// HRAG (history compaction): impression b keeps K_b = hist_off[b + 1] - hist_off[b] rows of X (hist_off[b] ..), its
+// candidates' scores are nt_b = ceil(K_b / 16) whole tiles each from tile tile_pre[b] of W (row stride 16 nt_b), and where
+// hist_mult[b] > 0 the LAST kept row stands for hist_mult[b] equal rows: its score is weighted where it is read (W itself stays unweighted).
+template <bool JSPLIT, bool RAGGED = false, bool HRAG = false>
 __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__ W, long wsb, long wsi, long wsj,
                                                        const float* __restrict__ X, long xsb, int ldx,
                                                        float* __restrict__ out, long osb, int ldo,
                                                        int B, int I, int J, int D, int accumulate,
-                                                       const int* __restrict__ cand_off, int N) {
+                                                       const int* __restrict__ cand_off, int N,
+                                                       const int* __restrict__ hist_off = nullptr, const int* __restrict__ hist_mult = nullptr,
+                                                       const int* __restrict__ tile_pre = nullptr, int R = 0, int Mt = 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) f32x4 part[JSPLIT ? 3 * 16 * 64 : 1];
     const int lane = threadIdx.x & 63;
@@ -50,8 +55,22 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
         I = min(max(cand_off[b + 1], c0), N) - c0;                      // this impression's rows
         if (i0 >= I) return;                                            // (uniform per task: JSPLIT workgroups leave together)
         wsb = 0; osb = 0;
-        W += (long)c0 * wsi;
+        if (!HRAG) W += (long)c0 * wsi;
         out += (long)c0 * ldo;
+    }
+    float wlast = 1.f;                                                  // HRAG: weight of the last kept row (the representative padded row)
+    if (HRAG) {
+        const int r0 = min(max(hist_off[b], 0), R);
+        J = min(max(hist_off[b + 1], r0), R) - r0;                       // K_b
+        const int nt = (J + 15) >> 4;
+        const long t0 = min(max((long)tile_pre[b], 0L), (long)Mt);
+        I = (int)min((long)I, nt > 0 ? (Mt - t0) / nt : 0L);            // never past the scores there are
+        if (i0 >= I || J <= 0) return;
+        wsi = 16L * nt; wsj = 1;
+        W += t0 * 16;
+        X += (long)r0 * ldx; xsb = 0;
+        const int mult = hist_mult[b];
+        if (mult > 0) wlast = (float)mult;
     }
     const float* Wb = W + b * wsb;
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
@@ -73,6 +92,7 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
         for (int it = 0; it < 4; ++it) {
             const int i = i0 + 16 * it + r16;
             a[it] = (it < nit && i < I && j < j_hi) ? Wb[(long)i * wsi + (long)j * wsj] : 0.f;
+            if (HRAG && j == J - 1) a[it] *= wlast;
         }
     };
     f32x4 x_cur, x_nxt;
@@ -231,6 +251,23 @@ hipError_t bmm_rows_ragged_launch(const float* S, int lds, const float* X, long 
     else
         hipLaunchKernelGGL((bmm_rows_kernel<false, true>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st,
                            S, 0L, (long)lds, 1L, X, xsb, ldx, out, 0L, ldo, B, max_count, J, D, 0, cand_off, N);
+    return hipGetLastError();
+}
+
+hipError_t bmm_rows_hragged_launch(const float* S, const float* X, int ldx, float* out, int ldo, const int* cand_off, const int* hist_off,
+                                   const int* hist_mult, const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D,
+                                   hipStream_t st) {
+    if (B <= 0 || N <= 0 || max_count <= 0) return hipSuccess;
+    const long tasks = (long)B * ((D + 63) / 64) * ((max_count + 63) / 64);
+    if ((tasks + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    const char* env = getenv("NRM_POOL_JSPLIT");
+    const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && k_max >= 32);      // the dense rule, on the longest kept history
+    if (jsplit)
+        hipLaunchKernelGGL((bmm_rows_kernel<true, true, true>), dim3((unsigned)tasks), dim3(256), 0, st,
+                           S, 0L, 0L, 1L, X, 0L, ldx, out, 0L, ldo, B, max_count, k_max, D, 0, cand_off, N, hist_off, hist_mult, tile_pre, R, Mt);
+    else
+        hipLaunchKernelGGL((bmm_rows_kernel<false, true, true>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st,
+                           S, 0L, 0L, 1L, X, 0L, ldx, out, 0L, ldo, B, max_count, k_max, D, 0, cand_off, N, hist_off, hist_mult, tile_pre, R, Mt);
     return hipGetLastError();
 }
 

@@ -8,6 +8,11 @@ hipError_t bmm_rows_launch(const float* W, long wsb, long wsi, long wsj, const f
 // ragged pool of the compact scoring path: out[c,:] = sum_j S[c,j] X[b(c),j,:], impression b owns the rows cand_off[b] .. cand_off[b + 1] - 1
 hipError_t bmm_rows_ragged_launch(const float* S, int lds, const float* X, long xsb, int ldx, float* out, int ldo, const int* cand_off,
                                   int B, int N, int max_count, int J, int D, hipStream_t st);
+// the same, ragged in the history too (section 5d): X [R, D] kept history rows, S whole 16-row tiles per candidate, the last kept row of an
+// impression weighted by hist_mult[b] where that is positive
+hipError_t bmm_rows_hragged_launch(const float* S, const float* X, int ldx, float* out, int ldo, const int* cand_off, const int* hist_off,
+                                   const int* hist_mult, const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D,
+                                   hipStream_t st);
 hipError_t rowdot_launch(const float* g, long gsb, int ldg, const float* h, long hsb, int ldh, float* ds,
                          int B, int T, int H, int D, float* zero_out, int zero_n, hipStream_t st);
 hipError_t loss_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,

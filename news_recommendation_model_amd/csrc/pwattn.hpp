@@ -31,12 +31,21 @@ struct RaggedTabs {
     const int* cand_off;   // [B + 1]
     int B, N;
     int max_count;         // longest candidate list (host side: task grids)
+    // History-ragged form (compact scoring with history compaction): h / u are the R kept history rows, impression b
+    // owns the rows hist_off[b] .. hist_off[b + 1] - 1 (K_b of them), and a candidate's scores are nt_b = ceil(K_b / 16) whole 16-row tiles
+    // of s [16 Mt].  Read by the HRAG instantiations only.
+    const int* hist_off;   // [B + 1]
+    const int* tile_pre;   // [B + 1] prefix sums of count_b nt_b: first tile of impression b's first candidate
+    const int4* tile_tab;  // [Mt] per tile {candidate, first row in h / u, valid rows, impression} (history_tiles_launch)
+    int R, Mt, k_max;      // k_max: longest kept history (host side: task grids, image choice)
 };
 struct FwdPlan { int NT, MT, nchunks, rows, kchunks; };
 FwdPlan pwattn_fwd_plan(int D);
 hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st);
 // fp32 arithmetic, no z store; p.M = N * H, p.T is not read
 hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st);
+// ragged in the history too: p.M = 16 * rg.Mt, p.h_bytes covers the R kept rows, p.T and p.H are not read
+hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st);
 hipError_t pack_wp_launch(const float* w, int ldw, int D, const FwdPlan& pl, int mma, float* packed, hipStream_t st);
 // resident-W forward (pwattn_fwd_rw.hip): mma = 0 (fp32 MFMA), 1 (bf16 operands) or 2 (bf16x3: hi + lo split).  The output
 // columns are cut into nsplit slices of nts 16-column tiles whose whole image stays resident in LDS (persistent workgroups).
@@ -45,6 +54,7 @@ RwPlan pwattn_rw_plan(int D, int mma);
 bool pwattn_fwd_uses_rw(int D, int mma);                  // which forward (and which packed layout) a call takes
 hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st);
 hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);     // fp32, D <= 128 (one resident slice)
+hipError_t pwattn_fwd_rw_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);    // the same widths, history-ragged
 hipError_t pack_wp_bf16_launch(const float* w, int ldw, int D, int mma, float* packed, hipStream_t st);
 
 // ---- backward (pwattn_bwd.hip)

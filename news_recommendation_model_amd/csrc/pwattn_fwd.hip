@@ -64,7 +64,11 @@ __global__ void pack_wp_kernel(const float* __restrict__ w, int ldw, int D, int 
 // RAGGED (compact scoring): the flattened rows are (c, h) over the N compact candidates and the impression of candidate c is
 // rg.cand_imp[c] instead of c / T -- the only two places the dense form derives it; the compact image is indexed by the flat
 // candidate already.  A table entry outside [0, B) is clamped: a wrong row is read, never a foreign address.
-template <int NT, int MT, bool SAVE_Z, int WPE = 2, bool CT = false, int NW = 4, bool RAGGED = false>
+// HRAG (history compaction): ragged in the history too.  The flattened rows are whole 16-row tiles, each of ONE
+// candidate: rg.tile_tab[m / 16] = {candidate, first row in h / u, valid rows, impression} replaces the two divisions.  Rows past a tile's
+// valid ones read 0 (offset out of bounds) and store 0; a workgroup's NW MT tiles belong to consecutive candidates, so the compact image
+// row of a tile is (its candidate) - (the first tile's candidate) < NW MT <= 16.
+template <int NT, int MT, bool SAVE_Z, int WPE = 2, bool CT = false, int NW = 4, bool RAGGED = false, bool HRAG = false>
 __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParams p, const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)      // buffer-descriptor types/builtins exist in the device pass only;
                                          // without the guard the host pass silently drops the kernel stub
@@ -89,6 +93,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
     const int m0 = tile_id * BM;
     const int T = p.T, H = p.H, D = p.D;
     const int rows_here = min(BM, M - m0);
+    static_assert(!HRAG || (RAGGED && !SAVE_Z && NW * MT <= 16), "history-ragged: a ragged form without z, at most 16 tiles per workgroup");
+    // HRAG: candidate, h / u row and validity of flattened row m < M (table entries clamped: a wrong row is read, never a foreign address)
+    auto hrow = [&](int m, unsigned& bt, unsigned& hr) -> bool {
+        const int4 e = rg.tile_tab[m >> 4];
+        bt = (unsigned)min(max(e.x, 0), rg.N - 1);
+        hr = (unsigned)min(max(e.y, 0), rg.R) + (unsigned)(m & 15);
+        return (m & 15) < e.z;
+    };
 
     // All global traffic goes through buffer descriptors: 32-bit lane offsets (no 64-bit pointers to keep
     // live or spill) and hardware bounds checking -- an offset >= num_records reads 0 / drops the store,
@@ -112,36 +124,58 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
         const int rl = lane >> 2;
         const int m = m0 + (wave * MT + j) * 16 + rl;
         const unsigned mm = m < M ? (unsigned)m : 0u;
-        const unsigned bt = mm / (unsigned)H;
-        const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
-        const unsigned hr = b * H + (mm - bt * H);
         const unsigned slot = (unsigned)((lane & 3) ^ swz4(rl));
-        voff_t[j] = (!CT && m < M) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
-        voff_h[j] = m < M ? (hr * p.ldh + 4 * slot) * 4u : OOB;
+        if constexpr (HRAG) {
+            unsigned bt, hr;
+            const bool ok = hrow((int)mm, bt, hr) && m < M;
+            voff_t[j] = (!CT && ok) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
+            voff_h[j] = ok ? (hr * p.ldh + 4 * slot) * 4u : OOB;
+        } else {
+            const unsigned bt = mm / (unsigned)H;
+            const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
+            const unsigned hr = b * H + (mm - bt * H);
+            voff_t[j] = (!CT && m < M) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
+            voff_h[j] = m < M ? (hr * p.ldh + 4 * slot) * 4u : OOB;
+        }
     }
     // CT: image row r (lane >> 2) holds candidate bt0 + r while that candidate has rows in this block (slots swizzled as in every
     // image); a lane's fragment comes from image row tix = (its row's candidate) - bt0
-    const unsigned bt0 = (unsigned)m0 / (unsigned)H;
-    const unsigned bt_last = (unsigned)(m0 + rows_here - 1) / (unsigned)H;
+    unsigned bt0, bt_last;
+    if constexpr (HRAG) {
+        bt0 = (unsigned)min(max(rg.tile_tab[m0 >> 4].x, 0), rg.N - 1);
+        bt_last = (unsigned)min(max(rg.tile_tab[(m0 + rows_here - 1) >> 4].x, 0), rg.N - 1);
+    } else {
+        bt0 = (unsigned)m0 / (unsigned)H;
+        bt_last = (unsigned)(m0 + rows_here - 1) / (unsigned)H;
+    }
     const unsigned voff_tc = (CT && bt0 + (unsigned)(lane >> 2) <= bt_last) ? ((bt0 + (unsigned)(lane >> 2)) * p.ldt + 4u * (unsigned)((lane & 3) ^ swz4(lane >> 2))) * 4u : OOB;
     int tfrag[MT];
 #pragma unroll
     for (int jt = 0; jt < MT; ++jt) {
         const int m = min(m0 + (wave * MT + jt) * 16 + r16, M - 1);
-        const int tix = m / H - (int)bt0;
+        const int tix = HRAG ? min(max(min(max(rg.tile_tab[m >> 4].x, 0), rg.N - 1) - (int)bt0, 0), 15) : m / H - (int)bt0;
         tfrag[jt] = tix * 16 + 4 * (q ^ swz4(tix));
     }
     // --- epilogue rows of this lane
     unsigned voff_u[MT], voff_v[MT];
+    bool row_ok[MT];                                 // HRAG: a valid row of its tile (the others store 0)
 #pragma unroll
     for (int jt = 0; jt < MT; ++jt) {
         const int m = m0 + (wave * MT + jt) * 16 + r16;
         const unsigned mm = m < M ? (unsigned)m : 0u;
-        const unsigned bt = mm / (unsigned)H;
-        const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
-        const unsigned hr = b * H + (mm - bt * H);
-        voff_u[jt] = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
-        voff_v[jt] = m < M ? (bt * p.ldv + 4 * q) * 4u : OOB;
+        if constexpr (HRAG) {
+            unsigned bt, hr;
+            const bool ok = hrow((int)mm, bt, hr) && m < M;
+            row_ok[jt] = ok;
+            voff_u[jt] = ok ? (hr * p.ldu + 4 * q) * 4u : OOB;
+            voff_v[jt] = ok ? (bt * p.ldv + 4 * q) * 4u : OOB;
+        } else {
+            const unsigned bt = mm / (unsigned)H;
+            const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
+            const unsigned hr = b * H + (mm - bt * H);
+            voff_u[jt] = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
+            voff_v[jt] = m < M ? (bt * p.ldv + 4 * q) * 4u : OOB;
+        }
     }
     const int rslot = 4 * (q ^ swz4(r16));          // swizzled float offset of this lane's fragment slot
 
@@ -274,7 +308,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
     for (int jt = 0; jt < MT; ++jt) {
         const float v = sum_rows4(s_part[jt]);
         const int m = m0 + (wave * MT + jt) * 16 + r16;
-        if (q == 0 && m < M) p.s[m] = v + b2;
+        if constexpr (HRAG) { if (q == 0 && m < M) p.s[m] = row_ok[jt] ? v + b2 : 0.f; }
+        else if (q == 0 && m < M) p.s[m] = v + b2;
     }
 #endif
 }
@@ -310,14 +345,18 @@ FwdPlan pwattn_fwd_plan(int D) {
 }
 
 // RAGGED: fp32 arithmetic, no z store (the only ragged instantiations there are)
-template <bool RAGGED, int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>
+template <int RAGGED, int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>      // RAGGED: 0 dense, 1 candidates, 2 candidates and history
 static hipError_t launch_fwd_t(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
     constexpr int BM = NW * MT * 16;
     const long nblk = (p.M + BM - 1) / BM;
     if (nblk <= 0) return hipSuccess;
     if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk), block(NW * 64);
-    if constexpr (RAGGED) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true>), grid, block, 0, st, p, rg);
+    if constexpr (RAGGED == 2) {
+        if constexpr (NW * MT <= 16) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true, true>), grid, block, 0, st, p, rg);
+        else return hipErrorInvalidValue;
+    }
+    else if constexpr (RAGGED == 1) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true>), grid, block, 0, st, p, rg);
     else if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), grid, block, 0, st, p, rg);
     else          hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), grid, block, 0, st, p, rg);
     return hipGetLastError();
@@ -334,9 +373,11 @@ static bool fwd_compact_t(int H, int block_rows = 64) {
 }
 
 // the chunk-streaming kernel for the plan's tiles, dense or ragged
-template <bool RAGGED>
+template <int RAGGED>
 static hipError_t fwd_dispatch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
 #define NRM_FWD(...) launch_fwd_t<RAGGED, __VA_ARGS__>(p, rg, st)
+    // history-ragged: tiles never straddle candidates, so the compact image holds for any history of at least one whole tile
+    auto fwd_compact_t = [&](int H, int block_rows = 64) { return RAGGED == 2 ? nrm::fwd_compact_t(rg.k_max >= 16 ? 64 : 1, block_rows) : nrm::fwd_compact_t(H, block_rows); };
     switch (pl.NT) {
         case 4:  return NRM_FWD(4, 4);
         case 6:  return NRM_FWD(6, 4);
@@ -361,14 +402,20 @@ static hipError_t fwd_dispatch(const FwdParams& p, const FwdPlan& pl, const Ragg
 
 hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st) {
     if (pwattn_fwd_uses_rw(p.D, mma)) return pwattn_fwd_rw_launch(p, mma, st);
-    return fwd_dispatch<false>(p, pl, RaggedTabs{}, st);
+    return fwd_dispatch<0>(p, pl, RaggedTabs{}, st);
 }
 
 // Ragged candidate lists: the plan of the dense forward for the same D and H (same tiles, same image choice); widths whose whole
 // W_p is one resident slice (D <= 128) take the resident-W forms, as the dense forward does -- the packed image is the same.
 hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
     if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_ragged_launch(p, rg, st);
-    return fwd_dispatch<true>(p, pl, rg, st);
+    return fwd_dispatch<1>(p, pl, rg, st);
+}
+
+// Ragged in the history too (section 5d): the same plan and the same choice between the resident-W and the streaming forms.
+hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
+    if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_hragged_launch(p, rg, st);
+    return fwd_dispatch<2>(p, pl, rg, st);
 }
 
 // bf16 forms: always the resident-W forward (pwattn_fwd_rw.hip).  fp32: only where the WHOLE W_p fits one LDS slice

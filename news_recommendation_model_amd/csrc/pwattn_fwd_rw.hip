@@ -92,7 +92,9 @@ RwPlan pwattn_rw_plan(int D, int mma) {
 
 // packed[c][img][row][32 bf16] (pack_wp_bf16_kernel) with rows = plan.rows
 // RAGGED (compact scoring, fp32): rows are (c, h) over the N compact candidates, the impression of candidate c is rg.cand_imp[c].
-template <int NTS, bool SAVE_Z, int MMA, bool RAGGED = false>
+// HRAG (history compaction): every 16-row tile belongs to one candidate; rg.tile_tab[tile] = {candidate, first row in
+// h / u, valid rows, impression}.  Rows past the valid ones read 0 and store 0.
+template <int NTS, bool SAVE_Z, int MMA, bool RAGGED = false, bool HRAG = false>
 __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_kernel(const FwdParams p, const RwPlan pl, int wgs_per_split,
                                                                                     const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -137,12 +139,22 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
     for (int tile = g * FB_WAVES + wave; tile < ntile; tile += stride) {
         const int m = tile * 16 + r16;
         const unsigned mm = m < M ? (unsigned)m : 0u;
-        const unsigned bt = mm / (unsigned)H;
-        const unsigned hr = (RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T) * H + (mm - bt * H);
-        const unsigned voff_t = m < M ? (bt * p.ldt + 4 * q) * 4u : OOB;
-        const unsigned voff_h = m < M ? (hr * p.ldh + 4 * q) * 4u : OOB;
-        const unsigned voff_u = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
-        const unsigned voff_v = m < M ? (bt * p.ldv + 4 * q) * 4u : OOB;
+        unsigned bt, hr;
+        bool ok = m < M;
+        if constexpr (HRAG) {
+            static_assert(RAGGED && !SAVE_Z && MMA == 0, "history-ragged: fp32, no z");
+            const int4 e = rg.tile_tab[min(tile, rg.Mt - 1)];           // (clamped: a wrong row is read, never a foreign address)
+            bt = (unsigned)min(max(e.x, 0), rg.N - 1);
+            hr = (unsigned)min(max(e.y, 0), rg.R) + (unsigned)r16;
+            ok = ok && r16 < e.z;
+        } else {
+            bt = mm / (unsigned)H;
+            hr = (RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T) * H + (mm - bt * H);
+        }
+        const unsigned voff_t = ok ? (bt * p.ldt + 4 * q) * 4u : OOB;
+        const unsigned voff_h = ok ? (hr * p.ldh + 4 * q) * 4u : OOB;
+        const unsigned voff_u = ok ? (hr * p.ldu + 4 * q) * 4u : OOB;
+        const unsigned voff_v = ok ? (bt * p.ldv + 4 * q) * 4u : OOB;
 
         f32x4 ta[3], tb[3], ha[3], hb[3];                              // three chunk sets of this lane's operand columns (requested two chunks ahead)
         auto load_th = [&](int c, int set) {
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
             if (NRM_DIAG_RW & 2) s_part += ww[it][0] * zz[0] + ww[it][1] * zz[1] + ww[it][2] * zz[2] + ww[it][3] * zz[3];
             else s_part += gelu_dot4(ww[it], zz);
         }
-        const float v = sum_rows4(s_part) + b2;
+        const float v = (!HRAG || ok) ? sum_rows4(s_part) + b2 : 0.f;
         if (q == 0 && m < M) {
             if (pl.nsplit == 1) p.s[m] = v; else atomicAdd(p.s + m, v);
         }
@@ -411,7 +423,10 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_kernel(const FwdParams
 // RAGGED (compact scoring): a task's candidates are the compact rows rg.cand_off[b] .. rg.cand_off[b + 1] - 1 instead of b T .. b T + T - 1,
 // and the tsplit cut is made per impression (parts of ceil(count_b / tsplit) candidates; a short list leaves its last parts empty).
 // The offsets are clamped to [0, N] and made wave-uniform before they enter a buffer descriptor.
-template <int NTS, bool SAVE_Z, int KCH, bool RAGGED = false>
+// HRAG (history compaction): impression b keeps K_b = hist_off[b + 1] - hist_off[b] history rows, hist_off[b] .. in h / u;
+// the task grid counts ceil(k_max / 16) tiles per impression and a task past its impression's last tile leaves at once.  The scores of
+// local candidate t, history tile jt go to the tile tile_pre[b] + t nt_b + jt of s (whole tiles: rows past K_b store 0).
+template <int NTS, bool SAVE_Z, int KCH, bool RAGGED = false, bool HRAG = false>
 __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdParams p, const RwPlan pl, int wgs, int tsplit, const RaggedTabs rg) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(KCH % 2 == 0 && NTS == KCH, "whole width in one slice: D = 16 KCH = 16 NTS");
@@ -436,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
 
     const int rslot = 4 * (q ^ swz4(r16));
     const float b2 = p.b2[0];
-    const int nht = (H + 15) >> 4;
+    const int nht = ((HRAG ? rg.k_max : H) + 15) >> 4;
     const int tlen = RAGGED ? 0 : (T + tsplit - 1) / tsplit;
     const int ntask = (RAGGED ? rg.B : (int)(p.M / ((long)T * H))) * nht * tsplit;         // B * nht * tsplit
     f32x4 wreg[NTS];                                                     // fc2 weights of this lane's four columns of every tile
@@ -457,12 +472,22 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
         const int tl = RAGGED ? (cnt + tsplit - 1) / tsplit : tlen;
         const int t_lo = tp * tl, t_hi = min(RAGGED ? cnt : T, t_lo + tl);
         if (t_lo >= t_hi) continue;
-        const bool rok = h0 + r16 < H;
+        // history rows of the task's impression: b H .. + H, or the kept rows hbase .. + hk
+        int hbase = 0, hk = H, tile0 = 0;
+        if constexpr (HRAG) {
+            static_assert(RAGGED && !SAVE_Z, "history-ragged: a ragged form without z");
+            hbase = __builtin_amdgcn_readfirstlane(min(max(rg.hist_off[b], 0), rg.R));
+            hk = __builtin_amdgcn_readfirstlane(min(max(rg.hist_off[b + 1], hbase), rg.R)) - hbase;
+            if (h0 >= hk) continue;
+            tile0 = __builtin_amdgcn_readfirstlane(rg.tile_pre[b]) + (h0 >> 4);
+        }
+        const int ntl = (hk + 15) >> 4;                                 // (HRAG) tiles per candidate of this impression
+        const bool rok = h0 + r16 < hk;
         const size_t trow = RAGGED ? (size_t)cbase : (size_t)b * T;    // first candidate row of the task's impression
         const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t) + trow * p.ldt, 0, (unsigned)(cnt * p.ldt * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v) + trow * p.ldv, 0, (unsigned)(cnt * p.ldv * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h) + (size_t)b * H * p.ldh, 0, (unsigned)(H * p.ldh * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u) + (size_t)b * H * p.ldu, 0, (unsigned)(H * p.ldu * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h) + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldh, 0, (unsigned)(hk * p.ldh * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u) + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldu, 0, (unsigned)(hk * p.ldu * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
             SAVE_Z ? p.z + (size_t)b * T * H * D : nullptr, 0, SAVE_Z ? (unsigned)((size_t)T * H * D * 4) : 0, 0x00020000);
 
@@ -529,7 +554,12 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float sv = sum_rows4(s_part) + b2;
-            if (q == 0 && rok) p.s[m] = sv;
+            if constexpr (HRAG) {
+                const long tile = (long)tile0 + (long)t * ntl;
+                if (q == 0 && tile >= 0 && tile < rg.Mt) p.s[tile * 16 + r16] = rok ? sv : 0.f;
+            } else {
+                if (q == 0 && rok) p.s[m] = sv;
+            }
         }
     }
 #endif
@@ -544,7 +574,7 @@ static int rw_cus() {       // of the CURRENT device (a process may drive severa
 // The launchers take the dense and the ragged (compact scoring) form alike: rg != nullptr selects the RAGGED instantiation, which exists
 // for fp32 arithmetic without a z store only.
 template <int NTS>
-static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const RaggedTabs* rg, hipStream_t st) {
+static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
     const int ntile = (int)((p.M + 15) / 16);
     if (ntile <= 0) return hipSuccess;
     int wgs = rw_cus() / pl.nsplit;                                     // one persistent workgroup per CU, CUs shared evenly by the slices
@@ -556,15 +586,16 @@ static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const
         if (e != hipSuccess) return e;
     }
     const dim3 grid((unsigned)(wgs * pl.nsplit)), block(FB_WAVES * 64);
-#define NRM_RW(SZ, M_, RG)                                                                                               \
+#define NRM_RW(SZ, M_, RG, ...)                                                                                          \
     {                                                                                                                    \
-        auto k = pwattn_fwd_rw_kernel<NTS, SZ, M_, RG>;                                                                  \
+        auto k = pwattn_fwd_rw_kernel<NTS, SZ, M_, RG, ##__VA_ARGS__>;                                                               \
         /* per launch: the attribute is per device, and a process may launch on more than one */                        \
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);  \
         if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, RG ? *rg : RaggedTabs{});                                \
     }
-    if (rg)            NRM_RW(false, 0, true)
+    if (rg && hrag)    NRM_RW(false, 0, true, true)
+    else if (rg)       NRM_RW(false, 0, true)
     else if (mma == 2) { if (p.z) NRM_RW(true, 2, false) else NRM_RW(false, 2, false) }
     else if (mma == 1) { if (p.z) NRM_RW(true, 1, false) else NRM_RW(false, 1, false) }
     else               { if (p.z) NRM_RW(true, 0, false) else NRM_RW(false, 0, false) }
@@ -618,15 +649,16 @@ static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hip
 
 // ragged: the same grid rule with the MEAN list length in T's place (the cut itself is per impression, in the kernel)
 template <int NTS>
-static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const RaggedTabs* rg, hipStream_t st) {
-    const int B = rg ? rg->B : (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
+static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
+    const int B = rg ? rg->B : (int)(p.M / ((long)p.T * p.H)), nht = ((hrag ? rg->k_max : p.H) + 15) / 16;
     const long base = (long)B * nht;
     if (base <= 0 || (rg && rg->N <= 0)) return hipSuccess;
     int wgs = 2 * rw_cus(), tsplit;                                     // two workgroups of 8 waves per CU
     if (hipError_t e = walk_grid(base, rg ? (rg->N + rg->B - 1) / rg->B : p.T, 4, rg ? rg->max_count : p.T, wgs, tsplit)) return e;
     const size_t shm = (size_t)pl.k32 * NTS * 1024;
     const dim3 grid((unsigned)wgs), block(512);
-    if (rg)       hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
+    if (rg && hrag) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
+    else if (rg)  hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
     else if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
     else          hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
     return hipGetLastError();
@@ -649,16 +681,16 @@ static bool fwd_walk_enabled() {
 
 // rg != nullptr: ragged candidate lists -- fp32 only, widths that are one resident slice (pwattn_fwd_uses_rw(D, 0)); p.T = 1 and
 // p.M = N H, so the walk where the dense forward walks, the tile-by-tile form otherwise
-static hipError_t rw_dispatch(const FwdParams& p, int mma, const RaggedTabs* rg, hipStream_t st) {
+static hipError_t rw_dispatch(const FwdParams& p, int mma, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
     const RwPlan pl = pwattn_rw_plan(p.D, mma);
     if (rg && pl.nsplit != 1) return hipErrorInvalidValue;
     const bool walk = !rg && fwd_walk_enabled();
-    const bool walkable = p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31);
+    const bool walkable = hrag || (p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31));
     // fp32: the walk for the widths that are one resident slice of whole 16-column tiles
     if (mma == 0 && pl.nsplit == 1 && p.D == pl.nts * 16 && walkable) {
         const int nts = walk_f32_nts(p.D);
-        if (nts == 4) return launch_walk_f32<4>(p, pl, rg, st);
-        if (nts == 8) return launch_walk_f32<8>(p, pl, rg, st);
+        if (nts == 4) return launch_walk_f32<4>(p, pl, rg, st, hrag);
+        if (nts == 8) return launch_walk_f32<8>(p, pl, rg, st, hrag);
     }
     if (walk && mma != 0 && walkable) {
         if (p.D == 256 && pl.nts == 8) return launch_walk<8, 8>(p, pl, mma, st);
@@ -666,18 +698,19 @@ static hipError_t rw_dispatch(const FwdParams& p, int mma, const RaggedTabs* rg,
         if (p.D == 64 && pl.nts == 4) return launch_walk<4, 2>(p, pl, mma, st);
     }
     switch (pl.nts) {
-        case 1:  return launch_rw<1>(p, pl, mma, rg, st);
-        case 2:  return launch_rw<2>(p, pl, mma, rg, st);
-        case 3:  return launch_rw<3>(p, pl, mma, rg, st);
-        case 4:  return launch_rw<4>(p, pl, mma, rg, st);
-        case 5:  return launch_rw<5>(p, pl, mma, rg, st);
-        case 6:  return launch_rw<6>(p, pl, mma, rg, st);
-        case 8:  return launch_rw<8>(p, pl, mma, rg, st);
+        case 1:  return launch_rw<1>(p, pl, mma, rg, st, hrag);
+        case 2:  return launch_rw<2>(p, pl, mma, rg, st, hrag);
+        case 3:  return launch_rw<3>(p, pl, mma, rg, st, hrag);
+        case 4:  return launch_rw<4>(p, pl, mma, rg, st, hrag);
+        case 5:  return launch_rw<5>(p, pl, mma, rg, st, hrag);
+        case 6:  return launch_rw<6>(p, pl, mma, rg, st, hrag);
+        case 8:  return launch_rw<8>(p, pl, mma, rg, st, hrag);
     }
     return hipErrorInvalidValue;
 }
 
 hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st) { return rw_dispatch(p, mma, nullptr, st); }
 hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) { return rw_dispatch(p, 0, &rg, st); }
+hipError_t pwattn_fwd_rw_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) { return rw_dispatch(p, 0, &rg, st, true); }
 
 }  // namespace nrm

@@ -211,7 +211,7 @@ def predict_ranked(models, batch, with_metrics=False):
 
 
 @torch.no_grad()
-def predict_ranked_compact(models, batch, with_metrics=False, force_compact=False):
+def predict_ranked_compact(models, batch, with_metrics=False, force_compact=False, history=False):
     """predict_ranked() on ragged candidate lists, same return contract: (scores [B, T'] fp32, rank [B, T'] int32, live [B] int32
     [, metrics [B, 3]]).  The padded candidates of one impression all have the same inputs and therefore the same logit, so each
     impression sends its ``n_b`` live candidates plus -- where it keeps ``e'_b > 0`` padded columns after the common trim -- ONE
@@ -225,17 +225,32 @@ def predict_ranked_compact(models, batch, with_metrics=False, force_compact=Fals
     made from the input; ``force_compact`` keeps the ragged kernels even then (tests, measurements).  The gather launch checks
     that the kept padded rows of every impression are bitwise alike and raises ``ops.pad_error_flag`` otherwise:
     ``ops.check_pad_errors(device)`` turns it into a ValueError (score_dataset does after its last batch).
-    Inference only; a model whose attention arithmetic is bf16 / bf16x3 is refused (RuntimeError)."""
+    Inference only; a model whose attention arithmetic is bf16 / bf16x3 is refused (RuntimeError).
+
+    ``history=True`` drops the trailing all-zero history rows as well: one kernel measures every impression's
+    history length ``L_b`` on the device, ONE device-to-host copy of those ``B`` integers (the one synchronisation per batch this
+    costs) feeds ``build_plan(..., history_len=, H=)``, and the models see ``L_b + [L_b < H]`` history rows per impression -- the
+    live ones and one representative padded row that the pool counts ``H - L_b`` times.  The scores agree with ``history=False``
+    to fp32 rounding of the logits.  A batch whose histories are all full (``plan.history_dense``) continues exactly as
+    ``history=False`` would, the hand-over of an unpadded batch to predict_ranked included: the caller has then paid the length
+    kernel and the synchronise for nothing.  A batch with full candidate lists but short histories stays on the ragged path."""
     from . import compact
     xh, xt, xg = batch["x_history"], batch["x_target"], batch["x_global"]
     ops._require_gpu(xh, xt, xg)
-    plan = compact.build_plan(batch["empty_num"], xt.shape[1])
+    hist_len = None
+    if history and xh.dim() == 3 and xh.shape[0] * xh.shape[1] > 0:
+        hist_len = ops.history_len(xh).cpu().numpy()             # the one device-to-host copy (and synchronise) of the history path
+        if bool((hist_len >= xh.shape[1]).all()):
+            hist_len = None                                      # history_dense: exactly the history=False call from here on
+    plan = compact.build_plan(batch["empty_num"], xt.shape[1], history_len=hist_len, H=xh.shape[1] if hist_len is not None else None)
     if plan.B != xt.shape[0]:
         raise ValueError(f"predict_ranked_compact: empty_num has {plan.B} entries for {xt.shape[0]} impressions")
-    if plan.N == 0 or (plan.dense and not force_compact):
+    if plan.N == 0 or (plan.dense and not force_compact and hist_len is None):
         return predict_ranked(models, batch, with_metrics=with_metrics)
     tabs = plan.upload(xt.device)
     xt_c, xg_c = ops.compact_gather(xt, xg, tabs["cand_off"], tabs["pad_mult"], plan.trim, plan.N)
+    if hist_len is not None:
+        xh = ops.history_gather(xh, tabs["hist_off"], plan.R, plan.k_max)
     logits = [m.eval().forward_compact(xh, xt_c, xg_c, plan) for m in models]
     label = None
     if with_metrics:
@@ -245,15 +260,20 @@ def predict_ranked_compact(models, batch, with_metrics=False, force_compact=Fals
 
 
 @torch.no_grad()
-def validate_ranked(models, batches):
-    """validate() with the ranking metrics: {"auc", "top1", "mrr", "ndcg5", "ndcg10"}, means over the impressions of an iterable
+def validate_ranked(models, batches, compact=False, compact_history=False):
+    """``compact`` / ``compact_history``: score through predict_ranked_compact (``history=compact_history``; the latter implies the
+    former) -- the per-epoch validation scores the same padded layout as the test set.  Defaults: the dense path, as before.
+    validate() with the ranking metrics: {"auc", "top1", "mrr", "ndcg5", "ndcg10"}, means over the impressions of an iterable
     of device batches (with labels).  AUC and top-1 come from ``row_auc`` on predict_ranked's scores; the sums are kept on the
     device in float64 and read once at the end (one synchronise), where a single-class row raises validate()'s ValueError."""
     dev = next(models[0].parameters()).device
     sums = torch.zeros(6, dtype=torch.float64, device=dev)   # auc, top1, rr, ndcg5, ndcg10, rows with a single class
     n = 0
     for batch in batches:
-        scores, _rank, live, metrics = predict_ranked(models, batch, with_metrics=True)
+        if compact or compact_history:
+            scores, _rank, live, metrics = predict_ranked_compact(models, batch, with_metrics=True, history=compact_history)
+        else:
+            scores, _rank, live, metrics = predict_ranked(models, batch, with_metrics=True)
         label = batch["label"][:, :scores.shape[1]].to(scores.device)
         auc, top1 = row_auc_top1(scores, label, live)
         per_row = torch.cat([auc[:, None].double(), top1[:, None].double(), metrics.double(), (auc < 0)[:, None].double()], dim=1)
@@ -327,13 +347,16 @@ def iter_dataset_batches(head_path, batch_size):
         yield data_io.collate(pending)
 
 
-def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions", compact=False):
+def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions", compact=False, compact_history=False):
     """test.py's ``model_test`` + ``write_submission_file`` for a processed test set: -> path of ``<out_dir>/<name>.zip`` holding
     ``predictions.txt``.  Every batch goes through predict_ranked (ranks computed on the device) and write_predictions (one
     device-to-host copy); nothing but the current batch and subvolume is held.
     ``compact=True`` scores through predict_ranked_compact (no forward work on padded candidates); a batch whose padded rows are not
     all alike raises ValueError after the last batch.  The default stays the dense path: the two are two correct fp32 evaluations
-    whose nearly tied scores may rank differently, so which one writes a submission is the caller's decision."""
+    whose nearly tied scores may rank differently, so which one writes a submission is the caller's decision.
+    ``compact_history=True`` implies the compact path and drops the padded history rows as well (predict_ranked_compact's
+    ``history=True``: one more synchronise per batch)."""
+    compact = compact or compact_history
     import os
     dev = next(models[0].parameters()).device
     os.makedirs(out_dir, exist_ok=True)
@@ -342,7 +365,10 @@ def score_dataset(models, head_path, out_dir, batch_size=80, name="predictions",
     for batch in iter_dataset_batches(head_path, batch_size):
         tb = {k: torch.from_numpy(batch[k]).to(dev, non_blocking=True) for k in ("x_history", "x_target", "x_global")}
         tb["empty_num"] = torch.from_numpy(batch["empty_num"])         # stays on the host: the trim costs no synchronisation
-        _scores, rank, live = (predict_ranked_compact if compact else predict_ranked)(models, tb)
+        if compact:
+            _scores, rank, live = predict_ranked_compact(models, tb, history=compact_history)
+        else:
+            _scores, rank, live = predict_ranked(models, tb)
         write_predictions(txt_path, batch["impression_id"], rank, live, append=True)
     ops.check_index_errors(dev)
     if compact:

@@ -293,7 +293,10 @@ class UserModel(nn.Module):
     def forward_compact(self, x_history, xt_compact, xg_compact, plan):
         """Inference on ragged candidate lists (compact scoring path): ``xt_compact`` [N, cols] and
         ``xg_compact`` [N, 3] are the plan's rows of x_target / x_global (``ops.compact_gather``), ``plan`` a
-        ``compact.CompactPlan``; -> logits [N] fp32 (a strided view of the last GEMM's output).  The logit of a compact candidate
+        ``compact.CompactPlan``; -> logits [N] fp32 (a strided view of the last GEMM's output).  A plan that carries history tables
+        (``build_plan(..., history_len=, H=)``) takes ``x_history`` as the gathered [R, cols] rows
+        (``ops.history_gather``) and runs the attention that is ragged in the history too; its logits agree with forward()'s to fp32
+        rounding (one product by ``H - L_b`` in place of as many equal addends), not bitwise.  The logit of a compact candidate
         is the one forward() gives its source cell: everything but the two attentions and the pool is row-wise and runs on the N
         rows unchanged, and eval-mode BatchNorm uses the running statistics.  Eval mode only: in training mode BatchNorm's
         batch statistics would see N rows where the reference sees B * T.  fp32 attention arithmetic only."""
@@ -302,8 +305,16 @@ class UserModel(nn.Module):
                                "statistics over the rows of the launch, and the compact path drops the padded ones)")
         inv = self.invariant_interest_model
         ops._require_gpu(x_history, xt_compact, xg_compact)
-        B, H, N = x_history.shape[0], x_history.shape[1], xt_compact.shape[0]
-        if plan.B != B or plan.N != N or xg_compact.shape[0] != N:
+        hist = getattr(plan, "hist_off", None) is not None
+        if hist:
+            if x_history.dim() != 2 or x_history.shape[0] != plan.R or plan.N != xt_compact.shape[0] or xg_compact.shape[0] != plan.N:
+                raise RuntimeError(f"forward_compact: plan for {plan.R} kept history rows / {plan.N} candidate rows, got x_history "
+                                   f"{tuple(x_history.shape)}, {xt_compact.shape[0]} target and {xg_compact.shape[0]} global rows")
+            B, H, N = plan.B, plan.H, plan.N
+            x_history = x_history.unsqueeze(0)                           # [1, R, cols]: the front end is row-wise
+        else:
+            B, H, N = x_history.shape[0], x_history.shape[1], xt_compact.shape[0]
+        if not hist and (plan.B != B or plan.N != N or xg_compact.shape[0] != N):
             raise RuntimeError(f"forward_compact: plan for {plan.B} impressions / {plan.N} rows, got {B} / {N} target and {xg_compact.shape[0]} global rows")
         if B * H == 0 or N == 0:
             raise RuntimeError("cannot reshape tensor of 0 elements (empty batch / history / candidate list)")
@@ -324,6 +335,10 @@ class UserModel(nn.Module):
             pooled = []
             for att, t, h in ((inv.label_attention, lab_t[0], lab_h), (inv.text_img_attention, ti_t[0], ti_h)):
                 m = att.mlp
+                if hist:
+                    pooled.append(ops.attend_pool_hragged(t, h[0], m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, tabs, plan.max_count,
+                                                          plan.k_max, mma=att.mma))
+                    continue
                 pooled.append(ops.attend_pool_ragged(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, tabs["cand_imp"],
                                                      tabs["cand_off"], plan.max_count, mma=att.mma))
             eu_L = self.instant_interest_model(xg_compact)

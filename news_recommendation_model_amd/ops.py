@@ -2194,6 +2194,129 @@ def attend_pool_ragged(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bi
         return attend_pool_ragged_fwd(*args, cand_imp, cand_off, int(max_count), resolve_mma(mma))[0][:, :D]
 
 
+# ---- history compaction: the trailing all-zero history rows are dropped like the padded candidates.  Tables (int32,
+# device; compact.build_plan(..., history_len=, H=)): hist_off [B + 1], hist_mult [B], tile_pre [B + 1]; tile_tab [Mt, 4] is built on the
+# device (history_tiles).
+def _history_len_impl(x_history):
+    """x_history [B, H, cols] (float64 or float32, read as the front end reads them) -> hist_len [B] int32: 1 + the last row that holds any
+    non-zero BIT (-0.0 and NaN are live), 0 if there is none.  One pass over the rows."""
+    _require_gpu(x_history)
+    x = (x_history if x_history.dtype in (torch.float32, torch.float64) else x_history.to(torch.float32)).contiguous()
+    if x.dim() != 3:
+        raise RuntimeError(f"history_len: x_history {tuple(x.shape)} is not [B, H, cols]")
+    B, H, cols = x.shape
+    out = torch.zeros(B, dtype=torch.int32, device=x.device)
+    if B * H * cols:
+        native.call("nrm_history_len", native.ptr(x), cols, 1 if x.dtype == torch.float64 else 0, B, H, native.ptr(out), native.stream_ptr())
+    return out
+
+
+history_len = _op("history_len", "(Tensor x_history) -> Tensor", _history_len_impl,
+                  lambda x: x.new_empty((x.shape[0],), dtype=torch.int32))
+
+
+def _history_gather_impl(x_history, hist_off, R, k_max):
+    """x_history [B, H, cols] -> [R, cols] (bitwise, dtype kept): row j < K_b of impression b goes to row hist_off[b] + j.  One launch."""
+    _require_gpu(x_history, hist_off)
+    x = (x_history if x_history.dtype in (torch.float32, torch.float64) else x_history.to(torch.float32)).contiguous()
+    if x.dim() != 3 or tuple(hist_off.shape) != (x.shape[0] + 1,):
+        raise RuntimeError(f"history_gather: x_history {tuple(x.shape)}, hist_off {tuple(hist_off.shape)} do not agree")
+    B, H, cols = x.shape
+    out = torch.empty(int(R), cols, dtype=x.dtype, device=x.device)
+    if R and cols:
+        native.call("nrm_history_gather", native.ptr(x), cols, 1 if x.dtype == torch.float64 else 0, native.ptr(_tab(hist_off)), B, H, int(R), int(k_max),
+                    native.ptr(out), native.stream_ptr())
+    return out
+
+
+history_gather = _op("history_gather", "(Tensor x_history, Tensor hist_off, int R, int k_max) -> Tensor", _history_gather_impl,
+                     lambda x, off, R, k_max: x.new_empty((R, x.shape[2]), dtype=x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32))
+
+
+def _history_tiles_impl(cand_imp, cand_off, hist_off, tile_pre, R, Mt):
+    """-> tile_tab [Mt, 4] int32: per 16-row score tile {compact candidate, first row of the tile in the kept history rows, valid rows,
+    impression}.  Built on the device from the [B + 1] tables (one thread per candidate): the host never copies a per-tile table."""
+    _require_gpu(cand_imp, cand_off, hist_off, tile_pre)
+    B, N = cand_off.shape[0] - 1, cand_imp.shape[0]
+    if tuple(hist_off.shape) != (B + 1,) or tuple(tile_pre.shape) != (B + 1,):
+        raise RuntimeError(f"history_tiles: cand_off {tuple(cand_off.shape)}, hist_off {tuple(hist_off.shape)}, tile_pre {tuple(tile_pre.shape)} do not agree")
+    tab = torch.zeros(int(Mt), 4, dtype=torch.int32, device=cand_imp.device)
+    if Mt and N and B > 0:
+        native.call("nrm_history_tiles", native.ptr(_tab(cand_imp)), native.ptr(_tab(cand_off)), native.ptr(_tab(hist_off)), native.ptr(_tab(tile_pre)),
+                    B, N, int(R), int(Mt), native.ptr(tab), native.stream_ptr())
+    return tab
+
+
+history_tiles = _op("history_tiles", "(Tensor cand_imp, Tensor cand_off, Tensor hist_off, Tensor tile_pre, int R, int Mt) -> Tensor", _history_tiles_impl,
+                    lambda ci, co, ho, tp, R, Mt: ci.new_empty((Mt, 4), dtype=torch.int32))
+
+
+def _attend_pool_hragged_fwd_impl(t, h, w1, b1, w2, b2, cand_imp, cand_off, hist_off, hist_mult, tile_pre, tile_tab, max_count, k_max, mma):
+    """Attention + pool, ragged in the candidates AND the history (inference only, no z): t [N, D] compact candidate rows, h [R, D] kept
+    history rows (impression b: rows hist_off[b] .. hist_off[b + 1] - 1, the last of which stands for hist_mult[b] equal padded rows where
+    hist_mult[b] > 0) -> (pooled [N, D], s [16 Mt]): the scores of a candidate are ceil(K_b / 16) whole 16-row tiles (rows past K_b hold 0),
+    UNWEIGHTED; pooled[c, :] = sum_j w_j s[c, j] h[hist_off[b] + j, :].  fp32 arithmetic only."""
+    _require_gpu(t, h, w1, b1, w2, b2, cand_imp, cand_off, hist_off, hist_mult, tile_pre, tile_tab)
+    if mma != MMA_F32:
+        raise RuntimeError("compact scoring: the ragged attention forward has fp32 arithmetic only; this attention is set to "
+                           f"{ {MMA_BF16: 'bf16', MMA_BF16X3: 'bf16x3'}.get(mma, mma)} -- score with the dense path, or set the attention "
+                           "arithmetic to 'f32'")
+    N, D = t.shape
+    R, B, Mt = h.shape[0], cand_off.shape[0] - 1, tile_tab.shape[0]
+    if (h.dim() != 2 or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or tuple(cand_imp.shape) != (N,) or tuple(hist_off.shape) != (B + 1,)
+            or tuple(hist_mult.shape) != (B,) or tuple(tile_pre.shape) != (B + 1,) or tile_tab.dim() != 2 or tile_tab.shape[1] != 4
+            or tile_tab.dtype != torch.int32 or not tile_tab.is_contiguous()):
+        raise RuntimeError(f"history-ragged attention: target {tuple(t.shape)}, history {tuple(h.shape)}, fc1 {tuple(w1.shape)}, cand_imp "
+                           f"{tuple(cand_imp.shape)}, cand_off {tuple(cand_off.shape)}, hist_off {tuple(hist_off.shape)}, hist_mult {tuple(hist_mult.shape)}, "
+                           f"tile_pre {tuple(tile_pre.shape)}, tile_tab {tuple(tile_tab.shape)} do not agree (feature width must be a multiple of 4)")
+    w1_arg = w1
+    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
+    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
+    s = torch.empty(16 * Mt, dtype=torch.float32, device=t.device)
+    pooled = torch.empty(N, D, dtype=torch.float32, device=t.device)
+    if N == 0 or R == 0 or Mt == 0 or B == 0:
+        return pooled.zero_(), s.zero_()
+    cand_imp, cand_off, hist_off, hist_mult, tile_pre = _tab(cand_imp), _tab(cand_off), _tab(hist_off), _tab(hist_mult), _tab(tile_pre)
+    own = w1 if w1 is w1_arg else None
+    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
+    u, _ = _gemm_nt(h, w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)                       # [R, D]
+    v, _ = _gemm_nt(t, w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)                      # [N, D]
+    st = native.stream_ptr()
+    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
+    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
+    _count_flops("contraction", 2.0 * 16 * Mt * D * D)
+    native.call("nrm_pwattn_fwd_hragged", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v), native.ptr(packed), native.ptr(w2v),
+                native.ptr(b2), native.ptr(s), native.ptr(cand_imp), native.ptr(cand_off), native.ptr(hist_off), native.ptr(tile_pre),
+                native.ptr(tile_tab), B, N, int(max_count), R, Mt, int(k_max), D, mma, st, tag="pwattn_fwd_hragged")
+    native.call("nrm_pool_bmm_hragged", native.ptr(s), native.ptr(h), native.ptr(pooled), native.ptr(cand_off), native.ptr(hist_off),
+                native.ptr(hist_mult), native.ptr(tile_pre), B, N, int(max_count), R, Mt, int(k_max), D, st)
+    return pooled, s
+
+
+attend_pool_hragged_fwd = _op("attend_pool_hragged_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
+                              "Tensor cand_imp, Tensor cand_off, Tensor hist_off, Tensor hist_mult, Tensor tile_pre, Tensor tile_tab, int max_count, "
+                              "int k_max, int mma) -> (Tensor, Tensor)", _attend_pool_hragged_fwd_impl,
+                              lambda t, h, w1, b1, w2, b2, ci, co, ho, hm, tp, tt, mc, km, mma: (
+                                  t.new_empty(tuple(t.shape), dtype=torch.float32), t.new_empty((16 * tt.shape[0],), dtype=torch.float32)))
+
+
+def attend_pool_hragged(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias, tabs, max_count, k_max, mma=None):
+    """[N, D] compact candidate rows x [R, D] kept history rows -> pooled [N, D] (inference; ``tabs``: the plan's device tables with
+    ``tile_tab``; widths that are not a multiple of 4 are zero-padded as in ``attend_pool_ragged``).  bf16 / bf16x3 is refused."""
+    D = target.shape[-1]
+    args = (target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
+    _require_gpu(*args)
+    if D % 4:
+        P = _pad4(D) - D
+        pad = torch.nn.functional.pad
+        blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]
+        args = (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
+                pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
+    with torch.no_grad():
+        return attend_pool_hragged_fwd(*args, tabs["cand_imp"], tabs["cand_off"], tabs["hist_off"], tabs["hist_mult"], tabs["tile_pre"],
+                                       tabs["tile_tab"], int(max_count), int(k_max), resolve_mma(mma))[0][:, :D]
+
+
 def _ensemble_rank_ragged_impl(logits, cand_off, pad_mult, label, T):
     """The scoring tail on compact logits (C ABI nrm_ensemble_rank_ragged): ``logits`` = one [N] fp32 vector per model (read by stride
     where it lies), impression b owns the entries cand_off[b] .. cand_off[b + 1] - 1, the last of which stands for pad_mult[b] padded
@@ -2250,4 +2373,5 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "batch_norm_bwd", "gate_block_fwd", "gate_block_bwd", "concat_cols",
        "weighted_pool_fwd", "weighted_pool_bwd", "attend_pool_fwd", "attend_pool_bwd", "softmax_bce_loss", "frontend_fwd", "frontend_bwd",
        "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
+       "history_len", "history_gather", "history_tiles", "attend_pool_hragged_fwd",
        "adam_step")
