@@ -91,6 +91,13 @@ int nrm_pwattn_bwd_nsplit(int B, int T, int H, int D, int mma);
 int nrm_pwattn_bwd_contract(const float* dz, const float* t, const float* h, const float* wp, int ldwp,
                             float* dt, float* dh, float* ws,
                             int B, int T, int H, int D, int passes, int mma, int dz_format, nrm_stream_t stream);
+/* Which kernel one launch of nrm_pwattn_bwd_contract takes (additive entry point, the ABI version is unchanged): the plan and
+ * the selection of the launch itself, the environment knobs included, without any device call.  pass: 1, 2 or 4 (passes = 3
+ * is launch 1, then launch 2).  Returns -1 for a combination nrm_pwattn_bwd_contract refuses, otherwise
+ *   bits 0-1  kernel family: 0 serial E-form, 1 pipelined E-form ((b,h) groups), 2 one-accumulator dW_p, 3 32-row dW_p
+ *   bit 2     EXACT (D fills whole wave tiles: no column guards)       bit 3  wave tile 5x5 (clear: 4x4)
+ *   bit 4     the pass writes dW_p slabs     bit 5  it forms a row gradient (dt or dh)     bit 6  it reads NRM_DZ_HL4 */
+int nrm_pwattn_bwd_form(int T, int H, int D, int pass, int mma, int dz_format);
 /* backward, step 2 in the "resident W_p" form (bf16 arithmetics, D <= 256): the same dt / dh as above from ONE contraction
  * dP = dz W_p whose W_p image stays in LDS and whose dz operand (NRM_DZ_HL4) is read exactly once; autograd of
  * models/attention_model.py:81-92 w.r.t. target and history.  nrm_pwattn_bwd_rw_supported: 1 if (D, mma) has this form;

@@ -50,6 +50,44 @@ static int check_dims(const char* fn, int B, int T, int H, int D) {
     return NRM_OK;
 }
 
+// plan of the (b,t)-grouped pass: nrm_pwattn_bwd_nsplit sizes the slab buffer that nrm_pwattn_bwd_contract then fills
+static nrm::BwdEPlan bwd_bt_plan(int B, int T, int D, int mma) {
+    const char* e = getenv("NRM_BT_WAVES");
+    return nrm::bwd_e_plan(D, B * T, e ? atoi(e) : kBtWaves, kBtMinGroups, mma);
+}
+
+// One launch of nrm_pwattn_bwd_contract: its parameter block and plan.  G = B G2 groups of R rows; X_g = the dz rows of group g, Y_g =
+// the R rows y[b]; out[g] += the row gradient.  pass 1: groups (b,t), rows r = h: X_g = dz[b,t,:,:], Y_g = h[b]; out = dt, scale rows = t,
+// dW_p slabs in ws; pass 4: the same without its dt epilogue; pass 2: groups (b,h), rows r = t: X_g = dz[b,:,h,:], Y_g = t[b]; out = dh
+struct BwdPass { nrm::BwdEParams p; nrm::BwdEPlan pl; bool with_dw; };
+static BwdPass bwd_pass(int pass, const float* dz, const float* t, const float* h, const float* wp, int ldwp, float* dt, float* dh,
+                        float* ws, int B, int T, int H, int D, int mma, int dz_format) {
+    const bool bh = pass == 2;
+    const int G2 = bh ? H : T, R = bh ? T : H; const long HD = (long)H * D;
+    nrm::BwdEParams p = {};
+    p.X = dz; p.xs1 = (long)T * HD; p.xs2 = bh ? D : HD; p.xrs = bh ? HD : D;
+    p.Y = bh ? t : h; p.ys1 = (long)R * D; p.yrs = D;
+    p.wp = wp; p.ldwp = ldwp; p.out = bh ? dh : dt; p.ldo = D;
+    p.G = B * G2; p.G2 = G2; p.R = R; p.D = D;
+    p.with_dt = pass != 4; p.x_hl4 = dz_format == NRM_DZ_HL4;
+    // big groups (C5: 128 rows x 768 columns = 393 KB of dz each): the waves of a workgroup walk neighbouring groups, which
+    // cuts what an XCD's L2 must hold -- FETCH_SIZE of the (b,t) pass at C5 26.3 -> 8.0 GB, same duration (the MALL had been
+    // absorbing the re-reads); small groups keep the blocked walk.  NRM_BT_INTERLEAVE=0|1 forces either (tests).
+    p.interleave = (long)R * D * (long)sizeof(float) > (256L << 10);       // ((b,h) pass: read by the serial kernel only -- bf16 forms, short T)
+    if (const char* e = getenv("NRM_BT_INTERLEAVE")) p.interleave = atoi(e);
+    if (bh) {                                           // no dW_p accumulators (<= 168 VGPRs): three waves per SIMD
+        const char* e = getenv("NRM_BH_WAVES");
+        return {p, nrm::bwd_e_plan(D, p.G, e ? atoi(e) : kBhWaves, 1, mma), false};
+    }
+    p.srow = t; p.lds_ = D; p.ws = ws;
+    if (const char* e = getenv("NRM_BT_ORDER")) p.order = atoi(e);
+    return {p, bwd_bt_plan(B, T, D, mma), true};
+}
+
+static bool bwd_dz_format_ok(int passes, int mma, int dz_format) {     // NRM_DZ_HL4: the dW_p-only pass (4) of the bf16 arithmetics alone
+    return dz_format == NRM_DZ_F32 || (dz_format == NRM_DZ_HL4 && passes == 4 && mma != NRM_MMA_F32);
+}
+
 extern "C" {
 
 int nrm_abi_version(void) { return NRM_ABI_VERSION; }
@@ -227,9 +265,7 @@ int nrm_pwattn_bwd_dp_dtdh(const float* dz, const float* t, const float* h, cons
 
 int nrm_pwattn_bwd_nsplit(int B, int T, int H, int D, int mma) {
     if (B <= 0 || T <= 0 || H <= 0 || D <= 0) return 0;
-    int tw1 = kBtWaves;
-    if (const char* e = getenv("NRM_BT_WAVES")) tw1 = atoi(e);
-    return nrm::bwd_e_plan(D, B * T, tw1, kBtMinGroups, mma).nsplit;
+    return bwd_bt_plan(B, T, D, mma).nsplit;
 }
 
 int nrm_pwattn_bwd_contract(const float* dz, const float* t, const float* h, const float* wp, int ldwp,
@@ -237,53 +273,29 @@ int nrm_pwattn_bwd_contract(const float* dz, const float* t, const float* h, con
                             int dz_format, nrm_stream_t stream) {
     if (int rc = check_dims("nrm_pwattn_bwd_contract", B, T, H, D)) return rc;
     if (int rc = check_mma("nrm_pwattn_bwd_contract", mma)) return rc;
-
     if (passes != 1 && passes != 2 && passes != 3 && passes != 4) return fail(NRM_EINVAL, "nrm_pwattn_bwd_contract: passes=%d", passes);
-    if ((dz_format != NRM_DZ_F32 && dz_format != NRM_DZ_HL4) || (dz_format == NRM_DZ_HL4 && (passes != 4 || mma == NRM_MMA_F32)))
+    if (!bwd_dz_format_ok(passes, mma, dz_format))
         return fail(NRM_EINVAL, "nrm_pwattn_bwd_contract: passes=%d mma=%d with dz_format=%d (only the dW_p-only pass, 4, of the bf16 arithmetics reads NRM_DZ_HL4)", passes, mma, dz_format);
     if (!dz || !t || !h || !wp) return fail(NRM_EINVAL, "nrm_pwattn_bwd_contract: null pointer");
     if (((passes & 1) && (!dt || !ws)) || ((passes & 2) && !dh) || (passes == 4 && !ws)) return fail(NRM_EINVAL, "nrm_pwattn_bwd_contract: null output");
     if (ldwp < D || ldwp % 4) return fail(NRM_EINVAL, "nrm_pwattn_bwd_contract: ldwp=%d", ldwp);
     if (B == 0) return NRM_OK;
-    const long HD = (long)H * D, TD = (long)T * D;
-    // pass 1: groups (b,t); rows r = h.  X_g = dz[b,t,:,:], Y_g = h[b];  out = dt, scale rows = t
-    if ((passes & 1) || passes == 4) {
-        nrm::BwdEParams p = {};
-        p.with_dt = passes == 4 ? 0 : 1; p.x_hl4 = dz_format == NRM_DZ_HL4 ? 1 : 0;
-        p.X = dz; p.xs1 = (long)T * HD; p.xs2 = HD; p.xrs = D;
-        p.Y = h; p.ys1 = HD; p.yrs = D;
-        p.wp = wp; p.ldwp = ldwp; p.srow = t; p.lds_ = D; p.out = dt; p.ldo = D; p.ws = ws;
-        p.G = B * T; p.G2 = T; p.R = H; p.D = D;
-        int tw1 = kBtWaves;
-        if (const char* e = getenv("NRM_BT_WAVES")) tw1 = atoi(e);
-        const nrm::BwdEPlan pl = nrm::bwd_e_plan(D, p.G, tw1, kBtMinGroups, mma);
-        // big groups (C5: 128 rows x 768 columns = 393 KB of dz each): the waves of a workgroup walk neighbouring groups, which
-        // cuts what an XCD's L2 must hold -- FETCH_SIZE of this pass at C5 26.3 -> 8.0 GB, same duration (the MALL had been
-        // absorbing the re-reads); small groups keep the blocked walk.  NRM_BT_INTERLEAVE=0|1 forces either (tests).
-        p.interleave = (long)p.R * D * (long)sizeof(float) > (256L << 10);
-        if (const char* e = getenv("NRM_BT_INTERLEAVE")) p.interleave = atoi(e);
-        p.order = 0;
-        if (const char* e = getenv("NRM_BT_ORDER")) p.order = atoi(e);
-        if (int rc = check_hip(nrm::bwd_e_launch(p, pl, true, mma, (hipStream_t)stream), "bwd_e pass 1")) return rc;
-    }
-    // pass 2: groups (b,h); rows r = t.  X_g = dz[b,:,h,:], Y_g = t[b];  out = dh
-    if (passes & 2) {
-        nrm::BwdEParams p = {};
-        p.X = dz; p.xs1 = (long)T * HD; p.xs2 = D; p.xrs = HD;
-        p.Y = t; p.ys1 = TD; p.yrs = D;
-        p.wp = wp; p.ldwp = ldwp; p.srow = nullptr; p.lds_ = 0; p.out = dh; p.ldo = D; p.ws = nullptr;
-        p.G = B * H; p.G2 = H; p.R = T; p.D = D; p.with_dt = 1;
-        // this variant keeps no dW_p accumulators (<= 168 VGPRs): three waves per SIMD
-        int tw = kBhWaves;
-        if (const char* e = getenv("NRM_BH_WAVES")) tw = atoi(e);
-        const nrm::BwdEPlan pl = nrm::bwd_e_plan(D, p.G, tw, 1, mma);
-        p.interleave = (long)p.R * D * (long)sizeof(float) > (256L << 10);       // read by the serial kernel only (bf16 forms, short T)
-        if (const char* e = getenv("NRM_BT_INTERLEAVE")) p.interleave = atoi(e);
-        if (int rc = check_hip(nrm::bwd_e_launch(p, pl, false, mma, (hipStream_t)stream), "bwd_e pass 2")) return rc;
+    for (int pass : {passes == 4 ? 4 : passes & 1, passes & 2}) {
+        if (!pass) continue;
+        const BwdPass a = bwd_pass(pass, dz, t, h, wp, ldwp, dt, dh, ws, B, T, H, D, mma, dz_format);
+        if (int rc = check_hip(nrm::bwd_e_launch(a.p, a.pl, a.with_dw, mma, (hipStream_t)stream), pass == 2 ? "bwd_e pass 2" : "bwd_e pass 1")) return rc;
     }
     return NRM_OK;
 }
 
+int nrm_pwattn_bwd_form(int T, int H, int D, int pass, int mma, int dz_format) {
+    if (check_dims("nrm_pwattn_bwd_form", 1, T, H, D) || check_mma("nrm_pwattn_bwd_form", mma)) return -1;
+    if ((pass != 1 && pass != 2 && pass != 4) || !bwd_dz_format_ok(pass, mma, dz_format)) return -1;
+    const BwdPass a = bwd_pass(pass, nullptr, nullptr, nullptr, nullptr, D, nullptr, nullptr, nullptr, 1, T, H, D, mma, dz_format);
+    const nrm::BwdEForm f = nrm::bwd_e_select(a.p, a.pl, a.with_dw, mma, nrm::bwd_e_knobs());
+    if (f.family == nrm::BWD_E_REFUSED) return -1;
+    return f.family | (f.exact ? 4 : 0) | (a.pl.DT == 5 ? 8 : 0) | (f.with_dw ? 16 : 0) | (f.with_dt ? 32 : 0) | (f.xhl4 ? 64 : 0);
+}
 
 // ------------------------------------------------------------------------------------------- dense layers
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

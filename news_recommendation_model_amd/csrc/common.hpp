@@ -12,6 +12,13 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;       // one v_mfma_f
 
 constexpr int WAVE = 64;
 
+// compute units of the CURRENT device (a process may drive several): queried per launch, not cached
+inline int device_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    return cus > 0 ? cus : 256;
+}
+
 // D(16x16) += A(16x4) * B(4x16), f32 in / f32 accumulate.
 // lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15];
 // it receives D[row = 4*(l>>4) + r][col = l&15] in element r of the accumulator.

@@ -1274,85 +1274,50 @@ BwdEPlan bwd_e_plan(int D, int G, int target_waves, int min_gps, int mma) {
     return pl;
 }
 
-static bool pipe_enabled() {
-    static const bool on = [] { const char* e = getenv("NRM_BH_PIPE"); return !(e && e[0] == '0'); }();
-    return on;
+BwdEKnobs bwd_e_knobs() {                                              // (read per launch: tests switch forms inside one process)
+    auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+    return {on("NRM_BH_PIPE"), on("NRM_DW_DIRECT"), on("NRM_DW_R32")};
 }
 
-template <int KT, int DT>
-static hipError_t launch_e_t(BwdEParams p, const BwdEPlan& pl, bool with_dw, int mma, hipStream_t st) {
-    p.nkw = pl.nkw; p.ndcol = pl.ndcol; p.gps = pl.gps; p.nsplit = pl.nsplit;
-    const dim3 grid(pl.nkw * pl.ndcol, (pl.nsplit + 3) / 4), block(256);
-    const bool exact = p.D % (16 * KT) == 0 && p.D % (16 * DT) == 0;
-    constexpr int KS_DW = DT;     // single pass (40 B of scratch at 5x5); the 3+2 sub-pass split is KS_DW = (DT + 1) / 2
-    if constexpr (KT != 4) {
-        if (mma != 0) return hipErrorInvalidValue;      // bwd_e_plan gives the bf16 forms 4x4 tiles only
+// Which kernel a contraction launch takes.  p: with_dt, x_hl4, R, D; pl: the tile shape; with_dw: the (b,t)-grouped pass.
+BwdEForm bwd_e_select(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, const BwdEKnobs& knobs) {
+    const int KT = pl.KT, DT = pl.DT;
+    const BwdEForm refused = {BWD_E_REFUSED, false, false, false, 0, false, mma};
+    // KS = DT: single pass (40 B of scratch at 5x5); the 3+2 sub-pass split is KS = (DT + 1) / 2
+    BwdEForm f = {BWD_E_SERIAL, with_dw, true, false, DT, p.D % (16 * KT) == 0 && p.D % (16 * DT) == 0, mma};
+    if (KT != 4) {
+        if (mma != 0) return refused;                   // bwd_e_plan gives the bf16 forms 4x4 tiles only
     } else if (mma == 1 || mma == 2) {
         if (!p.with_dt && !p.x_hl4) {                   // dW_p only from fp32 dz (no row gradient wanted; D > 256 keeps fp32 dz)
-            if (!with_dw) return hipErrorInvalidValue;
-            if (mma == 1) {
-                if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, 1, false, false>), grid, block, 0, st, p);
-                else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, 1, false, false>), grid, block, 0, st, p);
-            } else {
-                if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, 2, false, false>), grid, block, 0, st, p);
-                else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, 2, false, false>), grid, block, 0, st, p);
-            }
-            return hipGetLastError();
+            if (!with_dw) return refused;
+            f.with_dt = false;
+        } else if (!p.with_dt || p.x_hl4) {             // the dW_p-only pass of the resident-W backward (hl4 dz operand)
+            if (!with_dw || p.with_dt || !p.x_hl4) return refused;
+            f.with_dt = false; f.xhl4 = true;
+            if (knobs.dw_r32 && p.R <= 32) f.family = BWD_DW_R32;   // one 32-row MFMA step per group: Y kept in registers, X prefetched
         }
-        if (!p.with_dt || p.x_hl4) {                    // the dW_p-only pass of the resident-W backward (hl4 dz operand)
-            if (!with_dw || p.with_dt || !p.x_hl4) return hipErrorInvalidValue;
-            static const bool r32 = [] { const char* e = getenv("NRM_DW_R32"); return !(e && e[0] == '0'); }();
-            if (r32 && p.R <= 32) {                     // one 32-row MFMA step per group: Y kept in registers, X prefetched
-                if (mma == 1) {
-                    if (exact) hipLaunchKernelGGL((bwd_dw_r32_kernel<true, 1>), grid, block, 0, st, p);
-                    else       hipLaunchKernelGGL((bwd_dw_r32_kernel<false, 1>), grid, block, 0, st, p);
-                } else {
-                    if (exact) hipLaunchKernelGGL((bwd_dw_r32_kernel<true, 2>), grid, block, 0, st, p);
-                    else       hipLaunchKernelGGL((bwd_dw_r32_kernel<false, 2>), grid, block, 0, st, p);
-                }
-                return hipGetLastError();
-            }
-            if (mma == 1) {
-                if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, 1, false, true>), grid, block, 0, st, p);
-                else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, 1, false, true>), grid, block, 0, st, p);
-            } else {
-                if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, 2, false, true>), grid, block, 0, st, p);
-                else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, 2, false, true>), grid, block, 0, st, p);
-            }
-            return hipGetLastError();
-        }
-#define NRM_LAUNCH_E(M)                                                                                              \
-        if (with_dw) {                                                                                               \
-            if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, M>), grid, block, 0, st, p);       \
-            else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, M>), grid, block, 0, st, p);      \
-        } else {                                                                                                     \
-            if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, DT, false, true, M>), grid, block, 0, st, p);         \
-            else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, DT, false, false, M>), grid, block, 0, st, p);        \
-        }
-        if (mma == 1) { NRM_LAUNCH_E(1) } else { NRM_LAUNCH_E(2) }
-#undef NRM_LAUNCH_E
-        return hipGetLastError();
+        return f;                                       // (no pipelined and no one-accumulator kernel for the bf16 arithmetics)
     }
+    f.mma = 0;
     if (with_dw && !p.with_dt) {                        // fp32, dW_p only (no row gradient wanted, or beside the dP walk)
-        if (p.x_hl4) return hipErrorInvalidValue;
-        const char* e = getenv("NRM_DW_DIRECT");        // (read per launch: tests switch forms inside one process)
-        if (!(e && e[0] == '0') && (p.R + 3) / 4 >= DW_SETS) { // one accumulator set, the scale row folded into the operand
-            if (exact) hipLaunchKernelGGL((bwd_dw_direct_kernel<KT, DT, true>), grid, block, 0, st, p);
-            else       hipLaunchKernelGGL((bwd_dw_direct_kernel<KT, DT, false>), grid, block, 0, st, p);
-        } else
-        if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true, 0, false, false>), grid, block, 0, st, p);
-        else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false, 0, false, false>), grid, block, 0, st, p);
-    } else if (with_dw) {
-        if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, true>), grid, block, 0, st, p);
-        else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, KS_DW, true, false>), grid, block, 0, st, p);
-    } else if (pipe_enabled() && (p.R + 3) / 4 >= ((DT + 1) & ~1) + 2) {
-        if (exact) hipLaunchKernelGGL((bwd_e_pipe_kernel<KT, DT, true>), grid, block, 0, st, p);
-        else       hipLaunchKernelGGL((bwd_e_pipe_kernel<KT, DT, false>), grid, block, 0, st, p);
-    } else {
-        if (exact) hipLaunchKernelGGL((bwd_e_kernel<KT, DT, DT, false, true>), grid, block, 0, st, p);
-        else       hipLaunchKernelGGL((bwd_e_kernel<KT, DT, DT, false, false>), grid, block, 0, st, p);
+        if (p.x_hl4) return refused;
+        f.with_dt = false;
+        if (knobs.dw_direct && (p.R + 3) / 4 >= DW_SETS) f.family = BWD_DW_DIRECT;   // one accumulator set, the scale row folded into the operand
+    } else if (!with_dw && knobs.pipe && (p.R + 3) / 4 >= ((DT + 1) & ~1) + 2) {
+        f.family = BWD_E_PIPE;
     }
-    return hipGetLastError();
+    return f;
+}
+
+// f(tile, EXACT, MMA as integral constants) for the run-time triple: 5x5 tiles exist in fp32 only (bwd_e_plan, bwd_e_select)
+template <class F>
+static void with_tile_exact_mma(int tile, bool exact, int mma, F&& f) {
+    auto go = [&](auto t, auto m) { return exact ? f(t, std::true_type{}, m) : f(t, std::false_type{}, m); };
+    using T4 = std::integral_constant<int, 4>;
+    if (tile == 5) return go(std::integral_constant<int, 5>{}, std::integral_constant<int, 0>{});
+    if (mma == 1) return go(T4{}, std::integral_constant<int, 1>{});
+    if (mma == 2) return go(T4{}, std::integral_constant<int, 2>{});
+    return go(T4{}, std::integral_constant<int, 0>{});
 }
 
 int pwattn_bwd_diag_flags() {
@@ -1360,10 +1325,37 @@ int pwattn_bwd_diag_flags() {
            (NRM_DIAG_NOLOAD ? 128 : 0) | (NRM_PIPE_SGB != 1 ? 256 : 0);
 }
 
-hipError_t bwd_e_launch(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, hipStream_t st) {
-    if (p.G <= 0) return hipSuccess;
-    if (pl.DT == 5) return launch_e_t<5, 5>(p, pl, with_dw, mma, st);
-    return launch_e_t<4, 4>(p, pl, with_dw, mma, st);
+hipError_t bwd_e_launch(const BwdEParams& params, const BwdEPlan& pl, bool with_dw, int mma, hipStream_t st) {
+    if (params.G <= 0) return hipSuccess;
+    const BwdEForm f = bwd_e_select(params, pl, with_dw, mma, bwd_e_knobs());
+    BwdEParams p = params;
+    p.nkw = pl.nkw; p.ndcol = pl.ndcol; p.gps = pl.gps; p.nsplit = pl.nsplit;
+    const dim3 grid(pl.nkw * pl.ndcol, (pl.nsplit + 3) / 4), block(256);
+    hipError_t rc = hipErrorInvalidValue;               // stays for a refused form and for one without an instantiation (bwd_e_select names none)
+    if (f.family != BWD_E_REFUSED) with_tile_exact_mma(pl.DT, f.exact, f.mma, [&](auto tile, auto exact, auto arith) {
+        constexpr int KT = decltype(tile)::value, DT = KT, MMA = decltype(arith)::value;
+        constexpr bool EXACT = decltype(exact)::value;
+        constexpr std::true_type Y{}; constexpr std::false_type N{};
+        auto serial = [&](auto dw, auto dt, auto xhl4) {
+            hipLaunchKernelGGL((bwd_e_kernel<KT, DT, DT, decltype(dw)::value, EXACT, MMA, decltype(dt)::value, decltype(xhl4)::value>), grid, block, 0, st, p);
+        };
+        if (f.family == BWD_E_SERIAL) {
+            if (!f.with_dw) serial(N, Y, N);
+            else if (f.with_dt) serial(Y, Y, N);
+            else if (!f.xhl4) serial(Y, N, N);
+            else if constexpr (MMA != 0) serial(Y, N, Y);
+            else return;
+        } else if constexpr (MMA == 0) {
+            if (f.family == BWD_E_PIPE) hipLaunchKernelGGL((bwd_e_pipe_kernel<KT, DT, EXACT>), grid, block, 0, st, p);
+            else if (f.family == BWD_DW_DIRECT) hipLaunchKernelGGL((bwd_dw_direct_kernel<KT, DT, EXACT>), grid, block, 0, st, p);
+            else return;
+        } else {
+            if (f.family == BWD_DW_R32) hipLaunchKernelGGL((bwd_dw_r32_kernel<EXACT, MMA>), grid, block, 0, st, p);
+            else return;
+        }
+        rc = hipGetLastError();
+    });
+    return rc;
 }
 
 }  // namespace nrm

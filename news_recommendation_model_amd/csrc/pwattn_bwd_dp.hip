@@ -357,17 +357,11 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
 
 int pwattn_bwd_dp_diag_flags() { return NRM_DIAG_DP ? 1024 : 0; }
 
-static int dp_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return cus > 0 ? cus : 256;
-}
-
 template <int NT>
 static hipError_t launch_dp(BwdDpParams p, hipStream_t st) {
     // four rounds of workgroups at three per CU (measured at C3, 768 / 1536 / 3072 workgroups: 3.97 / 3.95 / 3.92 ms -- the CUs do not
     // finish equal ranges at the same time); never fewer than 4 steps per workgroup (a range pays one ring start and one dh flush)
-    long grid = 12L * dp_cus();
+    long grid = 12L * device_cus();
     if (const char* e = getenv("NRM_DP_GRID")) { const long v = atol(e); if (v > 0) grid = v; }
     if (grid > p.steps / 4) grid = p.steps / 4;
     if (grid < 1) grid = 1;

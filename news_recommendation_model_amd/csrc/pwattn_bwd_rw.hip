@@ -328,18 +328,12 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
 
 int pwattn_bwd_rw_diag_flags() { return NRM_DIAG_BRW ? 512 : 0; }
 
-static int brw_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return cus > 0 ? cus : 256;
-}
-
 template <int NG>
 static hipError_t launch_brw(BwdRwParams p, const BwdRwPlan& pl, int mma, hipStream_t st) {
     const int nht = (p.H + 15) / 16, ngs = pl.rows / (64 * NG);
     const long base = (long)p.B * nht * ngs;
     if (base <= 0) return hipSuccess;
-    int wgs = brw_cus() / pl.nks;
+    int wgs = device_cus() / pl.nks;
     if (wgs < 1) wgs = 1;
     // the candidate walk is cut into tsplit parts when the tasks would not fill the chip's wave slots twice over (every part adds
     // its dh with float atomics: C2, 2 rounds of tasks: 0.191 ms unsplit, 0.201 ms in two parts), as long as a part keeps >= 8 steps

@@ -565,19 +565,13 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
 #endif
 }
 
-static int rw_cus() {       // of the CURRENT device (a process may drive several): queried per launch, not cached
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return cus > 0 ? cus : 256;
-}
-
 // The launchers take the dense and the ragged (compact scoring) form alike: rg != nullptr selects the RAGGED instantiation, which exists
 // for fp32 arithmetic without a z store only.
 template <int NTS>
 static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
     const int ntile = (int)((p.M + 15) / 16);
     if (ntile <= 0) return hipSuccess;
-    int wgs = rw_cus() / pl.nsplit;                                     // one persistent workgroup per CU, CUs shared evenly by the slices
+    int wgs = device_cus() / pl.nsplit;                                     // one persistent workgroup per CU, CUs shared evenly by the slices
     if (wgs < 1) wgs = 1;
     if ((long)wgs * FB_WAVES > ntile) wgs = (ntile + FB_WAVES - 1) / FB_WAVES;
     const size_t shm = (size_t)pl.k32 * pl.wimg * NTS * 1024;
@@ -625,7 +619,7 @@ static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hip
     const int B = (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
     const long base = (long)B * nht;
     if (base <= 0) return hipSuccess;
-    int wgs = rw_cus() / pl.nsplit, tsplit;
+    int wgs = device_cus() / pl.nsplit, tsplit;
     if (wgs < 1) wgs = 1;
     if (hipError_t e = walk_grid(base, p.T, 8, p.T, wgs, tsplit)) return e;
     const size_t shm = (size_t)pl.k32 * pl.wimg * NTS * 1024;
@@ -653,7 +647,7 @@ static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const Ra
     const int B = rg ? rg->B : (int)(p.M / ((long)p.T * p.H)), nht = ((hrag ? rg->k_max : p.H) + 15) / 16;
     const long base = (long)B * nht;
     if (base <= 0 || (rg && rg->N <= 0)) return hipSuccess;
-    int wgs = 2 * rw_cus(), tsplit;                                     // two workgroups of 8 waves per CU
+    int wgs = 2 * device_cus(), tsplit;                                     // two workgroups of 8 waves per CU
     if (hipError_t e = walk_grid(base, rg ? (rg->N + rg->B - 1) / rg->B : p.T, 4, rg ? rg->max_count : p.T, wgs, tsplit)) return e;
     const size_t shm = (size_t)pl.k32 * NTS * 1024;
     const dim3 grid((unsigned)wgs), block(512);

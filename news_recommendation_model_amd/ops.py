@@ -576,6 +576,21 @@ def _use_dp_walk(lib, B, T, H, D, mma):
     return forced == "1" or B * T * H * D >= DP_MIN_ELEMS
 
 
+def _bwd_dtdh(lib, form, dz, t, h, w1, dt, dh, mma, st):
+    """dt and dh from ONE contraction dP = dz W_p (dz read once): 'rw', the resident-W kernel of the bf16 arithmetics (dz in NRM_DZ_HL4),
+    or 'dp', the fp32 dP walk (the forward's streaming skeleton walking the candidates).  An unwanted gradient goes to a scratch buffer."""
+    B, T, D = t.shape
+    H = h.shape[1]
+    entry, key, tail = ("nrm_pwattn_bwd_rw", mma, (mma,)) if form == "rw" else ("nrm_pwattn_bwd_dp", H, ())
+    img = torch.empty(getattr(lib, entry + "_packed_floats")(D, key), dtype=torch.float32, device=t.device)
+    native.call(entry + "_pack", native.ptr(w1), 4 * D, D, key, native.ptr(img), st)
+    dt_ = dt if dt.numel() else torch.empty(B, T, D, dtype=torch.float32, device=t.device)
+    dh_ = dh if dh.numel() else torch.empty(B, H, D, dtype=torch.float32, device=t.device)
+    _count_flops("contraction", 2.0 * B * T * H * D * D)
+    native.call(entry + "_dtdh", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(img), native.ptr(dt_), native.ptr(dh_),
+                B, T, H, D, *tail, st, tag="pwattn_bwd_rw_dtdh" if form == "rw" else "pwattn_bwd_dp_dtdh")
+
+
 def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=None):
     """``need_dt`` / ``need_dh``: whether the target / history rows want a gradient.  The text+image attention of the model reads
     raw input columns (reference user_invariant_interest_model.py:63-64,78: no parameter upstream), so autograd asks for neither
@@ -630,52 +645,32 @@ def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=Non
     nsplit = lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma)
     wsp = torch.empty(nsplit, D, D, dtype=torch.float32, device=dev)
     wp = w1[:, 3 * D:]                                   # view, row stride 4D
-    if rw:
-        # resident-W form: dt and dh from ONE contraction dP = dz W_p (dz read once), then the (b,t)-grouped pass without its dt
-        # epilogue for the dW_p slabs
-        if need_dt or need_dh:
-            img = torch.empty(lib.nrm_pwattn_bwd_rw_packed_floats(D, mma), dtype=torch.float32, device=dev)
-            native.call("nrm_pwattn_bwd_rw_pack", native.ptr(w1), 4 * D, D, mma, native.ptr(img), st)
-            # (one of the two unwanted: the kernel forms both anyway; the unwanted one goes to a scratch buffer)
-            dt_ = dt if need_dt else torch.empty(B, T, D, dtype=torch.float32, device=dev)
-            dh_ = dh if need_dh else torch.empty(B, H, D, dtype=torch.float32, device=dev)
-            _count_flops("contraction", 2.0 * B * T * H * D * D)
-            native.call("nrm_pwattn_bwd_rw_dtdh", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(img), native.ptr(dt_),
-                        native.ptr(dh_), B, T, H, D, mma, st, tag="pwattn_bwd_rw_dtdh")
+    # 'rw' (bf16 arithmetics with a resident-W backward) and 'dp' (fp32, both row gradients wanted, big enough or forced): dt and dh
+    # from ONE contraction, then the (b,t)-grouped pass without its dt epilogue for the dW_p slabs; 'e': the two grouped E-form passes
+    form = "rw" if rw else "dp" if need_dt and need_dh and _use_dp_walk(lib, B, T, H, D, mma) else "e"
+    rows = need_dt or need_dh
+
+    def contract(passes, tag, dz_format=DZ_F32, out=False):     # out: the launch writes row gradients (those that are wanted)
         _count_flops("contraction", 2.0 * B * T * H * D * D)
-        if not (need_dt or need_dh):
-            _wait_for_foreign_chain(B * T * H * D)
-        native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(wp), 4 * D, None, None,
-                    native.ptr(wsp), B, T, H, D, 4, mma, DZ_HL4, st, tag="pwattn_bwd_e_bt")
-        if need_dt or need_dh:
-            _note_chain_end()
-    elif need_dt and need_dh and _use_dp_walk(lib, B, T, H, D, mma):
-        # fp32, both row gradients wanted: dt and dh from ONE contraction dP = dz W_p (csrc/pwattn_bwd_dp.hip: the forward's
-        # streaming skeleton walking the candidates), then the (b,t)-grouped pass without its dt epilogue for the dW_p slabs
-        img = torch.empty(lib.nrm_pwattn_bwd_dp_packed_floats(D, H), dtype=torch.float32, device=dev)
-        native.call("nrm_pwattn_bwd_dp_pack", native.ptr(w1), 4 * D, D, H, native.ptr(img), st)
-        _count_flops("contraction", 2.0 * B * T * H * D * D)
-        native.call("nrm_pwattn_bwd_dp_dtdh", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(img), native.ptr(dt),
-                    native.ptr(dh), B, T, H, D, st, tag="pwattn_bwd_dp_dtdh")
-        _count_flops("contraction", 2.0 * B * T * H * D * D)
-        native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(wp), 4 * D, None, None,
-                    native.ptr(wsp), B, T, H, D, 4, mma, DZ_F32, st, tag="pwattn_bwd_e_dw")
-        _note_chain_end()
-    else:
+        if not rows:
+            _wait_for_foreign_chain(B * T * H * D)     # serves no row gradient: behind the other attention's chain (see _chain)
+        native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(wp), 4 * D,
+                    native.ptr(dt) if out and need_dt else None, native.ptr(dh) if out and need_dh else None,
+                    native.ptr(wsp), B, T, H, D, passes, mma, dz_format, st, tag=tag)
+
+    if form == "e":
         # two launches: (b,t)-grouped -> dt + dW_p slabs, (b,h)-grouped -> dh (issued separately so that
         # bench.py can time each kernel with its own event pair); the second one only when the history wants a gradient
         # (without a target gradient the first one runs without its dt epilogue: passes = 4)
-        for passes, tag in ((1, "pwattn_bwd_e_bt") if need_dt else (4, "pwattn_bwd_e_dw"), (2, "pwattn_bwd_e_bh")):
-            if passes == 2 and not need_dh:
-                continue
-            _count_flops("contraction", 2.0 * B * T * H * D * D)
-            if not (need_dt or need_dh):
-                _wait_for_foreign_chain(B * T * H * D)     # the dW_p-only pass: behind the other attention's chain (see _chain)
-            native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h),
-                        native.ptr(wp), 4 * D, native.ptr(dt) if need_dt else None, native.ptr(dh) if need_dh else None,
-                        native.ptr(wsp), B, T, H, D, passes, mma, DZ_F32, st, tag=tag)
-        if need_dt or need_dh:
-            _note_chain_end()
+        contract(1 if need_dt else 4, "pwattn_bwd_e_bt" if need_dt else "pwattn_bwd_e_dw", out=True)
+        if need_dh:
+            contract(2, "pwattn_bwd_e_bh", out=True)
+    else:
+        if rows:
+            _bwd_dtdh(lib, form, dz, t, h, w1, dt, dh, mma, st)
+        contract(4, "pwattn_bwd_e_bt" if rw else "pwattn_bwd_e_dw", DZ_HL4 if rw else DZ_F32)
+    if rows:
+        _note_chain_end()                              # the last contraction of a backward that produced a row gradient
     _slab_reduce(wsp, nsplit, D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
     return dt, dh, dw1, db1, acc
 

@@ -31,6 +31,106 @@ def test_abi_version_and_sizes(lib):
     assert lib.nrm_pwattn_bwd_nsplit(1, 1, 1, 64, 0) == 1
 
 
+def _bt_nsplit(B, T, D, mma, waves=6144, min_gps=96):
+    """bwd_e_plan (csrc/pwattn_bwd.hip) for the (b,t)-grouped pass, restated: 6144 wave tasks unless NRM_BT_WAVES says otherwise,
+    at least 96 groups per split or else exactly one round of the chip's 2048 wave slots."""
+    n16 = (D + 15) // 16
+    c5, c4 = (n16 + 4) // 5 * 5, (n16 + 3) // 4 * 4
+    tile = 5 if c5 < c4 and mma == 0 else 4
+    tiles = ((n16 + tile - 1) // tile) ** 2
+    G = B * T
+    ns = waves // tiles // 4 * 4
+    if ns > G // min_gps:
+        one_round = 2048 // tiles // 4 * 4
+        if 4 <= one_round < ns:
+            ns = one_round
+    ns = min(max(ns, 4), G)
+    gps = (G + ns - 1) // ns
+    return (G + gps - 1) // gps
+
+
+def test_slab_count_is_the_plan_of_the_bt_pass(lib, monkeypatch):
+    """nrm_pwattn_bwd_nsplit sizes the slab buffer nrm_pwattn_bwd_contract fills: both take the plan from one helper in capi.hip
+    (the NRM_BT_WAVES override included), held here to the plan arithmetic restated above."""
+    monkeypatch.delenv("NRM_BT_WAVES", raising=False)
+    shapes = [(1024, 30, 50, 400, 0), (1024, 30, 50, 400, 2), (512, 30, 32, 256, 2), (64, 5, 50, 400, 0), (2, 4, 16, 64, 0),
+              (2, 4, 16, 64, 2), (100, 30, 128, 768, 0), (7, 3, 17, 72, 0), (1, 1, 1, 64, 0)]
+    for B, T, H, D, mma in shapes:
+        assert lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma) == _bt_nsplit(B, T, D, mma), (B, T, H, D, mma)
+    monkeypatch.setenv("NRM_BT_WAVES", "2048")
+    for B, T, H, D, mma in shapes:
+        assert lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma) == _bt_nsplit(B, T, D, mma, waves=2048), (B, T, H, D, mma)
+
+
+# nrm_pwattn_bwd_form: family (bits 0-1), EXACT (bit 2), 5x5 wave tile (bit 3), writes dW_p (4), forms a row gradient (5), reads HL4 (6)
+SERIAL, PIPE, DIRECT, R32 = 0, 1, 2, 3
+F32, HL4 = 0, 1
+
+
+def _form(family, tile, exact, dw, dt, hl4=0):
+    return family | (4 if exact else 0) | (8 if tile == 5 else 0) | (16 if dw else 0) | (32 if dt else 0) | (64 if hl4 else 0)
+
+
+def _ask(lib, T, H, D, mma, pas, dz_format):
+    return lib.nrm_pwattn_bwd_form(T, H, D, pas, mma, dz_format)
+
+
+# (T, H, D, mma, pass, dz format) -> the kernel the launch takes with no knob set
+BWD_FORMS = [
+    ((30, 50, 400, 0, 1, F32), _form(SERIAL, 5, True, dw=1, dt=1)),
+    ((30, 50, 400, 0, 4, F32), _form(DIRECT, 5, True, dw=1, dt=0)),
+    ((30, 50, 400, 0, 2, F32), _form(PIPE, 5, True, dw=0, dt=1)),
+    ((28, 50, 400, 0, 2, F32), _form(SERIAL, 5, True, dw=0, dt=1)),            # the pipe needs R >= 29 at 5x5
+    ((29, 50, 400, 0, 2, F32), _form(PIPE, 5, True, dw=0, dt=1)),
+    ((30, 12, 400, 0, 4, F32), _form(SERIAL, 5, True, dw=1, dt=0)),            # the one-accumulator pass needs R >= 13
+    ((30, 13, 400, 0, 4, F32), _form(DIRECT, 5, True, dw=1, dt=0)),
+    ((21, 128, 768, 0, 2, F32), _form(PIPE, 4, True, dw=0, dt=1)),
+    ((20, 128, 768, 0, 2, F32), _form(SERIAL, 4, True, dw=0, dt=1)),           # R >= 21 at 4x4
+    ((5, 17, 72, 0, 1, F32), _form(SERIAL, 5, False, dw=1, dt=1)),
+    ((5, 20, 64, 0, 1, F32), _form(SERIAL, 4, True, dw=1, dt=1)),
+    ((30, 32, 256, 2, 4, HL4), _form(R32, 4, True, dw=1, dt=0, hl4=1)),
+    ((30, 33, 256, 2, 4, HL4), _form(SERIAL, 4, True, dw=1, dt=0, hl4=1)),     # more than one 32-row MFMA step per group
+    ((30, 32, 256, 1, 4, HL4), _form(R32, 4, True, dw=1, dt=0, hl4=1)),
+    ((30, 50, 400, 2, 4, F32), _form(SERIAL, 4, False, dw=1, dt=0)),           # dW_p only from fp32 dz; bf16 forms: 4x4 only
+    ((30, 50, 400, 1, 1, F32), _form(SERIAL, 4, False, dw=1, dt=1)),
+    ((30, 50, 256, 2, 2, F32), _form(SERIAL, 4, True, dw=0, dt=1)),            # no pipelined kernel for the bf16 arithmetics
+]
+BWD_FORM_KNOBS = ("NRM_DW_DIRECT", "NRM_BH_PIPE", "NRM_DW_R32", "NRM_BT_WAVES", "NRM_BH_WAVES")
+
+
+def test_backward_contraction_form_table(lib, monkeypatch):
+    """Which kernel a launch of nrm_pwattn_bwd_contract takes, for the shapes at which the choice turns: the table was read off
+    launch_e_t / bwd_e_plan as they stood before the selection moved into bwd_e_select."""
+    for k in BWD_FORM_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for args, want in BWD_FORMS:
+        assert _ask(lib, *args) == want, (args, _ask(lib, *args), want)
+
+
+def test_backward_contraction_form_obeys_its_knobs_per_call(lib, monkeypatch):
+    for k in BWD_FORM_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for knob, args, dflt, off in (
+            ("NRM_DW_DIRECT", (30, 50, 400, 0, 4, F32), _form(DIRECT, 5, True, dw=1, dt=0), _form(SERIAL, 5, True, dw=1, dt=0)),
+            ("NRM_BH_PIPE", (30, 50, 400, 0, 2, F32), _form(PIPE, 5, True, dw=0, dt=1), _form(SERIAL, 5, True, dw=0, dt=1)),
+            ("NRM_DW_R32", (30, 32, 256, 2, 4, HL4), _form(R32, 4, True, dw=1, dt=0, hl4=1), _form(SERIAL, 4, True, dw=1, dt=0, hl4=1))):
+        assert _ask(lib, *args) == dflt
+        monkeypatch.setenv(knob, "0")
+        assert _ask(lib, *args) == off, knob         # read at every call: the same process, the other kernel
+        monkeypatch.setenv(knob, "1")
+        assert _ask(lib, *args) == dflt, knob
+        monkeypatch.delenv(knob)
+
+
+def test_backward_contraction_form_refuses_what_the_launch_refuses(lib):
+    for args in [(30, 32, 256, 2, 1, HL4), (30, 32, 256, 2, 2, HL4), (30, 32, 256, 1, 2, HL4),     # HL4 is read by the dW_p-only pass alone
+                 (30, 32, 256, 0, 4, HL4), (30, 32, 256, 0, 1, HL4),                                 # ... and by the bf16 arithmetics alone
+                 (30, 50, 400, 3, 1, F32), (30, 50, 400, 7, 4, F32), (30, 50, 400, -1, 2, F32),      # unknown arithmetic
+                 (30, 50, 400, 0, 3, F32), (30, 50, 400, 0, 0, F32), (30, 50, 400, 0, 1, 2),         # one launch: pass 1, 2 or 4; unknown format
+                 (30, 50, 402, 0, 1, F32), (30, 50, 1028, 0, 1, F32), (0, 50, 400, 0, 1, F32)]:      # widths / sizes the entry refuses
+        assert _ask(lib, *args) == -1, args
+
+
 def test_in_tree_library_is_a_product_build(lib):
     """nrm_build_flags() is the OR of every timing-diagnostic override (scripts/_diag): 0 for the library the tests run."""
     assert lib.nrm_build_flags() == 0
