@@ -288,17 +288,36 @@ int nrm_frontend_fwd(const void* x, int x_is_f64, int nrows, int xcols, int P, i
                      int n_year, int n_month, int n_day, int n_hour, int e3,
                      float* lab, int ldlab, float* ti, int ldti, int* err, nrm_stream_t stream);
 /* backward of the label rows: accumulates (+=, float atomics) the table / sentiment-layer gradients.  d_cat_tab may be NULL:
- * the category-table gradient is then left to nrm_frontend_cat_grad */
+ * the category-table gradient is then left to nrm_frontend_cat_grad.  The seven other gradient pointers may be NULL together
+ * (d_cat_tab is then required): the small tables are left to nrm_frontend_bwd_tables */
 int nrm_frontend_bwd(const void* x, int x_is_f64, int nrows, int xcols, int P, int n_sub, int behaviour,
                      const float* dlab, int lddl, const float* sen_w, const float* sen_b,
                      int n_cat, int e0, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3,
                      float* d_cat_tab, float* d_sen_w, float* d_sen_b, float* d_type_tab,
                      float* d_year_tab, float* d_month_tab, float* d_day_tab, float* d_hour_tab, nrm_stream_t stream);
 
+/* gradients of the small tables (type, year, month, day, hour) and of the sentiment layer for up to two row sets (nrows = 0 skips
+ * one; both have the element type x_is_f64) as a one-hot contraction on v_mfma_f32_16x16x4_f32: a persistent launch whose
+ * workgroups store partial tables to ws, and a second kernel that adds them to the gradients (+=) in a fixed order, so the result
+ * is bitwise the same from run to run.  Non-finite gradient elements and rows with a non-finite sentiment scalar reach exactly the
+ * cells they reach in nrm_frontend_bwd (by float atomics).  ws: nrm_frontend_tables_ws_floats(nrows0 + nrows1, ...) floats; that
+ * function returns 0 for a shape these kernels do not take (more than 128 accumulator tiles of 16 x 16, or a staged block beyond
+ * 64 KB of LDS): such a shape goes to nrm_frontend_bwd. */
+long nrm_frontend_tables_ws_floats(long nrows_total, int n_sub, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3);
+int nrm_frontend_bwd_tables(const void* x0, int nrows0, int xcols0, int behaviour0, const float* dlab0, int lddl0,
+                            const void* x1, int nrows1, int xcols1, int behaviour1, const float* dlab1, int lddl1, int x_is_f64,
+                            int P, int n_sub, const float* sen_w, const float* sen_b,
+                            int e0, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3,
+                            float* d_sen_w, float* d_sen_b, float* d_type_tab,
+                            float* d_year_tab, float* d_month_tab, float* d_day_tab, float* d_hour_tab, float* ws, nrm_stream_t stream);
+
 /* category-table gradient of up to two row sets (history rows, candidate rows; nrows = 0 skips one) by a counting sort of the
  * (row, slot) references by category id and a gather-sum over runs of equal ids -- instead of (1 + n_sub) * e0 float atomics per
  * row.  d_cat_tab [n_cat, e0] is accumulated into (+=).  ws: nrm_frontend_cat_ws_ints(n_cat, nrows0 + nrows1, n_sub) int32 of
- * scratch.  Both row sets have the same element type (x_is_f64).  Summation order inside an id varies from run to run. */
+ * scratch.  Both row sets have the same element type (x_is_f64).  Summation order inside an id varies from run to run.  Up to
+ * 16384 ids the sort histograms and places the references in LDS, slice by slice, with no global atomic per reference.
+ * ws holds, with nref = (nrows0 + nrows1) * (n_sub + 1): [3 n_cat + 4 counters | nref category ids in reference order | refs:
+ * the nref references (row * (n_sub + 1) + slot, set 1 after set 0) sorted by id | refcat: their ids | per-slice histograms]. */
 long nrm_frontend_cat_ws_ints(int n_cat, long nrows_total, int n_sub);
 int nrm_frontend_cat_grad(const void* x0, int nrows0, int xcols0, const float* dlab0, int lddl0,
                           const void* x1, int nrows1, int xcols1, const float* dlab1, int lddl1, int x_is_f64,

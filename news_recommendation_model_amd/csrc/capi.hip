@@ -753,7 +753,8 @@ int nrm_frontend_bwd(const void* x, int x_is_f64, int nrows, int xcols, int P, i
                      float* d_cat_tab, float* d_sen_w, float* d_sen_b, float* d_type_tab,
                      float* d_year_tab, float* d_month_tab, float* d_day_tab, float* d_hour_tab, nrm_stream_t stream) {
     if (int rc = check_fe("nrm_frontend_bwd", nrows, xcols, P, n_sub, behaviour, e0, e1, e2, e3)) return rc;
-    if (!x || !dlab || !sen_w || !sen_b || !d_sen_w || !d_sen_b || !d_type_tab || !d_year_tab || !d_month_tab || !d_day_tab || !d_hour_tab)
+    const int n_small = !!d_sen_w + !!d_sen_b + !!d_type_tab + !!d_year_tab + !!d_month_tab + !!d_day_tab + !!d_hour_tab;
+    if (!x || !dlab || !sen_w || !sen_b || (n_small != 7 && (n_small != 0 || !d_cat_tab)))
         return fail(NRM_EINVAL, "nrm_frontend_bwd: null pointer");
     if (lddl < e0 + e1 + e2 + e3) return fail(NRM_EINVAL, "nrm_frontend_bwd: lddl=%d too small", lddl);
     nrm::FrontendParams p = {};
@@ -763,6 +764,42 @@ int nrm_frontend_bwd(const void* x, int x_is_f64, int nrows, int xcols, int P, i
     p.n_cat = n_cat; p.n_type = n_type; p.n_year = n_year; p.n_month = n_month; p.n_day = n_day; p.n_hour = n_hour;
     p.e0 = e0; p.e1 = e1; p.e2 = e2; p.e3 = e3; p.P = P; p.n_sub = n_sub; p.xcols = xcols; p.behaviour = behaviour;
     return check_hip(nrm::frontend_bwd_launch(p, x, x_is_f64, dlab, lddl, nrows, (hipStream_t)stream), "frontend_bwd");
+}
+
+static nrm::FrontendParams tab_dims(int n_sub, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3) {
+    nrm::FrontendParams p = {};
+    p.n_type = n_type; p.n_year = n_year; p.n_month = n_month; p.n_day = n_day; p.n_hour = n_hour;
+    p.e1 = e1; p.e2 = e2; p.e3 = e3; p.n_sub = n_sub;
+    return p;
+}
+
+long nrm_frontend_tables_ws_floats(long nrows_total, int n_sub, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3) {
+    if (nrows_total <= 0 || n_sub < 0) return 0;
+    return nrm::tab_grad_ws_floats(tab_dims(n_sub, e1, n_type, e2, n_year, n_month, n_day, n_hour, e3), nrows_total);
+}
+
+int nrm_frontend_bwd_tables(const void* x0, int nrows0, int xcols0, int behaviour0, const float* dlab0, int lddl0,
+                            const void* x1, int nrows1, int xcols1, int behaviour1, const float* dlab1, int lddl1, int x_is_f64,
+                            int P, int n_sub, const float* sen_w, const float* sen_b,
+                            int e0, int e1, int n_type, int e2, int n_year, int n_month, int n_day, int n_hour, int e3,
+                            float* d_sen_w, float* d_sen_b, float* d_type_tab,
+                            float* d_year_tab, float* d_month_tab, float* d_day_tab, float* d_hour_tab, float* ws, nrm_stream_t stream) {
+    if (nrows0 > 0) if (int rc = check_fe("nrm_frontend_bwd_tables", nrows0, xcols0, P, n_sub, behaviour0, e0, e1, e2, e3)) return rc;
+    if (nrows1 > 0) if (int rc = check_fe("nrm_frontend_bwd_tables", nrows1, xcols1, P, n_sub, behaviour1, e0, e1, e2, e3)) return rc;
+    if (nrows0 < 0 || nrows1 < 0 || (long)nrows0 + nrows1 >= (1L << 31) - 64) return fail(NRM_EINVAL, "nrm_frontend_bwd_tables: nrows=%d,%d", nrows0, nrows1);
+    if ((nrows0 > 0 && (!x0 || !dlab0 || lddl0 < e0 + e1 + e2 + e3)) || (nrows1 > 0 && (!x1 || !dlab1 || lddl1 < e0 + e1 + e2 + e3)))
+        return fail(NRM_EINVAL, "nrm_frontend_bwd_tables: null pointer or lddl too small");
+    if (!sen_w || !sen_b || !d_sen_w || !d_sen_b || !d_type_tab || !d_year_tab || !d_month_tab || !d_day_tab || !d_hour_tab || !ws)
+        return fail(NRM_EINVAL, "nrm_frontend_bwd_tables: null pointer");
+    nrm::FrontendParams p = tab_dims(n_sub, e1, n_type, e2, n_year, n_month, n_day, n_hour, e3);
+    p.e0 = e0; p.P = P; p.n_cat = 1;               // (the category columns are not read here)
+    p.sen_w = sen_w; p.sen_b = sen_b;
+    p.d_sen_w = d_sen_w; p.d_sen_b = d_sen_b; p.d_type_tab = d_type_tab;
+    p.d_year_tab = d_year_tab; p.d_month_tab = d_month_tab; p.d_day_tab = d_day_tab; p.d_hour_tab = d_hour_tab;
+    if (nrm::tab_grad_ws_floats(p, (long)nrows0 + nrows1) <= 0 && nrows0 + nrows1 > 0)
+        return fail(NRM_EINVAL, "nrm_frontend_bwd_tables: shape not taken (nrm_frontend_tables_ws_floats is 0): use nrm_frontend_bwd");
+    return check_hip(nrm::tab_grad_launch(p, x0, nrows0, xcols0, dlab0, lddl0, x1, nrows1, xcols1, dlab1, lddl1, x_is_f64, ws,
+                                          (hipStream_t)stream), "frontend_bwd_tables");
 }
 
 long nrm_frontend_cat_ws_ints(int n_cat, long nrows_total, int n_sub) {

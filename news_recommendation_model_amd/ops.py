@@ -1843,6 +1843,8 @@ def _frontend_bwd_impl(dlab, x, behaviour, n_sub, P, cat_tab, sen_w, sen_b, type
 # (measured per step: C3, 98 M atomics: 32.4 -> 31.9 ms; C2, 24 M: 3.36 -> 3.39; reference default, 11 M: 1.51 -> 1.65).
 # NRM_FE_SORT=0 / 1 forces the scatter / the sort.
 FE_SORT_MIN_ATOMICS = 50_000_000
+# the small tables (type, time, sentiment layer) go to the matrix-core kernels (frontend.hip: tab_grad_launch) wherever
+# nrm_frontend_tables_ws_floats takes the shape; NRM_FE_TABLES=0 keeps them in nrm_frontend_bwd's LDS atomics.
 
 
 def _frontend_bwd_sets(sets, n_sub, P, tabs):
@@ -1865,15 +1867,28 @@ def _frontend_bwd_sets(sets, n_sub, P, tabs):
     sort = (forced != "0" and (forced == "1" or refs * e0 >= FE_SORT_MIN_ATOMICS) and 1 <= n_sub <= 16 and e0 <= 512
             and len({x.dtype for _, x, _ in prepared}) == 1 and refs < (1 << 31))
     st = native.stream_ptr()
-    for dlab, x, behaviour in prepared:
+    one_dtype = len({x.dtype for _, x, _ in prepared}) == 1
+    rows = sum(x.shape[0] for _, x, _ in prepared)
+    (dl0, x0, beh0), (dl1, x1, beh1) = prepared[0], (prepared[1] if len(prepared) > 1 else (None, None, False))
+    tab_ws = 0
+    if _os.environ.get("NRM_FE_TABLES") != "0" and one_dtype and len(prepared) <= 2:
+        tab_ws = native.load().nrm_frontend_tables_ws_floats(rows, n_sub, e1, n_type, e2, n_year, n_month, n_day, n_hour, e3)
+    small = (None,) * 7 if tab_ws else tuple(native.ptr(g) for g in (d_sw, d_sb, d_type, d_year, d_month, d_day, d_hour))
+    if tab_ws:
+        ws = torch.empty(tab_ws, dtype=torch.float32, device=dev)
+        native.call("nrm_frontend_bwd_tables", native.ptr(x0), x0.shape[0], x0.shape[1], 1 if beh0 else 0, native.ptr(dl0), dl0.stride(0),
+                    native.ptr(x1) if x1 is not None else None, x1.shape[0] if x1 is not None else 0,
+                    x1.shape[1] if x1 is not None else 0, 1 if beh1 else 0, native.ptr(dl1) if x1 is not None else None,
+                    dl1.stride(0) if x1 is not None else 0, 1 if x0.dtype == torch.float64 else 0, P, n_sub,
+                    native.ptr(sen_w), native.ptr(sen_b), e0, e1, n_type, e2, n_year, n_month, n_day, n_hour, e3,
+                    native.ptr(d_sw), native.ptr(d_sb), native.ptr(d_type), native.ptr(d_year), native.ptr(d_month),
+                    native.ptr(d_day), native.ptr(d_hour), native.ptr(ws), st)
+    for dlab, x, behaviour in (prepared if not (tab_ws and sort) else ()):
         native.call("nrm_frontend_bwd", native.ptr(x), 1 if x.dtype == torch.float64 else 0, x.shape[0], x.shape[1], P,
                     n_sub, 1 if behaviour else 0, native.ptr(dlab), dlab.stride(0), native.ptr(sen_w), native.ptr(sen_b),
                     n_cat, e0, e1, n_type, e2, n_year, n_month, n_day, n_hour, e3,
-                    None if sort else native.ptr(d_cat), native.ptr(d_sw), native.ptr(d_sb), native.ptr(d_type),
-                    native.ptr(d_year), native.ptr(d_month), native.ptr(d_day), native.ptr(d_hour), st)
+                    None if sort else native.ptr(d_cat), *small, st)
     if sort:
-        (dl0, x0, _), (dl1, x1, _) = prepared[0], (prepared[1] if len(prepared) > 1 else (None, None, None))
-        rows = x0.shape[0] + (x1.shape[0] if x1 is not None else 0)
         ws = torch.empty(native.load().nrm_frontend_cat_ws_ints(n_cat, rows, n_sub), dtype=torch.int32, device=dev)
         native.call("nrm_frontend_cat_grad", native.ptr(x0), x0.shape[0], x0.shape[1], native.ptr(dl0), dl0.stride(0),
                     native.ptr(x1) if x1 is not None else None, x1.shape[0] if x1 is not None else 0,
@@ -1928,8 +1943,8 @@ def frontend(x, behaviour, n_sub, P, cat_tab, sen_w, sen_b, type_tab, year_tab, 
     return lab.reshape(B, N, -1) if lab.is_contiguous() else lab.unflatten(0, (B, N)), ti.unflatten(0, (B, N))
 
 
-# history + candidate rows through ONE autograd node: the two backward launches accumulate (float atomics) into one zeroed
-# arena, instead of two arenas, two fills and eight adds of autograd
+# history + candidate rows through ONE autograd node: one backward launch pair (or, for shapes the table kernels do not take, two
+# launches with float atomics) accumulates into one zeroed arena, instead of two arenas, two fills and eight adds of autograd
 def _frontend_pair_fwd_impl(xh, xt, n_sub, P, cat_tab, sen_w, sen_b, type_tab, year_tab, month_tab, day_tab, hour_tab):
     tabs = (cat_tab, sen_w, sen_b, type_tab, year_tab, month_tab, day_tab, hour_tab)
     lab_h, ti_h = _frontend_fwd_impl(xh, True, n_sub, P, *tabs)
