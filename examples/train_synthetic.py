@@ -4,12 +4,14 @@ Modules: model = UserModel(max_user_id) re-dimensioned as BASELINE's configs do,
 launch), host float64 batches staged one ahead, per-impression AUC on the device, a checkpoint without `delta` per epoch.
 
     python examples/train_synthetic.py --workload C1-demo --batches 20 --epochs 2
+    python examples/train_synthetic.py --workload ref-default --compact-history --history-lengths uniform      
 """
 import argparse
 import os
 import sys
 import tempfile
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,6 +28,9 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt-dir", default=None)
+    ap.add_argument("--compact-history", action="store_true", help="do not compute the padded history rows (train_step(compact_history=True))")
+    ap.add_argument("--history-lengths", default="full", choices=["full", "uniform", "tenth"],
+                    help="cut the synthetic histories the way the ETL pads them: rows past a user's own are all-zero (uniform in [1, H] / all H/10)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
@@ -40,8 +45,14 @@ def main():
     # the data takes the reference's route: records in zstd+pickle subvolumes behind a head file (process_data.py:252-291),
     # read back with load_processed_dataset (:92-145) and batched as DataLoader(shuffle=True) does (train.py:40)
     records = []
+    rng = np.random.default_rng(args.seed)
     for i in range(args.batches):
-        records += data_io.records_from_batch(synth.make_batch(dims, B, wl["H"], wl["T"], seed=1000 + i, user_num=user_num))
+        batch = synth.make_batch(dims, B, wl["H"], wl["T"], seed=1000 + i, user_num=user_num)
+        if args.history_lengths != "full":
+            lengths = rng.integers(1, wl["H"] + 1, B) if args.history_lengths == "uniform" else np.full(B, max(wl["H"] // 10, 1))
+            for b in range(B):
+                batch["x_history"][b, int(lengths[b]):] = 0.0
+        records += data_io.records_from_batch(batch)
     head = data_io.write_processed_dataset(records, os.path.join(ckpt_dir, "synthetic_train_processed"), subvolume_item_num=4 * B)
     records, max_user_id = data_io.load_processed_dataset(head)
     epoch_no = [0]
@@ -51,7 +62,7 @@ def main():
         return (b for b in data_io.iter_batches(records, B, shuffle=True, seed=args.seed + epoch_no[0]) if len(b["user_id"]) == B)
     hosts = list(data_io.iter_batches(records, B, shuffle=False))
     hist = trainer.train_epochs(model, opt, loader, args.epochs,
-                                ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"))
+                                ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"), compact_history=args.compact_history)
     for rec in hist:
         print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec))
     # the checkpoint round-trips into a fresh model (test.py:159-160) and validates (verify.py:19-43)

@@ -412,6 +412,30 @@ int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const
 int nrm_pool_bmm_hragged(const float* s, const float* h, float* out, const int* cand_off, const int* hist_off, const int* hist_mult,
                          const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D, nrm_stream_t stream);
 
+/* ---- training on compacted histories: length groups through the dense kernels
+ * The padded history rows are scored and pooled unmasked in training too (reference models/user_invariant_interest_model.py:77-78,
+ * 83-87).  The batch is sorted by history length and cut into G contiguous groups; group g (impressions b0_g .. b0_{g+1} - 1 of the
+ * sorted order) is trimmed to H_g <= H rows and runs through the DENSE attention entries above with H = H_g.  Where H_g < H, row
+ * H_g - 1 of every impression of the group is a padded row that stands for w_g = H - H_g + 1 equal rows, and only the pool sees it:
+ *   pooled[b,t,:] = sum_{j < H_g - 1} s[b,t,j] h[b,j,:] + w_g s[b,t,H_g - 1] h[b,H_g - 1,:]
+ *
+ * nrm_history_gather_groups: the grouped history arena, xh_arena[row_off[g] + (b - b0_g) H_g + j, :] = x_history[src_imp[b], j, :] for
+ *   j < H_g (bitwise, float64 or float32; the sorted x_history is never formed).  Tables (int32, device): src_imp [B] (the sort
+ *   permutation), group_b0 [G + 1], group_row_off [G + 1], group_h [G]; R = group_row_off[G]; G <= 64.  One wave per kept row, one launch
+ *   for all groups; table entries are clamped to the arrays.  Replaces the padded rows' share of user_invariant_interest_model.py:75-78.
+ * nrm_pool_bmm_wlast: nrm_pool_bmm with a weighted last row, wlast >= 1.  wlast_row = 0: the weight is on the reduction index J - 1,
+ *   applied where W is read (forward pool, user_invariant_interest_model.py:86-87; W = s stays unweighted in memory).  wlast_row = 1: the
+ *   weight is on output row I - 1 and scales only the product formed by this launch, not what `accumulate` finds there (the pool's
+ *   history gradient, autograd's backward of :86-87).  wlast = 1 is bitwise nrm_pool_bmm.
+ * nrm_pool_rowdot_wlast: nrm_pool_rowdot with ds[b,t,H - 1] = wlast * g[b,t,:] . h[b,H - 1,:] (autograd's backward of :86-87 with respect
+ *   to the scores); wlast = 1 is bitwise nrm_pool_rowdot. */
+int nrm_history_gather_groups(const void* x_history, int cols, int is_f64, const int* src_imp, const int* group_b0, const int* group_row_off,
+                              const int* group_h, int G, int B, int H, int R, void* xh_arena, nrm_stream_t stream);
+int nrm_pool_bmm_wlast(const float* W, long wsb, long wsi, long wsj, const float* X, int ldx, float* out,
+                       int B, int I, int J, int D, int accumulate, float wlast, int wlast_row, nrm_stream_t stream);
+int nrm_pool_rowdot_wlast(const float* g, int ldg, const float* h, float* ds, int B, int T, int H, int D, float* zero_out, int zero_n,
+                          float wlast, nrm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

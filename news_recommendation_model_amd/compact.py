@@ -163,3 +163,109 @@ def compact_scores_reference(logits, plan, dtype=np.float64):
             acc = ex / ex.sum()
         out[b, :n] = acc
     return out
+
+
+# ------------------------------------------------------------------------------------------------ training: history length groups
+#   The compacted TRAINING step sorts the batch by history length and cuts it into a few contiguous groups, each
+# trimmed to its own height H_g and run through the dense kernels; only the pool sees that the last kept row of a trimmed group
+# stands for w_g = H - H_g + 1 equal padded rows.
+MAX_GROUPS = 2          # default of plan_history_groups / train_step.  Speed: not measured on an MI355X -- the conservative value
+MIN_SAVING = 0.25       # a plan that drops less than this share of the B * H history rows runs dense.  Not measured either.
+GROUPS_CAP = 64         # csrc/compact.hpp HISTORY_GROUPS_MAX
+
+
+class HistoryGroupPlan:
+    """Length groups of one batch (host numpy; ``upload`` puts the tables on a device with ONE pinned copy).
+
+      B, H, G, quantum   impressions, history rows of the input, groups, the multiple every trimmed height is rounded up to
+      hist_len [B]       ``L_b`` clamped to [0, H], in the CALLER's order
+      perm [B]           stable argsort of hist_len: sorted impression i is impression perm[i] of the batch
+      inverse [B]        ``inverse[perm] == arange(B)``: row of the sorted order that holds impression b
+      bounds [G + 1]     group g = sorted impressions bounds[g] .. bounds[g + 1] - 1
+      H_g [G]            rows kept per impression of the group: min(H, quantum * ceil((max L_b + 1) / quantum))
+      w_g [G]            ``H - H_g + 1``: how many equal rows row H_g - 1 stands for (1 where H_g == H: the dense computation)
+      row_off [G + 1]    first row of each group in the grouped history arena, ``row_off[g + 1] - row_off[g] = B_g * H_g``
+      R                  ``row_off[G]``: history rows the step computes instead of B * H
+      saving             ``1 - R / (B * H)``
+      dense              nothing worth dropping: every H_g == H, or saving < MIN_SAVING
+    """
+
+    __slots__ = ("B", "H", "G", "quantum", "hist_len", "perm", "inverse", "bounds", "H_g", "w_g", "row_off", "R", "saving", "dense",
+                 "device_tables")
+
+    def upload(self, device):
+        """-> dict of int32 device views (perm, inverse, bounds, row_off, H_g) of ONE buffer copied from pinned host memory
+        (non-blocking).  Cached on the plan."""
+        import torch
+        if self.device_tables is not None and self.device_tables["perm"].device == torch.device(device):
+            return self.device_tables
+        parts = [("perm", self.perm), ("inverse", self.inverse), ("bounds", self.bounds), ("row_off", self.row_off), ("H_g", self.H_g)]
+        host = torch.empty(sum(len(p) for _, p in parts), dtype=torch.int32)
+        if torch.cuda.is_available():
+            host = host.pin_memory()
+        host.numpy()[:] = np.concatenate([p for _, p in parts])
+        dev = host.to(device, non_blocking=True)
+        tabs, o = {"_host": host}, 0
+        for name, p in parts:
+            tabs[name] = dev[o:o + len(p)]
+            o += len(p)
+        self.device_tables = tabs
+        return tabs
+
+
+def plan_history_groups(hist_len, H, max_groups=None, quantum=16):
+    """``hist_len`` [B]: ``L_b`` as ``ops.history_len`` measures it (host array or tensor; entries are clamped to [0, H]).  Sorts the
+    impressions by length (stable) and cuts the sorted order into at most ``max_groups`` contiguous groups that minimise the kept rows
+    ``sum_g B_g * H_g`` -- contiguous groups of the sorted order are optimal (a group's height is set by its longest member), and the
+    dynamic programme over the cut points is exact.  A group only ever ends where the quantised height changes: a cut inside a run
+    of equal heights saves nothing.  Ties go to fewer groups (every group multiplies the launches)."""
+    if hasattr(hist_len, "detach"):
+        hist_len = hist_len.detach().cpu().numpy()
+    H, q = int(H), int(quantum)
+    max_groups = MAX_GROUPS if max_groups is None else int(max_groups)
+    if H < 1 or q < 1 or not 1 <= max_groups <= GROUPS_CAP:
+        raise ValueError(f"plan_history_groups: H={H} quantum={q} max_groups={max_groups} (H, quantum >= 1, 1 <= max_groups <= {GROUPS_CAP})")
+    L = np.clip(np.asarray(hist_len).reshape(-1).astype(np.int64), 0, H)
+    B = int(L.shape[0])
+    if B * H >= 2 ** 31:
+        raise ValueError("plan_history_groups: more than 2^31 history rows")
+    perm = np.argsort(L, kind="stable")
+    inverse = np.empty(B, dtype=np.int64)
+    inverse[perm] = np.arange(B)
+    height = np.minimum(H, q * ((L[perm] + q) // q))                 # q * ceil((L + 1) / q) of each sorted impression: non-decreasing
+    ends = (np.flatnonzero(np.diff(height)) + 1).tolist() + [B] if B else []      # where a group may end
+    K = len(ends)
+    h_end = [int(height[e - 1]) for e in ends]
+    INF = float("inf")
+    # cost[g][k]: fewest rows of the first ends[k] impressions in exactly g + 1 groups, the last of which ends at ends[k]
+    cost = [[INF] * K for _ in range(min(max_groups, K))]
+    back = [[-1] * K for _ in range(min(max_groups, K))]
+    for k in range(K):
+        cost[0][k] = ends[k] * h_end[k]
+    for g in range(1, len(cost)):
+        for k in range(g, K):
+            for i in range(g - 1, k):
+                c = cost[g - 1][i] + (ends[k] - ends[i]) * h_end[k]
+                if c < cost[g][k]:
+                    cost[g][k], back[g][k] = c, i
+    cuts = []
+    if K:
+        g = min(range(len(cost)), key=lambda gg: (cost[gg][K - 1], gg))
+        k = K - 1
+        while k >= 0 and g >= 0:
+            cuts.append(ends[k])
+            k, g = back[g][k], g - 1
+    bounds = np.array([0] + cuts[::-1], dtype=np.int64)
+    G = len(bounds) - 1
+    H_g = np.array([int(height[bounds[g + 1] - 1]) for g in range(G)], dtype=np.int64)
+    row_off = np.zeros(G + 1, dtype=np.int64)
+    np.cumsum(np.diff(bounds) * H_g, out=row_off[1:])
+    plan = HistoryGroupPlan()
+    plan.B, plan.H, plan.G, plan.quantum = B, H, G, q
+    plan.hist_len, plan.perm, plan.inverse = L.astype(np.int32), perm.astype(np.int32), inverse.astype(np.int32)
+    plan.bounds, plan.H_g, plan.w_g, plan.row_off = bounds.astype(np.int32), H_g.astype(np.int32), (H - H_g + 1).astype(np.int32), row_off.astype(np.int32)
+    plan.R = int(row_off[G])
+    plan.saving = 1.0 - plan.R / (B * H) if B else 0.0
+    plan.dense = bool((H_g == H).all()) or plan.saving < MIN_SAVING
+    plan.device_tables = None
+    return plan

@@ -685,6 +685,42 @@ int nrm_history_tiles(const int* cand_imp, const int* cand_off, const int* hist_
     return check_hip(nrm::history_tiles_launch(cand_imp, cand_off, hist_off, tile_pre, B, N, R, Mt, (int4*)tile_tab, (hipStream_t)stream), "history_tiles");
 }
 
+// ---- training on compacted histories
+int nrm_history_gather_groups(const void* x_history, int cols, int is_f64, const int* src_imp, const int* group_b0, const int* group_row_off,
+                              const int* group_h, int G, int B, int H, int R, void* xh_arena, nrm_stream_t stream) {
+    if (B < 0 || H < 0 || cols <= 0 || R < 0 || G < 0 || G > nrm::HISTORY_GROUPS_MAX || (long)R > (long)B * H)
+        return fail(NRM_EINVAL, "nrm_history_gather_groups: B=%d H=%d cols=%d R=%d G=%d (0 <= G <= %d, R <= B*H)", B, H, cols, R, G, nrm::HISTORY_GROUPS_MAX);
+    if ((long)cols * 2 >= (1L << 31)) return fail(NRM_EINVAL, "nrm_history_gather_groups: cols=%d", cols);
+    if (R > 0 && (!x_history || !xh_arena || !src_imp || !group_b0 || !group_row_off || !group_h || G == 0))
+        return fail(NRM_EINVAL, "nrm_history_gather_groups: null pointer (or R=%d rows in G=0 groups)", R);
+    return check_hip(nrm::history_gather_groups_launch((const unsigned*)x_history, (unsigned*)xh_arena, cols * (is_f64 ? 2 : 1), src_imp, group_b0,
+                                                       group_row_off, group_h, G, B, H, R, (hipStream_t)stream), "history_gather_groups");
+}
+
+int nrm_pool_bmm_wlast(const float* W, long wsb, long wsi, long wsj, const float* X, int ldx, float* out,
+                       int B, int I, int J, int D, int accumulate, float wlast, int wlast_row, nrm_stream_t stream) {
+    if (!W || !X || !out) return fail(NRM_EINVAL, "nrm_pool_bmm_wlast: null pointer");
+    if (B < 0 || I <= 0 || J <= 0 || D <= 0 || D % 4 || B > 65535) return fail(NRM_EINVAL, "nrm_pool_bmm_wlast: B=%d I=%d J=%d D=%d", B, I, J, D);
+    if (ldx < D || ldx % 4 || !al16(X) || (long)J * ldx * 4 >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_pool_bmm_wlast: ldx=%d (>= D, a multiple of 4, X 16-byte aligned, J*ldx*4 < 2^31)", ldx);
+    if (!(wlast >= 1.f) || (wlast_row != 0 && wlast_row != 1))
+        return fail(NRM_EINVAL, "nrm_pool_bmm_wlast: wlast=%g wlast_row=%d (wlast >= 1: the rows the last one stands for; wlast_row 0 or 1)", (double)wlast, wlast_row);
+    return check_hip(nrm::bmm_rows_wlast_launch(W, wsb, wsi, wsj, X, (long)J * ldx, ldx, out, (long)I * D, D, B, I, J, D, accumulate, wlast, wlast_row,
+                                                (hipStream_t)stream), "pool_bmm_wlast");
+}
+
+int nrm_pool_rowdot_wlast(const float* g, int ldg, const float* h, float* ds, int B, int T, int H, int D, float* zero_out, int zero_n,
+                          float wlast, nrm_stream_t stream) {
+    if (!g || !h || !ds) return fail(NRM_EINVAL, "nrm_pool_rowdot_wlast: null pointer");
+    if (B < 0 || T <= 0 || H <= 0 || D <= 0 || D % 4 || D > 1024 || B > 65535) return fail(NRM_EINVAL, "nrm_pool_rowdot_wlast: B=%d T=%d H=%d D=%d", B, T, H, D);
+    if (ldg < D || ldg % 4 || !al16(g) || (long)T * ldg * 4 >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_pool_rowdot_wlast: ldg=%d (>= D, a multiple of 4, g 16-byte aligned, T*ldg*4 < 2^31)", ldg);
+    if (zero_n < 0 || (zero_n > 0 && !zero_out)) return fail(NRM_EINVAL, "nrm_pool_rowdot_wlast: zero_n=%d without zero_out", zero_n);
+    if (!(wlast >= 1.f)) return fail(NRM_EINVAL, "nrm_pool_rowdot_wlast: wlast=%g (>= 1: the rows the last one stands for)", (double)wlast);
+    return check_hip(nrm::rowdot_wlast_launch(g, (long)T * ldg, ldg, h, (long)H * D, D, ds, B, T, H, D, zero_out, zero_n, wlast, (hipStream_t)stream),
+                     "pool_rowdot_wlast");
+}
+
 int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,
                              const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream) {
     if (!logits || !cand_off || !pad_mult || !score || !rank || !live) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: null pointer");

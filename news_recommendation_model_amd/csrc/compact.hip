@@ -133,6 +133,37 @@ hipError_t history_gather_launch(const unsigned* x, unsigned* xh_c, int words, c
     return hipGetLastError();
 }
 
+// Grouped arena (section 5e).  One wave per kept row r < R: its group is the last g with row_off[g] <= r (G is a handful: a walk), then
+// r - row_off[g] = (b - b0[g]) * hg[g] + j.  Every table entry is clamped: a table that does not add up copies a wrong row or none,
+// never reads or writes outside x [B, H, words] and xh_g [R, words].
+__global__ __launch_bounds__(256) void history_gather_groups_kernel(const unsigned* __restrict__ x, unsigned* __restrict__ xh_g, int words,
+                                                                    const int* __restrict__ src_imp, const int* __restrict__ b0,
+                                                                    const int* __restrict__ row_off, const int* __restrict__ hg,
+                                                                    int G, int B, int H, int R) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R) return;
+    int g = 0;
+    for (int k = 1; k < G; ++k)
+        if ((long)min(max(row_off[k], 0), R) <= row) g = k;
+    const int r0 = min(max(row_off[g], 0), R);
+    const int hgg = min(max(hg[g], 1), H);
+    const int local = (int)(row - r0);
+    const int bs = min(max(b0[g], 0), B - 1) + local / hgg, j = local - (local / hgg) * hgg;      // j < hgg <= H
+    if (bs >= B) return;
+    const int b = min(max(src_imp[bs], 0), B - 1);
+    const long src = ((long)b * H + j) * words, dst = row * words;
+    for (int w = lane; w < words; w += 64) xh_g[dst + w] = x[src + w];
+}
+
+hipError_t history_gather_groups_launch(const unsigned* x, unsigned* xh_g, int words, const int* src_imp, const int* b0, const int* row_off,
+                                        const int* hg, int G, int B, int H, int R, hipStream_t st) {
+    if (R <= 0 || B <= 0 || G <= 0 || H <= 0) return hipSuccess;
+    hipLaunchKernelGGL(history_gather_groups_kernel, dim3((unsigned)(((long)R + 3) / 4)), dim3(256), 0, st, x, xh_g, words, src_imp, b0, row_off, hg,
+                       G, B, H, R);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void history_tiles_kernel(const int* __restrict__ cand_imp, const int* __restrict__ cand_off,
                                                             const int* __restrict__ hist_off, const int* __restrict__ tile_pre, int B, int N,
                                                             int R, int Mt, int4* __restrict__ tile_tab) {

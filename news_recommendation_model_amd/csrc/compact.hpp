@@ -20,6 +20,11 @@ hipError_t compact_gather_launch(const CompactGatherParams& p, hipStream_t st);
 hipError_t history_len_launch(const unsigned* x, int B, int H, int words, int* hist_len, hipStream_t st);
 // xh_c[hist_off[b] + j, :] = x[b, j, :] for j < hist_off[b + 1] - hist_off[b] (bitwise); k_max = the longest kept history (it sizes the grid)
 hipError_t history_gather_launch(const unsigned* x, unsigned* xh_c, int words, const int* hist_off, int B, int H, int R, int k_max, hipStream_t st);
+// Grouped history arena of the compacted training step (section 5e): group g holds the impressions b0[g] .. b0[g + 1] - 1 of the sorted batch, each
+// trimmed to hg[g] rows, from arena row row_off[g]; sorted impression b is impression src_imp[b] of x.  One launch for all G groups.
+constexpr int HISTORY_GROUPS_MAX = 64;
+hipError_t history_gather_groups_launch(const unsigned* x, unsigned* xh_g, int words, const int* src_imp, const int* b0, const int* row_off,
+                                        const int* hg, int G, int B, int H, int R, hipStream_t st);
 // Per-tile table of the history-ragged attention: the score rows of compact candidate c (impression b = cand_imp[c], K_b kept history rows)
 // are nt_b = ceil(K_b / 16) whole 16-row tiles, tile_pre[b] + (c - cand_off[b]) nt_b + jt; entry = {c, first row of the tile in h_c / u,
 // valid rows of the tile, b}.  One thread per candidate writes its nt_b entries.

@@ -29,14 +29,20 @@ namespace nrm {
 // HRAG (history compaction): impression b keeps K_b = hist_off[b + 1] - hist_off[b] rows of X (hist_off[b] ..), its
 // candidates' scores are nt_b = ceil(K_b / 16) whole tiles each from tile tile_pre[b] of W (row stride 16 nt_b), and where
 // hist_mult[b] > 0 the LAST kept row stands for hist_mult[b] equal rows: its score is weighted where it is read (W itself stays unweighted).
-template <bool JSPLIT, bool RAGGED = false, bool HRAG = false>
+// WLAST (training on length groups): every impression of the launch was trimmed to the same J (or I) rows and its last
+// row stands for `wlast` equal rows.  wlast_row = 0: the weight is on the REDUCTION index J - 1, applied where W is read (the forward pool:
+// W = s stays unweighted in memory; with JSPLIT the wave whose range holds row J - 1 is the only one that reads a non-zero there).
+// wlast_row = 1: the weight is on OUTPUT row I - 1 and scales only the product formed here, before `accumulate` adds what is already there
+// (the pool's history gradient onto the attention's).  wlast = 1 multiplies by 1.0f: bitwise the unweighted kernel.
+template <bool JSPLIT, bool RAGGED = false, bool HRAG = false, bool WLAST = false>
 __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__ W, long wsb, long wsi, long wsj,
                                                        const float* __restrict__ X, long xsb, int ldx,
                                                        float* __restrict__ out, long osb, int ldo,
                                                        int B, int I, int J, int D, int accumulate,
                                                        const int* __restrict__ cand_off, int N,
                                                        const int* __restrict__ hist_off = nullptr, const int* __restrict__ hist_mult = nullptr,
-                                                       const int* __restrict__ tile_pre = nullptr, int R = 0, int Mt = 0) {
+                                                       const int* __restrict__ tile_pre = nullptr, int R = 0, int Mt = 0,
+                                                       float wlast_arg = 1.f, int wlast_row = 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) f32x4 part[JSPLIT ? 3 * 16 * 64 : 1];
     const int lane = threadIdx.x & 63;
@@ -58,7 +64,8 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
         if (!HRAG) W += (long)c0 * wsi;
         out += (long)c0 * ldo;
     }
-    float wlast = 1.f;                                                  // HRAG: weight of the last kept row (the representative padded row)
+    float wlast = 1.f;                                                  // HRAG / WLAST: weight of the last kept row (the representative padded row)
+    if (WLAST) wlast = wlast_arg;
     if (HRAG) {
         const int r0 = min(max(hist_off[b], 0), R);
         J = min(max(hist_off[b + 1], r0), R) - r0;                       // K_b
@@ -92,7 +99,7 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
         for (int it = 0; it < 4; ++it) {
             const int i = i0 + 16 * it + r16;
             a[it] = (it < nit && i < I && j < j_hi) ? Wb[(long)i * wsi + (long)j * wsj] : 0.f;
-            if (HRAG && j == J - 1) a[it] *= wlast;
+            if ((HRAG || WLAST) && j == J - 1 && !(WLAST && wlast_row)) a[it] *= wlast;
         }
     };
     f32x4 x_cur, x_nxt;
@@ -137,6 +144,7 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
                 if (it < nit && i < I) {
                     float* o = out + b * osb + (long)i * ldo + d0 + 4 * r16;
                     f32x4 v = f32x4{acc[it][0][e], acc[it][1][e], acc[it][2][e], acc[it][3][e]};
+                    if (WLAST && wlast_row && i == I - 1) v *= wlast;
                     if (accumulate) v += *reinterpret_cast<const f32x4*>(o);
                     *reinterpret_cast<f32x4*>(o) = v;
                 }
@@ -151,10 +159,13 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
 // columns {16c + 4q + e}: any split of the reduction index over the MFMAs is fine as long as both operands use the same)
 // and keeps up to four 16-row history tiles of accumulators; rows / columns past the edge read as 0 through the buffer
 // descriptors.  The chunk after the current one is requested before the current MFMAs.
+// WLAST (training on length groups): history row H - 1 stands for `wlast` equal rows, so its score gradient is
+// wlast * g . h[H - 1] (one product at the store; wlast = 1 is bitwise the plain kernel).
+template <bool WLAST = false>
 __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ g, long gsb, int ldg,
                                                      const float* __restrict__ h, long hsb, int ldh,
                                                      float* __restrict__ ds, int B, int T, int H, int D,
-                                                     float* __restrict__ zero_out, int zero_n) {
+                                                     float* __restrict__ zero_out, int zero_n, float wlast = 1.f) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // optional: clear a small accumulator of the kernels that follow (dw2 | db2 of the attention backward) -- saves their fill
     if (blockIdx.x == 0)
@@ -212,23 +223,30 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ g
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int t = t0 + 4 * q + e;
-                if (t < T && hc < H) ds[((long)b * T + t) * H + hc] = acc[j][e];
+                if (t < T && hc < H) ds[((long)b * T + t) * H + hc] = (WLAST && hc == H - 1) ? wlast * acc[j][e] : acc[j][e];
             }
         }
     }
 #endif
 }
 
+// The (impression, slab, row group) tasks of a launch and which form it takes -- ONE rule for the dense, the weighted, and the two ragged
+// launchers.  Few tasks (one wave each would leave most SIMDs empty) and a reduction long enough to cut in four: one workgroup per task.
+// Measured (graph replay, same box): reference default sizes, 256 tasks, J = 200: 27.8 -> 14.8 us per launch; C2, 2048 tasks,
+// J = 32: 18.6 -> 22.4 us -- so only up to 1024 tasks.  NRM_POOL_JSPLIT=0|1 forces either form.  false: more tasks than a grid holds.
+static bool bmm_rows_plan(int B, int I, int J, int D, long& tasks, bool& jsplit) {
+    tasks = (long)B * ((D + 63) / 64) * ((I + 63) / 64);
+    const char* env = getenv("NRM_POOL_JSPLIT");
+    jsplit = env ? env[0] == '1' : (tasks <= 1024 && J >= 32);
+    return (tasks + 3) / 4 <= 0x7fffffffL;
+}
+
 hipError_t bmm_rows_launch(const float* W, long wsb, long wsi, long wsj, const float* X, long xsb, int ldx,
                            float* out, long osb, int ldo, int B, int I, int J, int D, int accumulate, hipStream_t st) {
     if (B <= 0 || I <= 0) return hipSuccess;
-    const long tasks = (long)B * ((D + 63) / 64) * ((I + 63) / 64);
-    if ((tasks + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
-    // few tasks (one wave each would leave most SIMDs empty) and a reduction long enough to cut in four: one workgroup per task.
-    // Measured (graph replay, same box): reference default sizes, 256 tasks, J = 200: 27.8 -> 14.8 us per launch; C2, 2048 tasks,
-    // J = 32: 18.6 -> 22.4 us -- so only up to 1024 tasks.  NRM_POOL_JSPLIT=0|1 forces either form.
-    const char* env = getenv("NRM_POOL_JSPLIT");
-    const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && J >= 32);
+    long tasks;
+    bool jsplit;
+    if (!bmm_rows_plan(B, I, J, D, tasks, jsplit)) return hipErrorInvalidValue;
     if (jsplit)
         hipLaunchKernelGGL(bmm_rows_kernel<true>, dim3((unsigned)tasks), dim3(256), 0, st,
                            W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate, nullptr, 0);
@@ -238,13 +256,31 @@ hipError_t bmm_rows_launch(const float* W, long wsb, long wsi, long wsj, const f
     return hipGetLastError();
 }
 
+// The dense launch with a weighted last row (same task count, same JSPLIT rule as bmm_rows_launch).
+hipError_t bmm_rows_wlast_launch(const float* W, long wsb, long wsi, long wsj, const float* X, long xsb, int ldx,
+                                 float* out, long osb, int ldo, int B, int I, int J, int D, int accumulate, float wlast, int wlast_row,
+                                 hipStream_t st) {
+    if (B <= 0 || I <= 0) return hipSuccess;
+    long tasks;
+    bool jsplit;
+    if (!bmm_rows_plan(B, I, J, D, tasks, jsplit)) return hipErrorInvalidValue;
+    if (jsplit)
+        hipLaunchKernelGGL((bmm_rows_kernel<true, false, false, true>), dim3((unsigned)tasks), dim3(256), 0, st,
+                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
+                           wlast, wlast_row);
+    else
+        hipLaunchKernelGGL((bmm_rows_kernel<false, false, false, true>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st,
+                           W, wsb, wsi, wsj, X, xsb, ldx, out, osb, ldo, B, I, J, D, accumulate, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
+                           wlast, wlast_row);
+    return hipGetLastError();
+}
+
 hipError_t bmm_rows_ragged_launch(const float* S, int lds, const float* X, long xsb, int ldx, float* out, int ldo, const int* cand_off,
                                   int B, int N, int max_count, int J, int D, hipStream_t st) {
     if (B <= 0 || N <= 0 || max_count <= 0) return hipSuccess;
-    const long tasks = (long)B * ((D + 63) / 64) * ((max_count + 63) / 64);
-    if ((tasks + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
-    const char* env = getenv("NRM_POOL_JSPLIT");
-    const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && J >= 32);          // the dense rule
+    long tasks;
+    bool jsplit;
+    if (!bmm_rows_plan(B, max_count, J, D, tasks, jsplit)) return hipErrorInvalidValue;
     if (jsplit)
         hipLaunchKernelGGL((bmm_rows_kernel<true, true>), dim3((unsigned)tasks), dim3(256), 0, st,
                            S, 0L, (long)lds, 1L, X, xsb, ldx, out, 0L, ldo, B, max_count, J, D, 0, cand_off, N);
@@ -258,10 +294,9 @@ hipError_t bmm_rows_hragged_launch(const float* S, const float* X, int ldx, floa
                                    const int* hist_mult, const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D,
                                    hipStream_t st) {
     if (B <= 0 || N <= 0 || max_count <= 0) return hipSuccess;
-    const long tasks = (long)B * ((D + 63) / 64) * ((max_count + 63) / 64);
-    if ((tasks + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
-    const char* env = getenv("NRM_POOL_JSPLIT");
-    const bool jsplit = env ? env[0] == '1' : (tasks <= 1024 && k_max >= 32);      // the dense rule, on the longest kept history
+    long tasks;
+    bool jsplit;
+    if (!bmm_rows_plan(B, max_count, k_max, D, tasks, jsplit)) return hipErrorInvalidValue;      // (on the longest kept history)
     if (jsplit)
         hipLaunchKernelGGL((bmm_rows_kernel<true, true, true>), dim3((unsigned)tasks), dim3(256), 0, st,
                            S, 0L, 0L, 1L, X, 0L, ldx, out, 0L, ldo, B, max_count, k_max, D, 0, cand_off, N, hist_off, hist_mult, tile_pre, R, Mt);
@@ -275,7 +310,16 @@ hipError_t rowdot_launch(const float* g, long gsb, int ldg, const float* h, long
                          int B, int T, int H, int D, float* zero_out, int zero_n, hipStream_t st) {
     if (B <= 0) return zero_n > 0 ? hipMemsetAsync(zero_out, 0, (size_t)zero_n * sizeof(float), st) : hipSuccess;
     const long tiles = (long)B * ((T + 15) / 16);
-    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, g, gsb, ldg, h, hsb, ldh, ds, B, T, H, D, zero_out, zero_n);
+    hipLaunchKernelGGL(rowdot_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, g, gsb, ldg, h, hsb, ldh, ds, B, T, H, D, zero_out, zero_n, 1.f);
+    return hipGetLastError();
+}
+
+hipError_t rowdot_wlast_launch(const float* g, long gsb, int ldg, const float* h, long hsb, int ldh, float* ds,
+                               int B, int T, int H, int D, float* zero_out, int zero_n, float wlast, hipStream_t st) {
+    if (B <= 0) return zero_n > 0 ? hipMemsetAsync(zero_out, 0, (size_t)zero_n * sizeof(float), st) : hipSuccess;
+    const long tiles = (long)B * ((T + 15) / 16);
+    hipLaunchKernelGGL(rowdot_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, g, gsb, ldg, h, hsb, ldh, ds, B, T, H, D, zero_out, zero_n,
+                       wlast);
     return hipGetLastError();
 }
 

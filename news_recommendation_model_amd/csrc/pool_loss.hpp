@@ -15,6 +15,13 @@ hipError_t bmm_rows_hragged_launch(const float* S, const float* X, int ldx, floa
                                    hipStream_t st);
 hipError_t rowdot_launch(const float* g, long gsb, int ldg, const float* h, long hsb, int ldh, float* ds,
                          int B, int T, int H, int D, float* zero_out, int zero_n, hipStream_t st);
+// the two dense launches with a weighted last row (training on length groups); wlast_row: 0 = reduction index J - 1
+// (where W is read), 1 = output row I - 1 (the product formed here only)
+hipError_t bmm_rows_wlast_launch(const float* W, long wsb, long wsi, long wsj, const float* X, long xsb, int ldx,
+                                 float* out, long osb, int ldo, int B, int I, int J, int D, int accumulate, float wlast, int wlast_row,
+                                 hipStream_t st);
+hipError_t rowdot_wlast_launch(const float* g, long gsb, int ldg, const float* h, long hsb, int ldh, float* ds,
+                               int B, int T, int H, int D, float* zero_out, int zero_n, float wlast, hipStream_t st);
 hipError_t loss_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,
                        long n_delta, float alpha, int B, int T, float* loss_sum, float* dout, int dout_stride, float* ddelta, int* err,
                        hipStream_t st);

@@ -184,12 +184,66 @@ class UserInvariantInterestModel(nn.Module):
             pooled_ti = self._attend_and_pool(self.text_img_attention, ti_t, ti_h)
         return pooled_lab, pooled_ti, lab_t, ti_t
 
+    def forward_parts_grouped(self, x_history_arena, x_target, plan):
+        """forward_parts on length groups: ``x_history_arena`` [R, cols] are the plan's kept history rows
+        (``ops.history_gather_groups``), ``x_target`` [B, T, cols] is in the plan's SORTED order; -> the same four blocks in sorted order.
+        The front end and w1 are row-wise and run on the R rows unchanged; only the two attention + pool nodes know about the groups."""
+        ops._require_gpu(x_history_arena, x_target)
+        B, T = x_target.shape[0], x_target.shape[1]
+        if x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or B != plan.B or B * T == 0 or plan.R == 0:
+            raise RuntimeError(f"forward_grouped: plan for {plan.B} impressions / {plan.R} kept history rows, got a history arena "
+                               f"{tuple(x_history_arena.shape)} and targets {tuple(x_target.shape)}")
+        if not self.grouped_attention_applies():
+            raise RuntimeError("forward_grouped: an attention of this model does not take the fused attention + pool node (feature width "
+                               "not a multiple of 4, a non-GELU MLP or a substituted module): run the dense forward")
+        sen = self.sentiment_embedding[0]
+        lab_h, ti_h, lab_t, ti_t = ops.frontend_pair_fwd(
+            x_history_arena, x_target.reshape(B * T, x_target.shape[2]), int(self._dims.n_subcat), int(self._dims.pca_vector),
+            self.category_embedding[0].weight, sen.weight, sen.bias, self.type_embedding[0].weight, self.year_embedding[0].weight,
+            self.month_embedding[0].weight, self.day_embedding[0].weight, self.hour_embedding[0].weight)
+        ti_h, ti_t = ti_h.detach(), ti_t.detach().unflatten(0, (B, T))
+        lab_t = lab_t.reshape(B, T, -1) if lab_t.is_contiguous() else lab_t.unflatten(0, (B, T))
+        lab_h = ops.linear(lab_h, self.w1.weight, self.w1.bias)                                       # [R, D_l]
+
+        def attend(att, t, h):
+            m = att.mlp
+            return ops.attend_and_pool_grouped(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, plan, mma=att.mma)
+
+        # two streams as in forward_parts; the choice goes by the z elements the groups really have
+        side = ops.branch_stream(lab_t) if self.uses_two_streams(plan.R * T * lab_h.shape[1]) else None
+        if side is not None:
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            ti_t.record_stream(side)
+            ti_h.record_stream(side)
+            with torch.cuda.stream(side):
+                pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
+            pooled_lab = attend(self.label_attention, lab_t, lab_h)
+            main.wait_stream(side)
+            pooled_ti.record_stream(main)
+        else:
+            pooled_lab = attend(self.label_attention, lab_t, lab_h)
+            pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
+        return pooled_lab, pooled_ti, lab_t, ti_t
+
+    def grouped_attention_applies(self):
+        """Whether both attentions take the fused attention + pool node on feature widths the grouped node accepts (multiples of 4)."""
+        for att, width in ((self.label_attention, self._dims.label_dim), (self.text_img_attention, self._dims.pca_vector)):
+            if not self._fused_node_applies(att) or width % 4 or att._forward_hooks or att._forward_pre_hooks:
+                return False
+        return True
+
+    @staticmethod
+    def _fused_node_applies(attention):
+        mlp = getattr(attention, "mlp", None)
+        return (type(attention) is PointwiseAttentionExpanded and isinstance(mlp, MLP) and isinstance(mlp.activation, nn.GELU)
+                and mlp.activation.approximate == "none")
+
     @staticmethod
     def _attend_and_pool(attention, t, h):
         # un-normalised weighted pool: sum_h score * history  (no softmax, padding not masked)
-        mlp = getattr(attention, "mlp", None)
-        if type(attention) is PointwiseAttentionExpanded and isinstance(mlp, MLP) and isinstance(mlp.activation, nn.GELU) \
-                and mlp.activation.approximate == "none" and t.dim() == 3:
+        if UserInvariantInterestModel._fused_node_applies(attention) and t.dim() == 3:
+            mlp = attention.mlp
             # scores + pool as one autograd node (the backward chains their kernels: ops._attend_pool_bwd_impl)
             return ops.attend_and_pool(t, h, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias, mma=attention.mma)
         s = attention(t, h)                                            # [B,T,H,1]
@@ -280,6 +334,10 @@ class UserModel(nn.Module):
             eu_H, ec = inv(x_history, x_target)
             eu_L = self.instant_interest_model(x_global)
             e = ops.concat_last((eu_H, eu_L, ec))
+        return self._head(e)
+
+    def _head(self, e):
+        """BatchNorm gate -> MLP -> MLP on the concatenated rows e [B, T, width] -> logits [B, T] (:32-34)."""
         B, T, N = e.shape
         rows = e.reshape(B * T, N)
         g = self.gate
@@ -289,6 +347,26 @@ class UserModel(nn.Module):
         else:
             gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)     # the gate multiplies the RAW concat
         return self._tail(gated).reshape(B, T)
+
+    def compact_history_applies(self):
+        """Whether ``forward_grouped`` can stand in for ``forward``: the plain invariant-interest model (not hooked, not substituted)
+        whose two attentions take the fused node, and no forward hook on the model itself."""
+        inv = self.invariant_interest_model
+        if self._forward_hooks or self._forward_pre_hooks:          # forward_grouped is not forward(): hooks on the model would not run
+            return False
+        return (type(inv) is UserInvariantInterestModel and not (inv._forward_hooks or inv._forward_pre_hooks)
+                and inv.grouped_attention_applies())
+
+    def forward_grouped(self, x_history_arena, x_target_sorted, x_global_sorted, plan):
+        """forward() on histories cut into length groups, training or eval mode.  ``plan`` is a
+        ``compact.HistoryGroupPlan``; ``x_history_arena`` [R, cols] its kept history rows (``ops.history_gather_groups``), ``x_target_sorted``
+        / ``x_global_sorted`` the batch's rows in the plan's sorted order (``index_select`` with ``plan.perm``).  -> logits [B, T] in SORTED
+        order (the caller un-permutes them with ``plan.inverse``).  Every candidate row is there, so training-mode BatchNorm sees the
+        B * T rows the dense forward sees, in another order.  Agrees with forward() on the dense batch to fp32 rounding (one product by
+        w_g in place of w_g equal addends in the pool)."""
+        pooled_lab, pooled_ti, lab_t, ti_t = self.invariant_interest_model.forward_parts_grouped(x_history_arena, x_target_sorted, plan)
+        eu_L = self.instant_interest_model(x_global_sorted)
+        return self._head(ops.concat_last((pooled_lab, pooled_ti, eu_L, lab_t, ti_t)))
 
     def forward_compact(self, x_history, xt_compact, xg_compact, plan):
         """Inference on ragged candidate lists (compact scoring path): ``xt_compact`` [N, cols] and

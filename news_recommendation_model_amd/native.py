@@ -75,6 +75,9 @@ SIGNATURES = {
     "nrm_history_tiles": (_c_i, [_c_fp] * 4 + [_c_i] * 4 + [_c_fp, _c_fp]),
     "nrm_pwattn_fwd_hragged": (_c_i, [_c_fp] * 13 + [_c_i] * 8 + [_c_fp]),
     "nrm_pool_bmm_hragged": (_c_i, [_c_fp] * 7 + [_c_i] * 7 + [_c_fp]),
+    "nrm_history_gather_groups": (_c_i, [_c_fp, _c_i, _c_i] + [_c_fp] * 4 + [_c_i] * 4 + [_c_fp, _c_fp]),
+    "nrm_pool_bmm_wlast": (_c_i, [_c_fp, _c_l, _c_l, _c_l, _c_fp, _c_i, _c_fp] + [_c_i] * 5 + [ctypes.c_float, _c_i, _c_fp]),
+    "nrm_pool_rowdot_wlast": (_c_i, [_c_fp, _c_i, _c_fp, _c_fp] + [_c_i] * 4 + [_c_fp, _c_i, ctypes.c_float, _c_fp]),
     "nrm_ensemble_rank_ragged": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i] + [_c_fp] * 5),     # the first two: HOST arrays
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,

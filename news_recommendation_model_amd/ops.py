@@ -620,12 +620,30 @@ def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=Non
     native.call("nrm_pwattn_bwd_dz", native.ptr(z), native.ptr(ds), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
                 native.ptr(du), native.ptr(dv), B, T, H, D, DZ_HL4 if rw else DZ_F32, st)
     dz = z
+    dw1, db1, dh2, dt2 = _attn_bwd_once(du.reshape(B * H, D), dv.reshape(B * T, D), h.reshape(B * H, D), t.reshape(B * T, D), w1, w1_arg, own,
+                                        mma, need_dt, need_dh)
+    dh = dh2.reshape(B, H, D) if need_dh else dh2
+    dt = dt2.reshape(B, T, D) if need_dt else dt2
+    nsplit = lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma)
+    wsp = torch.empty(nsplit, D, D, dtype=torch.float32, device=dev)
+    _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh, st)
+    if need_dt or need_dh:
+        _note_chain_end()                              # the last contraction of a backward that produced a row gradient
+    _slab_reduce(wsp, nsplit, D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
+    return dt, dh, dw1, db1, acc
+
+
+def _attn_bwd_once(du2, dv2, h2, t2, w1, w1_arg, own, mma, need_dt, need_dh):
+    """The part of an attention backward that runs ONCE over all rows, whatever (B, T, H) blocks the rows came from: the two
+    weight-gradient GEMMs du^T h and dv^T t with their slab reductions, and the two side-projection dX GEMMs.  du2 / h2: [rows_h, D],
+    dv2 / t2: [rows_t, D].  -> (dw1 [D, 4D] whose dW_p block the caller's slab reduction fills, db1, dh [rows_h, D], dt [rows_t, D]);
+    an unwanted row gradient is an empty tensor."""
+    D = w1.shape[0]
+    dev = w1.device
     w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
-    du2, dv2 = du.reshape(B * H, D), dv.reshape(B * T, D)
     # fc1 gradient [D, 4D] = [da_h | da_t | da_t - da_h | dW_p]: every block is written in place by a slab reduction
     dw1 = torch.empty(D, 4 * D, dtype=torch.float32, device=dev)                    # zeroed by the first GEMM launch below
     db1 = torch.empty(D, dtype=torch.float32, device=dev)
-    h2, t2 = h.reshape(B * H, D), t.reshape(B * T, D)
     ctx = _wgrad_stream(du2, h2, dv2, t2, dw1)          # (big batches under train_step: on the weight-gradient stream)
     with ctx as side:
         ws, cs, ns, ldws = _gemm_tn_slabs(du2, h2, True, zero_out=dw1, mma=mma)  # du^T h, db1 = column sums of du
@@ -638,12 +656,17 @@ def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=Non
                 x.record_stream(ctx.main)
     # du (W_h - W_d), dv (W_t + W_d): the transposed orientation of the same two combinations   (D % 4 == 0: contiguous results)
     none = torch.empty(0, dtype=torch.float32, device=dev)
-    dh = (_gemm_nt(du2, w_h, 1, 4 * D, D, D, None, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)[0].reshape(B, H, D)
-          if need_dh else none)
-    dt = (_gemm_nt(dv2, w_t, 1, 4 * D, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)[0].reshape(B, T, D)
-          if need_dt else none)
-    nsplit = lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma)
-    wsp = torch.empty(nsplit, D, D, dtype=torch.float32, device=dev)
+    dh = _gemm_nt(du2, w_h, 1, 4 * D, D, D, None, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)[0] if need_dh else none
+    dt = _gemm_nt(dv2, w_t, 1, 4 * D, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)[0] if need_dt else none
+    return dw1, db1, dh, dt
+
+
+def _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh, st, z_elems=None):
+    """The contraction launches of ONE (B, T, H) block: dt / dh (which already hold the side projections' share) get the bilinear term's,
+    ``wsp`` [nsplit, D, D] the block's dW_p slabs.  The form is chosen for the block's own shape.  ``z_elems``: what the wait for the other
+    attention's chain is sized by (None: this block's B*T*H*D)."""
+    B, T, D = t.shape
+    H = h.shape[1]
     wp = w1[:, 3 * D:]                                   # view, row stride 4D
     # 'rw' (bf16 arithmetics with a resident-W backward) and 'dp' (fp32, both row gradients wanted, big enough or forced): dt and dh
     # from ONE contraction, then the (b,t)-grouped pass without its dt epilogue for the dW_p slabs; 'e': the two grouped E-form passes
@@ -653,7 +676,7 @@ def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=Non
     def contract(passes, tag, dz_format=DZ_F32, out=False):     # out: the launch writes row gradients (those that are wanted)
         _count_flops("contraction", 2.0 * B * T * H * D * D)
         if not rows:
-            _wait_for_foreign_chain(B * T * H * D)     # serves no row gradient: behind the other attention's chain (see _chain)
+            _wait_for_foreign_chain(B * T * H * D if z_elems is None else z_elems)     # serves no row gradient: behind the other attention's chain (see _chain)
         native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(wp), 4 * D,
                     native.ptr(dt) if out and need_dt else None, native.ptr(dh) if out and need_dh else None,
                     native.ptr(wsp), B, T, H, D, passes, mma, dz_format, st, tag=tag)
@@ -669,10 +692,6 @@ def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=Non
         if rows:
             _bwd_dtdh(lib, form, dz, t, h, w1, dt, dh, mma, st)
         contract(4, "pwattn_bwd_e_bt" if rw else "pwattn_bwd_e_dw", DZ_HL4 if rw else DZ_F32)
-    if rows:
-        _note_chain_end()                              # the last contraction of a backward that produced a row gradient
-    _slab_reduce(wsp, nsplit, D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
-    return dt, dh, dw1, db1, acc
 
 
 def _pwattn_bwd_fake(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True):
@@ -1666,6 +1685,207 @@ def attend_and_pool(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias,
     return attend_pool_fwd(*args, save_z, resolve_mma(mma))[0]
 
 
+# ------------------------------------------------------------------------------------------------ attention + pool on length groups
+# (DESIGN.md section 5e)  The batch is sorted by history length and cut into groups (compact.plan_history_groups); group g -- sorted
+# impressions b0[g] .. b0[g + 1] - 1, each trimmed to hg[g] <= H history rows, from row row_off[g] of the history arena h [R, D] -- runs through
+# the DENSE forward and backward kernels with H = hg[g].  Only the pool knows that where hg[g] < H the group's last row is a padded row that
+# stands for w_g = H - hg[g] + 1 equal rows.  The group table travels as host integers: the launches are per group.
+def _group_layout(b0, hg, T):
+    """[(b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo)] per group and the totals (R, S, Z): r = rows of the arena, s = floats of the score buffer
+    (a group's [B_g, T, H_g] block starts on a 256-byte boundary), z = score elements before the group (its z block starts at z_lo * D)."""
+    b0, hg = [int(x) for x in b0], [int(x) for x in hg]
+    if len(b0) != len(hg) + 1 or b0[0] != 0 or any(b0[g + 1] <= b0[g] for g in range(len(hg))) or any(x < 1 for x in hg):
+        raise RuntimeError(f"grouped attention: group bounds {b0} / heights {hg} are not a partition into non-empty groups")
+    out, r, sf, zr = [], 0, 0, 0
+    for g, H_g in enumerate(hg):
+        n = b0[g + 1] - b0[g]
+        out.append((b0[g], b0[g + 1], H_g, r, r + n * H_g, sf, zr))
+        r, sf, zr = r + n * H_g, (sf + n * T * H_g + 63) // 64 * 64, zr + n * T * H_g
+    return out, r, sf, zr
+
+
+def _attend_pool_grouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
+    """t [B, T, D] (sorted order), h [R, D] (the arena) -> (pooled [B, T, D], s [S], z [Z * D] or empty).  ONE u GEMM over the R rows and ONE
+    v GEMM over the B*T rows; per group the dense forward on pointer-offset views and the pool with the weighted last row.  s and z hold
+    sum_g B_g T H_g (D) elements instead of B T H (D); s is UNWEIGHTED (the weight is applied where the pool reads it)."""
+    _require_gpu(t, h, w1, b1, w2, b2)
+    if save_z:
+        _chain["end"] = None
+    B, T, D = t.shape
+    groups, R, S, Z = _group_layout(group_b0, group_h, T)
+    if (h.dim() != 2 or h.shape[0] != R or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or groups[-1][1] != B
+            or max(group_h) > H):
+        raise RuntimeError(f"grouped attention: target {tuple(t.shape)}, history arena {tuple(h.shape)}, fc1 {tuple(w1.shape)}, groups of "
+                           f"{list(group_b0)} x {list(group_h)} rows (H = {H}) do not agree (feature width must be a multiple of 4)")
+    w1_arg = w1
+    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
+    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
+    own = w1 if w1 is w1_arg else None
+    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
+    u, _ = _gemm_nt(h, w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)                       # [R, D]
+    v, _ = _gemm_nt(t.reshape(B * T, D), w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)   # [B*T, D]
+    v = v.reshape(B, T, D)
+    st = native.stream_ptr()
+    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
+    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
+    s = torch.empty(S, dtype=torch.float32, device=t.device)
+    z = torch.empty(Z * D if save_z else 0, dtype=torch.float32, device=t.device)
+    pooled = torch.empty(B, T, D, dtype=torch.float32, device=t.device)
+    for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
+        n = b_hi - b_lo
+        _count_flops("contraction", 2.0 * n * T * H_g * D * D)
+        native.call("nrm_pwattn_fwd", native.ptr(t[b_lo:b_hi]), native.ptr(h[r_lo:r_hi]), native.ptr(u[r_lo:r_hi]), native.ptr(v[b_lo:b_hi]),
+                    native.ptr(packed), native.ptr(w2v), native.ptr(b2), native.ptr(z[z_lo * D:]) if save_z else None, native.ptr(s[s_lo:]),
+                    n, T, H_g, D, mma, st)
+        native.call("nrm_pool_bmm_wlast", native.ptr(s[s_lo:]), T * H_g, H_g, 1, native.ptr(h[r_lo:r_hi]), D, native.ptr(pooled[b_lo:b_hi]),
+                    n, T, H_g, D, 0, float(H - H_g + 1), 0, st)
+    return pooled, s, z
+
+
+def _attend_pool_grouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
+    _, _, S, Z = _group_layout(group_b0, group_h, t.shape[1])
+    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
+    return f(*t.shape), f(S), f(Z * t.shape[2] if save_z else 0)
+
+
+attend_pool_grouped_fwd = _op("attend_pool_grouped_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
+                              "int[] group_b0, int[] group_h, int H, bool save_z, int mma) -> (Tensor, Tensor, Tensor)",
+                              _attend_pool_grouped_fwd_impl, _attend_pool_grouped_fwd_fake)
+
+
+def _attend_pool_grouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
+    """Backward of the grouped node from the pooled gradient g [B, T, D].  Per group: weighted rowdot (the first one clears dw2 | db2) and
+    the dz pass; ONCE over all rows: the two weight-gradient GEMMs and the two side-projection dX GEMMs (_attn_bwd_once); per group again:
+    the contraction launches in the form _attn_bwd_core would choose for the group's own shape, and the pool's history gradient, whose
+    last row alone carries the weight, added onto the attention's.  The dW_p slabs of all groups lie in one buffer and reduce into the ONE dw1."""
+    _require_gpu(g, t, h, w1, w2, s, z)
+    B, T, D = t.shape
+    groups, R, S, Z = _group_layout(group_b0, group_h, T)
+    st = native.stream_ptr()
+    w1_arg = w1
+    t, h, w1, s = _f32c(t), _f32c(h), _f32c(w1), _f32c(s)
+    own = w1 if w1 is w1_arg else None
+    w2v = _f32c(w2).reshape(-1)
+    dev = t.device
+    g, ldg = _pooled_grad_rows(g, B, T, D)
+    lib = native.load()
+    rw = mma != MMA_F32 and bool(lib.nrm_pwattn_bwd_rw_supported(D, mma))
+    acc = torch.empty(D + 4, dtype=torch.float32, device=dev)
+    dw2, db2 = acc[:D], acc[D:D + 1]
+    du = torch.empty(R, D, dtype=torch.float32, device=dev)
+    dv = torch.empty(B, T, D, dtype=torch.float32, device=dev)
+    for i, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in enumerate(groups):
+        n = b_hi - b_lo
+        ds = torch.empty(n, T, H_g, dtype=torch.float32, device=dev)
+        native.call("nrm_pool_rowdot_wlast", native.ptr(g[b_lo:b_hi]), ldg, native.ptr(h[r_lo:r_hi]), native.ptr(ds), n, T, H_g, D,
+                    native.ptr(acc) if i == 0 else None, D + 4 if i == 0 else 0, float(H - H_g + 1), st)
+        native.call("nrm_pwattn_bwd_dz", native.ptr(z[z_lo * D:]), native.ptr(ds), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
+                    native.ptr(du[r_lo:r_hi]), native.ptr(dv[b_lo:b_hi]), n, T, H_g, D, DZ_HL4 if rw else DZ_F32, st)
+    dw1, db1, dh, dt2 = _attn_bwd_once(du, dv.reshape(B * T, D), h, t.reshape(B * T, D), w1, w1_arg, own, mma, need_dt, need_dh)
+    dt = dt2.reshape(B, T, D) if need_dt else dt2
+    nsplits = [lib.nrm_pwattn_bwd_nsplit(b_hi - b_lo, T, H_g, D, mma) for b_lo, b_hi, H_g, *_ in groups]
+    wsp = torch.empty(sum(nsplits), D, D, dtype=torch.float32, device=dev)
+    none = torch.empty(0, dtype=torch.float32, device=dev)
+    k = 0
+    for ns, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in zip(nsplits, groups):
+        n = b_hi - b_lo
+        _attn_bwd_contract(lib, z[z_lo * D:], t[b_lo:b_hi], h[r_lo:r_hi].view(n, H_g, D), w1, dt[b_lo:b_hi] if need_dt else none,
+                           dh[r_lo:r_hi].view(n, H_g, D) if need_dh else none, wsp[k:k + ns], mma, rw, need_dt, need_dh, st, z_elems=Z * D)
+        k += ns
+    if need_dt or need_dh:
+        _note_chain_end()                              # after the last group
+    if need_dh:
+        for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
+            native.call("nrm_pool_bmm_wlast", native.ptr(s[s_lo:]), T * H_g, 1, H_g, native.ptr(g[b_lo:b_hi]), ldg, native.ptr(dh[r_lo:r_hi]),
+                        b_hi - b_lo, H_g, T, D, 1, float(H - H_g + 1), 1, st)
+    _slab_reduce(wsp, sum(nsplits), D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)
+    return dt, dh, dw1, db1, acc
+
+
+def _attend_pool_grouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
+    B, T, D = t.shape
+    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
+    return (f(B, T, D) if need_dt else f(0)), (f(h.shape[0], D) if need_dh else f(0)), f(D, 4 * D), f(D), f(D + 4)
+
+
+attend_pool_grouped_bwd = _op("attend_pool_grouped_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
+                              "int[] group_b0, int[] group_h, int H, int mma, bool need_dt, bool need_dh) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+                              _attend_pool_grouped_bwd_impl, _attend_pool_grouped_bwd_fake)
+
+
+def _attend_pool_grouped_setup(ctx, inputs, output):
+    t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma = inputs
+    pooled, s, z = output
+    ctx.set_materialize_grads(False)
+    ctx.save_z, ctx.mma, ctx.consumed = save_z, mma, False
+    ctx.groups = (list(group_b0), list(group_h), H)
+    ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
+    ctx.mark_non_differentiable(s, z)
+    if save_z:
+        ctx.save_for_backward(t, h, w1, w2, s, z)
+
+
+def _attend_pool_grouped_backward(ctx, g, _ds, _dz):
+    if g is None:
+        return (None,) * 11
+    if not ctx.save_z:
+        raise RuntimeError("grouped attention: the forward ran with save_z=False (no-grad / inference call); there is nothing to "
+                           "differentiate through")
+    t, h, w1, w2, s, z = ctx.saved_tensors
+    if _retain_attention_graph:
+        z = z.detach().clone()
+    elif ctx.consumed:
+        raise RuntimeError("grouped attention: a second backward through the same graph finds the saved pre-activation overwritten by the "
+                           "first one's dz (the grouped node does not recompute it); call ops.set_retain_attention_graph(True) before "
+                           "the forward's backward passes to work on a copy instead")
+    else:
+        ctx.consumed, z = True, z.detach()
+    need = ctx.needs_input_grad
+    dt, dh, dw1, db1, dw2b2 = attend_pool_grouped_bwd(g, t, h, w1, w2, s, z, *ctx.groups, ctx.mma, bool(need[0]), bool(need[1]))
+    D = t.shape[2]
+    return ((dt if need[0] else None), (dh if need[1] else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
+            dw2b2[D:D + 1].reshape(ctx.b2_shape), None, None, None, None, None)
+
+
+torch.library.register_autograd("nrm::attend_pool_grouped_fwd", _attend_pool_grouped_backward, setup_context=_attend_pool_grouped_setup, lib=_LIB)
+
+
+def attend_and_pool_grouped(target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
+    """[B, T, D] candidates in the plan's SORTED order x the grouped history arena [R, D] (``compact.plan_history_groups`` +
+    ``history_gather_groups``, then whatever row-wise layers lead to the attention) -> pooled [B, T, D] in sorted order: what
+    ``attend_and_pool`` gives the dense [B, H, D] history whose rows j >= H_g - 1 of every impression of a trimmed group are all equal.
+    One autograd node, every arithmetic; the feature width must be a multiple of 4 (no padded fallback: the caller runs dense then)."""
+    args = (target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
+    _require_gpu(*args)
+    if target.dim() != 3 or target.shape[-1] % 4 or target.shape[0] != plan.B or plan.B == 0:
+        raise RuntimeError(f"attend_and_pool_grouped: target {tuple(target.shape)} for a plan of {plan.B} impressions (needs [B, T, D], D a "
+                           "multiple of 4, B > 0)")
+    save_z = torch.is_grad_enabled() and any(a.requires_grad for a in args)
+    return attend_pool_grouped_fwd(*args, [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], int(plan.H), save_z, resolve_mma(mma))[0]
+
+
+def _history_gather_groups_impl(x_history, perm, bounds, row_off, H_g, R):
+    """x_history [B, H, cols] (float64 or float32, kept) -> the grouped arena [R, cols] (bitwise): row (b - bounds[g]) * H_g[g] + j of group g
+    is row j of impression perm[b].  One launch for all groups; the sorted x_history is never formed."""
+    _require_gpu(x_history, perm, bounds, row_off, H_g)
+    x = (x_history if x_history.dtype in (torch.float32, torch.float64) else x_history.to(torch.float32)).contiguous()
+    G = H_g.shape[0]
+    if x.dim() != 3 or tuple(perm.shape) != (x.shape[0],) or tuple(bounds.shape) != (G + 1,) or tuple(row_off.shape) != (G + 1,):
+        raise RuntimeError(f"history_gather_groups: x_history {tuple(x.shape)}, perm {tuple(perm.shape)}, bounds {tuple(bounds.shape)}, row_off "
+                           f"{tuple(row_off.shape)}, H_g {tuple(H_g.shape)} do not agree")
+    B, H, cols = x.shape
+    out = torch.empty(int(R), cols, dtype=x.dtype, device=x.device)
+    if R and cols:
+        native.call("nrm_history_gather_groups", native.ptr(x), cols, 1 if x.dtype == torch.float64 else 0, native.ptr(_tab(perm)),
+                    native.ptr(_tab(bounds)), native.ptr(_tab(row_off)), native.ptr(_tab(H_g)), G, B, H, int(R), native.ptr(out), native.stream_ptr())
+    return out
+
+
+history_gather_groups = _op("history_gather_groups", "(Tensor x_history, Tensor perm, Tensor bounds, Tensor row_off, Tensor H_g, int R) -> Tensor",
+                            _history_gather_groups_impl,
+                            lambda x, perm, bounds, row_off, H_g, R: x.new_empty((R, x.shape[2]), dtype=x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32))
+
+
 # ------------------------------------------------------------------------------------------------ loss
 _index_error_flag = {}
 
@@ -2384,4 +2604,5 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "weighted_pool_fwd", "weighted_pool_bwd", "attend_pool_fwd", "attend_pool_bwd", "softmax_bce_loss", "frontend_fwd", "frontend_bwd",
        "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
        "history_len", "history_gather", "history_tiles", "attend_pool_hragged_fwd",
+       "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
        "adam_step")

@@ -290,19 +290,94 @@ def _index_watch(device):
     return w
 
 
+_len_streams = {}
+
+
+def history_len_host(x_history, after=None):
+    """``L_b`` of a device-resident ``x_history`` [B, H, cols] as a HOST int32 tensor (pinned), measured by ``ops.history_len`` on a side
+    stream that waits for ``after`` (an event: the batch's own upload) or, without one, for what the current stream holds now.  Returns
+    (host tensor, event): the lengths are valid once the event has completed -- the compute stream is never drained for them."""
+    from . import ops
+    dev = x_history.device
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    side = _len_streams.get(key)
+    if side is None:
+        side = _len_streams[key] = torch.cuda.Stream(device=dev)
+    if after is not None:
+        side.wait_event(after)
+    else:
+        side.wait_stream(torch.cuda.current_stream(dev))
+    host = torch.empty(x_history.shape[0], dtype=torch.int32).pin_memory()
+    with torch.cuda.stream(side):
+        lens = ops.history_len(x_history)
+        host.copy_(lens, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(side)
+    x_history.record_stream(side)
+    return host, done
+
+
+def attach_history_len(batch, after=None):
+    """-> ``batch`` with ``"history_len_host"`` = (host lengths, event, address and version counter of ``x_history``), measured now by
+    ``history_len_host``.  The entry is PRIVATE to this module: the lengths describe exactly the tensor contents they were measured on, and
+    ``train_step`` uses them only while ``x_history`` still has that address and version counter -- a batch refreshed in place (a
+    ``copy_`` into the same buffers) is measured again instead of being planned with stale lengths.  A length anybody else supplies is not
+    trusted."""
+    xh = batch["x_history"]
+    host, done = history_len_host(xh, after)
+    return dict(batch, history_len_host=(host, done, xh.data_ptr(), xh._version))
+
+
+def _compact_forward(model, batch, alpha, max_groups):
+    """forward + loss of train_step(compact_history=True) -> (loss, out in the caller's order), or None where the step runs dense: a
+    model whose attentions do not take the fused node, or a plan with nothing worth dropping."""
+    from . import compact, ops
+    if not (hasattr(model, "compact_history_applies") and model.compact_history_applies()):
+        return None
+    xh = batch["x_history"]
+    pre = batch.get("history_len_host")                      # attach_history_len's entry: valid for the tensor it was measured on only
+    if pre is None or (pre[2], pre[3]) != (xh.data_ptr(), xh._version):
+        pre = history_len_host(xh)                           # nobody measured THESE rows: measure now, at the cost of a synchronise
+    host, done = pre[0], pre[1]
+    done.synchronize()                                       # the side stream's copy only -- not the compute stream
+    plan = compact.plan_history_groups(host.numpy(), xh.shape[1], max_groups=max_groups)
+    if plan.dense or plan.B == 0:
+        return None
+    tabs = plan.upload(xh.device)
+    arena = ops.history_gather_groups(xh, tabs["perm"], tabs["bounds"], tabs["row_off"], tabs["H_g"], plan.R)
+    perm = tabs["perm"]
+    out_sorted = model.forward_grouped(arena, batch["x_target"].index_select(0, perm), batch["x_global"].index_select(0, perm), plan)
+    loss = model.loss(batch["user_id"].index_select(0, perm), out_sorted, batch["label"].index_select(0, perm), alpha)
+    return loss, out_sorted.detach().index_select(0, tabs["inverse"])
+
+
 def train_step(model, optimizer, batch, reducer: FlatGradReducer | None = None, alpha=0.95, defer_reductions=True,
-               strict_ids=False):
+               strict_ids=False, compact_history=False, max_groups=None):
     """One step of train.py:69-75 on device-resident tensors; returns (loss, out) detached.  An out-of-range id of an EARLIER
     step raises IndexError here, before this step's work is enqueued (IndexErrorWatch: asynchronous, the offending step has
     been applied by then).  ``strict_ids=True``: the ids of THIS batch are checked first (validate_batch_ids, one host
-    synchronisation) and the IndexError is raised before anything is enqueued -- the reference's behaviour."""
+    synchronisation) and the IndexError is raised before anything is enqueued -- the reference's behaviour.
+    ``compact_history=True``: the trailing all-zero history rows the ETL pads with are not computed -- the batch is
+    sorted by history length, cut into at most ``max_groups`` groups (None: ``compact.MAX_GROUPS``) and every group runs through the dense
+    kernels at its own height; loss, BatchNorm statistics and every gradient are the dense step's to fp32 rounding, ``out`` is in the
+    caller's order.  The plan needs the lengths on the HOST: what ``BatchPrefetcher(..., history_len=True)`` measured while staging the
+    batch (``attach_history_len``; used only while ``x_history`` is the very tensor contents it was measured on) costs nothing here;
+    without it the lengths are measured now and this call waits for everything enqueued before it (one synchronise per step).  A plan with nothing worth dropping, and a model whose attentions do not take the fused node, run the dense
+    step unchanged.  Not inside a stream capture."""
+    if compact_history and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("train_step(compact_history=True) plans the length groups on the host and cannot run inside a stream capture "
+                           "(GraphedTrainStep captures the dense step)")
     watch = _index_watch(batch["x_history"].device) if not torch.cuda.is_current_stream_capturing() else None
     if watch is not None:
         watch.before_step()
     if strict_ids:
         validate_batch_ids(model, batch)
-    out = model(batch["x_history"], batch["x_target"], batch["x_global"])
-    loss = model.loss(batch["user_id"], out, batch["label"], alpha)
+    compacted = _compact_forward(model, batch, alpha, max_groups) if compact_history else None
+    if compacted is not None:
+        loss, out = compacted
+    else:
+        out = model(batch["x_history"], batch["x_target"], batch["x_global"])
+        loss = model.loss(batch["user_id"], out, batch["label"], alpha)
     if isinstance(optimizer, FlatAdam):
         from . import ops
         ops.begin_step()                              # (stream ordering of the two attentions' backward contractions: ops._chain)
@@ -335,9 +410,12 @@ class GraphedTrainStep:
     (reference default dimensions: 3.1 -> 2.7 ms).  New data is copied INTO the tensors
     of ``batch`` before ``replay()``; ``loss`` / ``out`` are overwritten in place by every replay."""
 
-    def __init__(self, model, optimizer, batch, alpha=0.95, warmup=3, pool=None):
+    def __init__(self, model, optimizer, batch, alpha=0.95, warmup=3, pool=None, compact_history=False):
         """``pool``: the memory pool of another GraphedTrainStep (``other.graph.pool()``) -- several captured steps, e.g. one per
         resident input batch, then share their intermediates' memory (they must be replayed one at a time, in any order)."""
+        if compact_history:
+            raise RuntimeError("GraphedTrainStep(compact_history=True): the length groups are planned on the host for every batch; a "
+                               "captured step replays one fixed sequence of launches.  Capture the dense step")
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedTrainStep needs trainer.FlatAdam (its step counter lives on the device)")
         from . import native
@@ -400,7 +478,11 @@ class BatchPrefetcher:
     preallocated device buffer sets on a copy stream while the current step runs; the compute stream waits on the
     copy's event, and a buffer is only overwritten after the step that read it has been enqueued (its event)."""
 
-    def __init__(self, batches, device="cuda", pin=True):
+    def __init__(self, batches, device="cuda", pin=True, history_len=False):
+        """``history_len=True``: the history lengths of every staged batch are measured on a side stream that waits only for the batch's
+        own upload, copied to the host and attached as ``batch["history_len_host"]`` (what ``train_step(compact_history=True)`` plans
+        from, without draining the compute stream)."""
+        self.history_len = history_len
         self.device = torch.device(device)
         self.batches = iter(batches)
         self.pin = pin
@@ -428,16 +510,20 @@ class BatchPrefetcher:
             self._pending = None
             return
         i = self.slot
-        if self.bufs[i] is None or any(self.bufs[i][k].shape != v.shape or self.bufs[i][k].dtype != v.dtype
+        if self.bufs[i] is None or any(k not in self.bufs[i] or self.bufs[i][k].shape != v.shape or self.bufs[i][k].dtype != v.dtype
                                        for k, v in host.items()):
             self.bufs[i] = {k: torch.empty(v.shape, dtype=v.dtype, device=self.device) for k, v in host.items()}
             self.free[i] = None
         with torch.cuda.stream(self.copy_stream):
             if self.free[i] is not None:
                 self.copy_stream.wait_event(self.free[i])
+            if self.bufs[i].get("history_len_host") is not None:        # the length kernel of the batch this buffer held reads x_history
+                self.copy_stream.wait_event(self.bufs[i]["history_len_host"][1])
             for k, v in host.items():
                 self.bufs[i][k].copy_(v, non_blocking=True)
             self.ready[i].record(self.copy_stream)
+        if self.history_len:
+            self.bufs[i] = attach_history_len(self.bufs[i], after=self.ready[i])
         self._pending = (i, host)                                   # keep the pinned tensors alive until consumed
 
     def __iter__(self):
@@ -460,12 +546,14 @@ class BatchPrefetcher:
         self.free[slot] = ev
 
 
-def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path=None, on_batch=None):
+def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path=None, on_batch=None, compact_history=False,
+                 max_groups=None):
     """The epoch loop of reference train.py:52-100 around ``train_step``: every epoch re-reads ``param_groups[0]['lr']``
     (:57), steps through ``make_loader()`` (an iterable of host batches, dict fields as in ``synth.make_batch``), keeps
     the running loss and per-impression AUC averages the reference prints (:77-88, AUC on the device instead of a
     host sklearn loop), and saves the state_dict without ``delta`` (:95-97).  The reference never steps its scheduler
-    (:99-100), so none is taken here.  Batches are staged through ``BatchPrefetcher``.
+    (:99-100), so none is taken here.  Batches are staged through ``BatchPrefetcher``.  ``compact_history`` / ``max_groups``: as in
+    ``train_step``; the prefetcher then measures the history lengths while it stages a batch.
     Returns one dict per epoch: lr, loss_avg, auc_avg, impressions."""
     from . import evaluation, ops
     history = []
@@ -476,9 +564,9 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
         auc_sum = torch.zeros((), dtype=torch.float64, device=device)
         bad_rows = torch.zeros((), dtype=torch.int64, device=device)
         seen = 0
-        pf = BatchPrefetcher(make_loader(), device)
+        pf = BatchPrefetcher(make_loader(), device, history_len=compact_history)
         for i, (batch, slot) in enumerate(pf):
-            loss, out = train_step(model, optimizer, batch)
+            loss, out = train_step(model, optimizer, batch, compact_history=compact_history, max_groups=max_groups)
             auc, _hit = evaluation.row_auc_top1(out, batch["label"])
             pf.release(slot)
             n = out.shape[0]

@@ -7,9 +7,10 @@ a template parameter or a kernel argument must leave the existing instantiations
     python scripts/asm_diff_instantiations.py OLD NEW [FILE ...]          default: pwattn_fwd pwattn_fwd_rw pool_loss
 
 A kernel of OLD is matched to the kernel of NEW with the same demangled name, or with one more trailing ``false`` template argument
-(a new flag that defaults to off); the argument list may have grown.  Symbol names, label numbers and comments are normalised away;
+(a new flag that defaults to off; a kernel that was no template becomes ``name<false>``); the argument list may have grown.  Symbol names, label numbers and comments are normalised away;
 every remaining difference is printed.  Differences in ``.amdhsa_kernarg_size`` and in the offset of an ``s_load`` from the kernel
-argument segment (a hidden argument behind a larger block) are counted apart from real ones.  Exit status 1 on a real difference."""
+argument segment (a hidden argument behind a larger block) are counted apart from real ones, and so is the section directive of a kernel
+that became a template instantiation (``.text`` -> its own comdat ``.section .text.<symbol>``: where the code lies, not what it is).  Exit status 1 on a real difference."""
 import difflib
 import os
 import re
@@ -45,6 +46,7 @@ for f in (sys.argv[3:] or ['pwattn_fwd', 'pwattn_fwd_rw', 'pool_loss']):
         cand = [d]
         m = re.match(r'^(void nrm::\w+<)([^>]*)(>\()', d)
         if m: cand.append(m.group(1) + m.group(2) + ', false' + m.group(3))
+        elif '<' not in d.split('(')[0]: cand.append('void ' + d.split('(')[0] + '<false>(')
         # prefix match on "name<args>(" since the argument list may have grown
         hit = None
         for c in cand:
@@ -56,12 +58,12 @@ for f in (sys.argv[3:] or ['pwattn_fwd', 'pwattn_fwd_rw', 'pool_loss']):
         if b[k] == n[hit]: same += 1
         else:
             dl = [l for l in difflib.unified_diff(b[k], n[hit], lineterm='', n=0) if not l.startswith(('---', '+++', '@@'))]
-            if all(re.search(r'\.amdhsa_kernarg_size|s_load_dword\w* \S+ s\[\d+:\d+\], 0x', l) for l in dl):
+            if all(re.search(r'\.amdhsa_kernarg_size|s_load_dword\w* \S+ s\[\d+:\d+\], 0x|^[-+]\s*\.text$|^[-+]\s*\.section\s+\.text\.SYM,', l) for l in dl):
                 moved += 1
                 continue
             diff += 1
             print(f, 'DIFF', d[:100], len(dl), 'lines'); print('\n'.join(dl[:12]))
     real += diff
-    print(f'{f}: {len(bo)} existing instantiations: {same} identical, {moved} differ only in the kernel-argument size / a hidden-argument offset, '
+    print(f'{f}: {len(bo)} existing instantiations: {same} identical, {moved} differ only in the kernel-argument size / a hidden-argument offset / the section directive of a kernel that became a template, '
           f'{diff} really different; the new tree has {len(no)} kernels')
 sys.exit(1 if real else 0)
