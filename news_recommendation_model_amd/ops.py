@@ -472,35 +472,107 @@ def _op(name, schema, impl, fake):
 
 
 # ------------------------------------------------------------------------------------------------ pointwise attention
-def _pwattn_fwd_impl(t, h, w1, b1, w2, b2, save_z, mma):
-    """s[b,t,h] = fc2(GELU(fc1(cat[h, t, t-h, t*h]))) with fc1 = [W_h|W_t|W_d|W_p] re-associated as
-    z = h(W_h-W_d)^T + b1 + t(W_t+W_d)^T + sum_d W_p[:,d] t_d h_d  (SURVEY.md §8 a7)."""
-    _require_gpu(t, h, w1, b1, w2, b2)
+def _attn_operands(t, h, w1, b1, w2, b2, mma):
+    """What every attention forward starts with: the fp32-contiguous operands (target and history as 2-D rows [rows_t, D] and
+    [rows_h, D]), the side projections u = h (W_h - W_d)^T + b1 [rows_h, D] and v = t (W_t + W_d)^T [rows_t, D] -- the difference /
+    sum is formed by the pack kernel -- and the packed W_p image.  -> (t, h, u, v, packed, w2v, b2)"""
+    D = w1.shape[0]
+    w1_arg = w1
+    t, h, w1, b1 = _f32c(t).reshape(-1, D), _f32c(h).reshape(-1, D), _f32c(w1), _f32c(b1)
+    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
+    own = w1 if w1 is w1_arg else None
+    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
+    u, _ = _gemm_nt(h, w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)
+    v, _ = _gemm_nt(t, w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)
+    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
+    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), native.stream_ptr())
+    return t, h, u, v, packed, w2v, b2
+
+
+# The training nodes work on a list of (B_g, T, H_g) blocks (DESIGN.md section 5e): block g -- impressions b0[g] .. b0[g + 1] - 1, each with
+# hg[g] history rows, from row r_lo of the history rows h [R, D] -- runs through the DENSE forward and backward kernels with H = hg[g].  Only
+# the pool knows that where hg[g] < H the block's last row stands for w_g = H - hg[g] + 1 equal rows.  The dense nodes are the one-block case.
+def _group_layout(b0, hg, T):
+    """[(b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo)] per group and the totals (R, S, Z): r = rows of the arena, s = floats of the score buffer
+    (a group's [B_g, T, H_g] block starts on a 256-byte boundary), z = score elements before the group (its z block starts at z_lo * D)."""
+    b0, hg = [int(x) for x in b0], [int(x) for x in hg]
+    if len(b0) != len(hg) + 1 or b0[0] != 0 or any(b0[g + 1] <= b0[g] for g in range(len(hg))) or any(x < 1 for x in hg):
+        raise RuntimeError(f"grouped attention: group bounds {b0} / heights {hg} are not a partition into non-empty groups")
+    out, r, sf, zr = [], 0, 0, 0
+    for g, H_g in enumerate(hg):
+        n = b0[g + 1] - b0[g]
+        out.append((b0[g], b0[g + 1], H_g, r, r + n * H_g, sf, zr))
+        r, sf, zr = r + n * H_g, (sf + n * T * H_g + 63) // 64 * 64, zr + n * T * H_g
+    return out, r, sf, zr
+
+
+def _one_group(B, T, H):
+    """_group_layout of a dense [B, T, H] node: one group of full height at offset 0 of every buffer, its score buffer exactly B*T*H floats."""
+    return [(0, B, H, 0, B * H, 0, 0)], B * H, B * T * H, B * T * H
+
+
+def _pool_bmm(s, s_b, s_i, s_j, x, ldx, out, B, I, J, D, accumulate, wlast, wlast_row, st):
+    """out[b, i, :] (+)= sum_j s[b*s_b + i*s_i + j*s_j] x[b, j, :], the last row (of j: wlast_row 0, of i: 1) weighted by ``wlast``: the
+    plain kernel where the weight is 1 (bit for bit what the weighted one gives there)."""
+    args = (native.ptr(s), s_b, s_i, s_j, native.ptr(x), ldx, native.ptr(out), B, I, J, D, accumulate)
+    if wlast == 1:
+        native.call("nrm_pool_bmm", *args, st)
+    else:
+        native.call("nrm_pool_bmm_wlast", *args, float(wlast), wlast_row, st)
+
+
+def _pool_rowdot(g, ldg, h, ds, B, T, H, D, acc, wlast, st):
+    """ds[b, t, j] = g[b, t, :] . h[b, j, :], the last row weighted by ``wlast``; ``acc`` (or None) is zeroed by the same launch."""
+    args = (native.ptr(g), ldg, native.ptr(h), native.ptr(ds), B, T, H, D, native.ptr(acc) if acc is not None else None,
+            acc.numel() if acc is not None else 0)
+    if wlast == 1:
+        native.call("nrm_pool_rowdot", *args, st)
+    else:
+        native.call("nrm_pool_rowdot_wlast", *args, float(wlast), st)
+
+
+def _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, pool):
+    """The training forward of every attention node.  t [B, T, D], h: the R history rows of ``groups`` (with S, Z: _group_layout's or
+    _one_group's).  ONE u GEMM over the R rows and ONE v GEMM over the B*T rows; per block the dense forward
+    s[b,t,h] = fc2(GELU(fc1(cat[h, t, t-h, t*h]))), fc1 = [W_h|W_t|W_d|W_p] re-associated as
+    z = h(W_h-W_d)^T + b1 + t(W_t+W_d)^T + sum_d W_p[:,d] t_d h_d  (SURVEY.md §8 a7), on pointer-offset views and, with ``pool``,
+    pooled[b,t,:] = sum_h s[b,t,h] h[b,h,:] with the weighted last row.  -> (pooled [B, T, D] or None, s [S], z [Z * D] or empty);
+    s is UNWEIGHTED (the weight is applied where the pool reads it)."""
     if save_z:
         _chain["end"] = None               # a training forward: whatever an earlier backward left there is stale (see _chain below)
+    B, T, D = t.shape
+    t, h, u, v, packed, w2v, b2 = _attn_operands(t, h, w1, b1, w2, b2, mma)
+    dev, st = t.device, native.stream_ptr()
+    s = torch.empty(S, dtype=torch.float32, device=dev)
+    z = torch.empty(Z * D if save_z else 0, dtype=torch.float32, device=dev)
+    pooled = torch.empty(B, T, D, dtype=torch.float32, device=dev) if pool else None
+    for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
+        n = b_hi - b_lo
+        _count_flops("contraction", 2.0 * n * T * H_g * D * D)
+        native.call("nrm_pwattn_fwd", native.ptr(t[b_lo * T:]), native.ptr(h[r_lo:]), native.ptr(u[r_lo:]), native.ptr(v[b_lo * T:]),
+                    native.ptr(packed), native.ptr(w2v), native.ptr(b2), native.ptr(z[z_lo * D:]) if save_z else None, native.ptr(s[s_lo:]),
+                    n, T, H_g, D, mma, st)
+        if pool:
+            _pool_bmm(s[s_lo:], T * H_g, H_g, 1, h[r_lo:], D, pooled[b_lo:], n, T, H_g, D, 0, H - H_g + 1, 0, st)
+    return pooled, s, z
+
+
+def _attn_dense_fwd(t, h, w1, b1, w2, b2, save_z, mma, pool):
+    """The dense nodes: _attn_blocks_fwd on the one full-height group, s as [B, T, H] and z as [B, T, H, D]."""
+    _require_gpu(t, h, w1, b1, w2, b2)
     B, T, D = t.shape
     H = h.shape[1]
     if h.shape[0] != B or h.shape[2] != D or tuple(w1.shape) != (D, 4 * D) or D % 4:
         raise RuntimeError(f"pointwise attention: target {tuple(t.shape)}, history {tuple(h.shape)}, "
                            f"fc1 {tuple(w1.shape)} do not agree (feature width must be a multiple of 4)")
-    w1_arg = w1
-    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
-    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
-    # side projections u = h (W_h - W_d)^T + b1, v = t (W_t + W_d)^T: the difference / sum is formed by the pack kernel
-    own = w1 if w1 is w1_arg else None
-    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
-    u, _ = _gemm_nt(h.reshape(B * H, D), w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)     # [B*H, D]
-    v, _ = _gemm_nt(t.reshape(B * T, D), w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)   # [B*T, D]
-    st = native.stream_ptr()
-    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
-    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
-    s = torch.empty(B, T, H, dtype=torch.float32, device=t.device)
-    z = torch.empty((B, T, H, D) if save_z else (0,), dtype=torch.float32, device=t.device)
-    _count_flops("contraction", 2.0 * B * T * H * D * D)
-    native.call("nrm_pwattn_fwd", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v),
-                native.ptr(packed), native.ptr(w2v), native.ptr(b2),
-                native.ptr(z) if save_z else None, native.ptr(s), B, T, H, D, mma, st)
-    return s, z
+    groups, _, S, Z = _one_group(B, T, H)
+    pooled, s, z = _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, pool)
+    return pooled, s.view(B, T, H), (z.view(B, T, H, D) if save_z else z)
+
+
+def _pwattn_fwd_impl(t, h, w1, b1, w2, b2, save_z, mma):
+    """s [B,T,H], and the pre-activation z [B,T,H,D] when ``save_z``: the scores-only node."""
+    return _attn_dense_fwd(t, h, w1, b1, w2, b2, save_z, mma, False)[1:]
 
 
 def _pwattn_fwd_fake(t, h, w1, b1, w2, b2, save_z, mma):
@@ -514,10 +586,20 @@ pwattn_fwd = _op("pwattn_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor f
                  "bool save_z, int mma) -> (Tensor, Tensor)", _pwattn_fwd_impl, _pwattn_fwd_fake)
 
 
+def _attn_dense_bwd(t, h, w1, w2, z, mma, need_dt, need_dh, **source):
+    """The dense nodes: _attn_blocks_bwd on the one full-height group, dh as [B, H, D]."""
+    B, T, D = t.shape
+    H = h.shape[1]
+    groups, _, _, Z = _one_group(B, T, H)
+    dt, dh, dw1, db1, acc = _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, **source)
+    return dt, (dh.view(B, H, D) if need_dh else dh), dw1, db1, acc
+
+
 def _pwattn_bwd_impl(ds, t, h, w1, w2, z, mma, need_dt, need_dh):
     """All gradients of one attention from ds [B,T,H] and the saved pre-activation z [B,T,H,D], which is overwritten
     in place by dz (schema: Tensor(a!))."""
-    return _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt, need_dh)
+    _require_gpu(ds, t, h, w1, w2, z)
+    return _attn_dense_bwd(t, h, w1, w2, z, mma, need_dt, need_dh, ds=ds)
 
 
 # Order of the two attentions' backward contractions when they run on two streams (round 5).  The label attention's chain
@@ -591,45 +673,67 @@ def _bwd_dtdh(lib, form, dz, t, h, w1, dt, dh, mma, st):
                 B, T, H, D, *tail, st, tag="pwattn_bwd_rw_dtdh" if form == "rw" else "pwattn_bwd_dp_dtdh")
 
 
-def _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt=True, need_dh=True, acc=None):
-    """``need_dt`` / ``need_dh``: whether the target / history rows want a gradient.  The text+image attention of the model reads
-    raw input columns (reference user_invariant_interest_model.py:63-64,78: no parameter upstream), so autograd asks for neither
-    -- as in the reference, where those products are never formed -- and the (b,h)-grouped contraction pass, the two
-    side-projection GEMMs and the dt epilogue are skipped: the weight gradients only need dz, du, dv and the dW_p pass.
-    Skipped gradients are returned as empty tensors.
-    ``acc``: [D + 4] floats (dw2 | db2 | pad) that an earlier launch on this stream has ALREADY zeroed (the pool's rowdot
-    kernel in the merged pool + attention backward); None: allocated and zeroed here."""
-    _require_gpu(ds, t, h, w1, w2, z)
+def _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, ds=None, pool=None):
+    """The backward of every attention node, over the blocks of ``groups`` (Z: their z elements / D): t [B, T, D], h the R history rows,
+    z the saved pre-activation [Z * D], overwritten in place by dz.  From ``ds`` (the scores-only node: the gradient of s, in s's layout; the
+    dw2 | db2 accumulators are zeroed here) or from ``pool`` = (g, ldg, s) (the fused nodes: the pooled gradient as _pooled_grad_rows gives
+    it and the saved scores; per block the pool's weighted rowdot makes ds, and the first one also clears the accumulators -- no fill).
+    Per block: [rowdot,] the dz pass (z -> dz, du = sum_t dz, dv = sum_h dz, dw2, db2 = sum ds).  ONCE over all rows: the two weight-gradient
+    GEMMs and the two side-projection dX GEMMs (_attn_bwd_once).  Per block again: the contraction launches, in the form chosen for the
+    block's own shape (_attn_bwd_contract); the dW_p slabs of all blocks lie in one buffer and reduce into the ONE dw1.  Last, with a pool and
+    a history gradient: the pool's, whose last row alone carries the weight, ADDED onto the attention's -- no [B,H,D] add by autograd.
+    ``need_dt`` / ``need_dh``: whether the target / history rows want a gradient.  The text+image attention of the model reads raw input
+    columns (reference user_invariant_interest_model.py:63-64,78: no parameter upstream), so autograd asks for neither -- as in the
+    reference, where those products are never formed -- and the (b,h)-grouped contraction pass, the two side-projection GEMMs and the dt
+    epilogue are skipped: the weight gradients only need dz, du, dv and the dW_p pass.  Skipped gradients are returned as empty tensors.
+    -> (dt [B, T, D], dh [R, D], dw1 [D, 4D], db1 [D], acc [D + 4] = dw2 | db2 | pad)"""
     B, T, D = t.shape
-    H = h.shape[1]
     st = native.stream_ptr()
     w1_arg = w1
-    t, h, w1, ds = _f32c(t), _f32c(h), _f32c(w1), _f32c(ds)
+    t, h, w1 = _f32c(t), _f32c(h).reshape(-1, D), _f32c(w1)
     own = w1 if w1 is w1_arg else None
     w2v = _f32c(w2).reshape(-1)
+    z = z.view(-1)
     dev = t.device
-    if acc is None:
-        acc = torch.zeros(D + 4, dtype=torch.float32, device=dev)
-    dw2, db2 = acc[:D], acc[D:D + 1]                   # the dz pass accumulates both (db2 = sum ds); returned as ONE tensor
-    # one pass over z: z -> dz in place, du = sum_t dz, dv = sum_h dz, dw2.  The bf16 arithmetics with a resident-W backward
-    # (D <= 256) get dz as bf16 hi/lo pairs (NRM_DZ_HL4): the contraction kernels then read MFMA-ready operands
     lib = native.load()
+    # the bf16 arithmetics with a resident-W backward (D <= 256) get dz as bf16 hi/lo pairs (NRM_DZ_HL4): the contraction kernels then
+    # read MFMA-ready operands
     rw = mma != MMA_F32 and bool(lib.nrm_pwattn_bwd_rw_supported(D, mma))
-    du = torch.empty(B, H, D, dtype=torch.float32, device=dev)
+    if pool is None:
+        ds = _f32c(ds).reshape(-1)
+        acc = torch.zeros(D + 4, dtype=torch.float32, device=dev)
+    else:
+        g, ldg, s = pool[0], pool[1], _f32c(pool[2]).reshape(-1)
+        acc = torch.empty(D + 4, dtype=torch.float32, device=dev)
+    dw2, db2 = acc[:D], acc[D:D + 1]                   # the dz pass accumulates both; returned as ONE tensor
+    du = torch.empty(h.shape[0], D, dtype=torch.float32, device=dev)
     dv = torch.empty(B, T, D, dtype=torch.float32, device=dev)
-    native.call("nrm_pwattn_bwd_dz", native.ptr(z), native.ptr(ds), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
-                native.ptr(du), native.ptr(dv), B, T, H, D, DZ_HL4 if rw else DZ_F32, st)
-    dz = z
-    dw1, db1, dh2, dt2 = _attn_bwd_once(du.reshape(B * H, D), dv.reshape(B * T, D), h.reshape(B * H, D), t.reshape(B * T, D), w1, w1_arg, own,
-                                        mma, need_dt, need_dh)
-    dh = dh2.reshape(B, H, D) if need_dh else dh2
-    dt = dt2.reshape(B, T, D) if need_dt else dt2
-    nsplit = lib.nrm_pwattn_bwd_nsplit(B, T, H, D, mma)
-    wsp = torch.empty(nsplit, D, D, dtype=torch.float32, device=dev)
-    _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh, st)
+    for i, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in enumerate(groups):
+        n = b_hi - b_lo
+        if pool is None:
+            ds_g = ds[s_lo:]
+        else:
+            ds_g = torch.empty(n, T, H_g, dtype=torch.float32, device=dev)
+            _pool_rowdot(g[b_lo:b_hi], ldg, h[r_lo:r_hi], ds_g, n, T, H_g, D, acc if i == 0 else None, H - H_g + 1, st)
+        native.call("nrm_pwattn_bwd_dz", native.ptr(z[z_lo * D:]), native.ptr(ds_g), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
+                    native.ptr(du[r_lo:r_hi]), native.ptr(dv[b_lo:b_hi]), n, T, H_g, D, DZ_HL4 if rw else DZ_F32, st)
+    dw1, db1, dh, dt = _attn_bwd_once(du, dv.reshape(B * T, D), h, t.reshape(B * T, D), w1, w1_arg, own, mma, need_dt, need_dh)
+    if need_dt:
+        dt = dt.reshape(B, T, D)
+    nsplits = [lib.nrm_pwattn_bwd_nsplit(b_hi - b_lo, T, H_g, D, mma) for b_lo, b_hi, H_g, *_ in groups]
+    wsp = torch.empty(sum(nsplits), D, D, dtype=torch.float32, device=dev)
+    k = 0
+    for ns, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in zip(nsplits, groups):
+        n = b_hi - b_lo
+        _attn_bwd_contract(lib, z[z_lo * D:], t[b_lo:b_hi], h[r_lo:r_hi].view(n, H_g, D), w1, dt[b_lo:b_hi] if need_dt else dt,
+                           dh[r_lo:r_hi].view(n, H_g, D) if need_dh else dh, wsp[k:k + ns], mma, rw, need_dt, need_dh, st, Z * D)
+        k += ns
     if need_dt or need_dh:
         _note_chain_end()                              # the last contraction of a backward that produced a row gradient
-    _slab_reduce(wsp, nsplit, D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
+    _slab_reduce(wsp, sum(nsplits), D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
+    if pool is not None and need_dh:
+        for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
+            _pool_bmm(s[s_lo:], T * H_g, 1, H_g, g[b_lo:b_hi], ldg, dh[r_lo:r_hi], b_hi - b_lo, H_g, T, D, 1, H - H_g + 1, 1, st)
     return dt, dh, dw1, db1, acc
 
 
@@ -661,10 +765,10 @@ def _attn_bwd_once(du2, dv2, h2, t2, w1, w1_arg, own, mma, need_dt, need_dh):
     return dw1, db1, dh, dt
 
 
-def _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh, st, z_elems=None):
+def _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh, st, z_elems):
     """The contraction launches of ONE (B, T, H) block: dt / dh (which already hold the side projections' share) get the bilinear term's,
-    ``wsp`` [nsplit, D, D] the block's dW_p slabs.  The form is chosen for the block's own shape.  ``z_elems``: what the wait for the other
-    attention's chain is sized by (None: this block's B*T*H*D)."""
+    ``wsp`` [nsplit, D, D] the block's dW_p slabs.  The form is chosen for the block's own shape.  ``z_elems``: the whole node's z elements,
+    what the wait for the other attention's chain is sized by."""
     B, T, D = t.shape
     H = h.shape[1]
     wp = w1[:, 3 * D:]                                   # view, row stride 4D
@@ -676,7 +780,7 @@ def _attn_bwd_contract(lib, dz, t, h, w1, dt, dh, wsp, mma, rw, need_dt, need_dh
     def contract(passes, tag, dz_format=DZ_F32, out=False):     # out: the launch writes row gradients (those that are wanted)
         _count_flops("contraction", 2.0 * B * T * H * D * D)
         if not rows:
-            _wait_for_foreign_chain(B * T * H * D if z_elems is None else z_elems)     # serves no row gradient: behind the other attention's chain (see _chain)
+            _wait_for_foreign_chain(z_elems)     # serves no row gradient: behind the other attention's chain (see _chain)
         native.call("nrm_pwattn_bwd_contract", native.ptr(dz), native.ptr(t), native.ptr(h), native.ptr(wp), 4 * D,
                     native.ptr(dt) if out and need_dt else None, native.ptr(dh) if out and need_dh else None,
                     native.ptr(wsp), B, T, H, D, passes, mma, dz_format, st, tag=tag)
@@ -720,46 +824,72 @@ def set_retain_attention_graph(on=True):
     return prev
 
 
-def _consume_z(ctx, z, t, h, w1, b1, w2):
+def _consume_z(ctx, z, t, h, w1, b1, w2, recompute):
     """The dz buffer of this backward: z itself on the first walk of the graph; a copy with set_retain_attention_graph; on a later
-    walk (the buffer now holds the first walk's dz) the pre-activation recomputed from the saved inputs."""
+    walk (the buffer now holds the first walk's dz) the pre-activation recomputed from the saved inputs -- by the dense nodes
+    (``recompute``); the grouped node raises."""
     if _retain_attention_graph:
         return z.detach().clone()
-    if ctx.consumed:
-        with torch.no_grad():
-            b2 = torch.zeros(1, dtype=torch.float32, device=t.device)            # (does not enter z)
-            return _pwattn_fwd_impl(t.detach(), h.detach(), w1.detach(), b1.detach(), w2.detach(), b2, True, ctx.mma)[1]
-    ctx.consumed = True
-    return z.detach()
+    if not ctx.consumed:
+        ctx.consumed = True
+        return z.detach()
+    if not recompute:
+        raise RuntimeError("grouped attention: a second backward through the same graph finds the saved pre-activation overwritten by the "
+                           "first one's dz (the grouped node does not recompute it); call ops.set_retain_attention_graph(True) before "
+                           "the forward's backward passes to work on a copy instead")
+    with torch.no_grad():
+        b2 = torch.zeros(1, dtype=torch.float32, device=t.device)            # (does not enter z)
+        return _pwattn_fwd_impl(t.detach(), h.detach(), w1.detach(), b1.detach(), w2.detach(), b2, True, ctx.mma)[1]
 
 
-def _pwattn_setup(ctx, inputs, output):
-    t, h, w1, b1, w2, b2, save_z, mma = inputs
-    s, z = output
-    ctx.set_materialize_grads(False)
-    ctx.save_z = save_z
-    ctx.mma = mma
-    ctx.consumed = False
-    ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
-    if save_z:
-        ctx.save_for_backward(t, h, w1, w2, z, b1)
+def _attention_node(fwd_name, bwd_op, n_extra, has_pool, recompute):
+    """Registers the autograd formula of the attention node ``nrm::fwd_name``, whose inputs are (t, h, fc1_weight, fc1_bias, fc2_weight,
+    fc2_bias, then ``n_extra`` non-tensor inputs that end in save_z, mma) and whose outputs are ([pooled,] s, z): with a pool, s and z are
+    saved and non-differentiable.  ``bwd_op`` takes (grad, t, h, fc1_weight, fc2_weight, [s,] z, the non-tensor inputs before save_z, mma,
+    need_dt, need_dh); ``recompute``: what a second backward does for its z (_consume_z)."""
+    what = "pointwise attention" if recompute else "grouped attention"
+
+    def setup(ctx, inputs, output):
+        t, h, w1, b1, w2, b2, *extra, save_z, mma = inputs
+        ctx.set_materialize_grads(False)
+        ctx.save_z, ctx.mma, ctx.consumed, ctx.extra = save_z, mma, False, tuple(extra)
+        ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
+        if has_pool:
+            ctx.mark_non_differentiable(*output[1:])
+        if save_z:
+            ctx.save_for_backward(t, h, w1, b1, w2, *output[1:])
+
+    def backward(ctx, grad, *_):
+        if grad is None:
+            return (None,) * (6 + n_extra)
+        if not ctx.save_z:
+            raise RuntimeError(f"{what}: the forward ran with save_z=False (no-grad / inference call); there is nothing to differentiate "
+                               "through")
+        t, h, w1, b1, w2, *s, z = ctx.saved_tensors
+        need_dt, need_dh = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        dt, dh, dw1, db1, dw2b2 = bwd_op(grad, t, h, w1, w2, *s, _consume_z(ctx, z, t, h, w1, b1, w2, recompute), *ctx.extra, ctx.mma,
+                                         need_dt, need_dh)
+        D = t.shape[2]
+        return ((dt if need_dt else None), (dh if need_dh else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
+                dw2b2[D:D + 1].reshape(ctx.b2_shape)) + (None,) * n_extra
+
+    torch.library.register_autograd("nrm::" + fwd_name, backward, setup_context=setup, lib=_LIB)
 
 
-def _pwattn_backward(ctx, ds, _dz):
-    if ds is None:
-        return None, None, None, None, None, None, None, None
-    if not ctx.save_z:
-        raise RuntimeError("pointwise attention: the forward ran with save_z=False (no-grad / inference call); there "
-                           "is nothing to differentiate through")
-    t, h, w1, w2, z, b1 = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    dt, dh, dw1, db1, dw2b2 = pwattn_bwd(ds, t, h, w1, w2, _consume_z(ctx, z, t, h, w1, b1, w2), ctx.mma, bool(need[0]), bool(need[1]))
-    D = t.shape[2]
-    return ((dt if need[0] else None), (dh if need[1] else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
-            dw2b2[D:D + 1].reshape(ctx.b2_shape), None, None)
+_attention_node("pwattn_fwd", pwattn_bwd, 2, False, True)
 
 
-torch.library.register_autograd("nrm::pwattn_fwd", _pwattn_backward, setup_context=_pwattn_setup, lib=_LIB)
+def _pad_feature_width(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias):
+    """The six attention inputs with a feature width D that is not a multiple of 4 zero-padded to the next one (differentiable ops);
+    unchanged otherwise."""
+    D = target.shape[-1]
+    if D % 4 == 0:
+        return target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias
+    P = _pad4(D) - D
+    pad = torch.nn.functional.pad
+    blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]     # [D4, D4] each
+    return (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
+            pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
 
 
 def pointwise_attention_scores(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias, mma=None):
@@ -769,7 +899,6 @@ def pointwise_attention_scores(target, history, fc1_weight, fc1_bias, fc2_weight
     The kernels need the feature width to be a multiple of 4 (float4 rows).  Any other D is zero-padded here with
     differentiable ops: padded features contribute exactly 0 to every term (their fc1 rows/columns and fc2 weights
     are 0, gelu(0) = 0), and autograd slices the gradients back."""
-    D = target.shape[-1]
     if target.shape[0] * target.shape[1] * history.shape[1] == 0:
         return _degenerate((target.shape[0], target.shape[1], history.shape[1]), target, history, fc1_weight, fc1_bias,
                            fc2_weight, fc2_bias)
@@ -777,13 +906,7 @@ def pointwise_attention_scores(target, history, fc1_weight, fc1_bias, fc2_weight
     _require_gpu(*args)
     # the [B,T,H,D] pre-activation is only kept when something will differentiate through the call
     save_z = torch.is_grad_enabled() and any(a.requires_grad for a in args)
-    if D % 4:
-        P = _pad4(D) - D
-        pad = torch.nn.functional.pad
-        blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]     # [D4, D4] each
-        args = (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
-                pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
-    return pwattn_fwd(*args, save_z, resolve_mma(mma))[0]
+    return pwattn_fwd(*_pad_feature_width(*args), save_z, resolve_mma(mma))[0]
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
@@ -1605,8 +1728,7 @@ def _attend_pool_fwd_impl(t, h, w1, b1, w2, b2, save_z, mma):
     """pooled[b,t,:] = sum_h s[b,t,h] h[b,h,:] with s = the pointwise attention scores: the two calls of
     user_invariant_interest_model.py:83-87 as ONE autograd node, so that its backward can chain the pool's and the
     attention's kernels (see _attend_pool_bwd_impl)."""
-    s, z = _pwattn_fwd_impl(t, h, w1, b1, w2, b2, save_z, mma)
-    return _pool_fwd_impl(s, h), s, z
+    return _attn_dense_fwd(t, h, w1, b1, w2, b2, save_z, mma, True)
 
 
 def _attend_pool_fwd_fake(t, h, w1, b1, w2, b2, save_z, mma):
@@ -1622,21 +1744,9 @@ def _attend_pool_bwd_impl(g, t, h, w1, w2, s, z, mma, need_dt, need_dh):
     """Backward of pool + attention from the pooled gradient g [B,T,D] (read in place when it is a column block of the head
     gradient).  Compared with the two separate nodes: the pool's rowdot launch also clears the attention's dw2 | db2
     accumulators, and the pool's history gradient is ADDED onto the attention's by the last launch -- no fill, no [B,T,D]
-    copy of g, no [B,H,D] add by autograd."""
+    copy of g, no [B,H,D] add by autograd (_attn_blocks_bwd)."""
     _require_gpu(g, t, h, w1, w2, s, z)
-    B, T, D = t.shape
-    H = h.shape[1]
-    s, h = _f32c(s), _f32c(h)
-    g, ldg = _pooled_grad_rows(g, B, T, D)
-    st = native.stream_ptr()
-    dev = h.device
-    acc = torch.empty(D + 4, dtype=torch.float32, device=dev)
-    ds = torch.empty(B, T, H, dtype=torch.float32, device=dev)
-    native.call("nrm_pool_rowdot", native.ptr(g), ldg, native.ptr(h), native.ptr(ds), B, T, H, D, native.ptr(acc), D + 4, st)
-    dt, dh, dw1, db1, dw2b2 = _attn_bwd_core(ds, t, h, w1, w2, z, mma, need_dt, need_dh, acc=acc)
-    if need_dh:
-        native.call("nrm_pool_bmm", native.ptr(s), T * H, 1, H, native.ptr(g), ldg, native.ptr(dh), B, H, T, D, 1, st)
-    return dt, dh, dw1, db1, dw2b2
+    return _attn_dense_bwd(t, h, w1, w2, z, mma, need_dt, need_dh, pool=(*_pooled_grad_rows(g, *t.shape), s))
 
 
 attend_pool_bwd = _op("attend_pool_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
@@ -1644,34 +1754,7 @@ attend_pool_bwd = _op("attend_pool_bwd", "(Tensor g, Tensor t, Tensor h, Tensor 
                       lambda g, t, h, w1, w2, s, z, mma, need_dt, need_dh: _pwattn_bwd_fake(s, t, h, w1, w2, z, mma, need_dt, need_dh))
 
 
-def _attend_pool_setup(ctx, inputs, output):
-    t, h, w1, b1, w2, b2, save_z, mma = inputs
-    pooled, s, z = output
-    ctx.set_materialize_grads(False)
-    ctx.save_z = save_z
-    ctx.mma = mma
-    ctx.consumed = False
-    ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
-    ctx.mark_non_differentiable(s, z)
-    if save_z:
-        ctx.save_for_backward(t, h, w1, w2, s, z, b1)
-
-
-def _attend_pool_backward(ctx, g, _ds, _dz):
-    if g is None:
-        return None, None, None, None, None, None, None, None
-    if not ctx.save_z:
-        raise RuntimeError("pointwise attention: the forward ran with save_z=False (no-grad / inference call); there "
-                           "is nothing to differentiate through")
-    t, h, w1, w2, s, z, b1 = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    dt, dh, dw1, db1, dw2b2 = attend_pool_bwd(g, t, h, w1, w2, s, _consume_z(ctx, z, t, h, w1, b1, w2), ctx.mma, bool(need[0]), bool(need[1]))
-    D = t.shape[2]
-    return ((dt if need[0] else None), (dh if need[1] else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
-            dw2b2[D:D + 1].reshape(ctx.b2_shape), None, None)
-
-
-torch.library.register_autograd("nrm::attend_pool_fwd", _attend_pool_backward, setup_context=_attend_pool_setup, lib=_LIB)
+_attention_node("attend_pool_fwd", attend_pool_bwd, 2, True, True)
 
 
 def attend_and_pool(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias, mma=None):
@@ -1689,57 +1772,19 @@ def attend_and_pool(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias,
 # (DESIGN.md section 5e)  The batch is sorted by history length and cut into groups (compact.plan_history_groups); group g -- sorted
 # impressions b0[g] .. b0[g + 1] - 1, each trimmed to hg[g] <= H history rows, from row row_off[g] of the history arena h [R, D] -- runs through
 # the DENSE forward and backward kernels with H = hg[g].  Only the pool knows that where hg[g] < H the group's last row is a padded row that
-# stands for w_g = H - hg[g] + 1 equal rows.  The group table travels as host integers: the launches are per group.
-def _group_layout(b0, hg, T):
-    """[(b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo)] per group and the totals (R, S, Z): r = rows of the arena, s = floats of the score buffer
-    (a group's [B_g, T, H_g] block starts on a 256-byte boundary), z = score elements before the group (its z block starts at z_lo * D)."""
-    b0, hg = [int(x) for x in b0], [int(x) for x in hg]
-    if len(b0) != len(hg) + 1 or b0[0] != 0 or any(b0[g + 1] <= b0[g] for g in range(len(hg))) or any(x < 1 for x in hg):
-        raise RuntimeError(f"grouped attention: group bounds {b0} / heights {hg} are not a partition into non-empty groups")
-    out, r, sf, zr = [], 0, 0, 0
-    for g, H_g in enumerate(hg):
-        n = b0[g + 1] - b0[g]
-        out.append((b0[g], b0[g + 1], H_g, r, r + n * H_g, sf, zr))
-        r, sf, zr = r + n * H_g, (sf + n * T * H_g + 63) // 64 * 64, zr + n * T * H_g
-    return out, r, sf, zr
-
-
+# stands for w_g = H - hg[g] + 1 equal rows.  The group table travels as host integers: the launches are per group (_attn_blocks_fwd,
+# _attn_blocks_bwd; the layout of the arena, s and z: _group_layout).
 def _attend_pool_grouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
-    """t [B, T, D] (sorted order), h [R, D] (the arena) -> (pooled [B, T, D], s [S], z [Z * D] or empty).  ONE u GEMM over the R rows and ONE
-    v GEMM over the B*T rows; per group the dense forward on pointer-offset views and the pool with the weighted last row.  s and z hold
+    """t [B, T, D] (sorted order), h [R, D] (the arena) -> (pooled [B, T, D], s [S], z [Z * D] or empty).  s and z hold
     sum_g B_g T H_g (D) elements instead of B T H (D); s is UNWEIGHTED (the weight is applied where the pool reads it)."""
     _require_gpu(t, h, w1, b1, w2, b2)
-    if save_z:
-        _chain["end"] = None
     B, T, D = t.shape
     groups, R, S, Z = _group_layout(group_b0, group_h, T)
     if (h.dim() != 2 or h.shape[0] != R or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or groups[-1][1] != B
             or max(group_h) > H):
         raise RuntimeError(f"grouped attention: target {tuple(t.shape)}, history arena {tuple(h.shape)}, fc1 {tuple(w1.shape)}, groups of "
                            f"{list(group_b0)} x {list(group_h)} rows (H = {H}) do not agree (feature width must be a multiple of 4)")
-    w1_arg = w1
-    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
-    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
-    own = w1 if w1 is w1_arg else None
-    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
-    u, _ = _gemm_nt(h, w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)                       # [R, D]
-    v, _ = _gemm_nt(t.reshape(B * T, D), w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)   # [B*T, D]
-    v = v.reshape(B, T, D)
-    st = native.stream_ptr()
-    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
-    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
-    s = torch.empty(S, dtype=torch.float32, device=t.device)
-    z = torch.empty(Z * D if save_z else 0, dtype=torch.float32, device=t.device)
-    pooled = torch.empty(B, T, D, dtype=torch.float32, device=t.device)
-    for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
-        n = b_hi - b_lo
-        _count_flops("contraction", 2.0 * n * T * H_g * D * D)
-        native.call("nrm_pwattn_fwd", native.ptr(t[b_lo:b_hi]), native.ptr(h[r_lo:r_hi]), native.ptr(u[r_lo:r_hi]), native.ptr(v[b_lo:b_hi]),
-                    native.ptr(packed), native.ptr(w2v), native.ptr(b2), native.ptr(z[z_lo * D:]) if save_z else None, native.ptr(s[s_lo:]),
-                    n, T, H_g, D, mma, st)
-        native.call("nrm_pool_bmm_wlast", native.ptr(s[s_lo:]), T * H_g, H_g, 1, native.ptr(h[r_lo:r_hi]), D, native.ptr(pooled[b_lo:b_hi]),
-                    n, T, H_g, D, 0, float(H - H_g + 1), 0, st)
-    return pooled, s, z
+    return _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, True)
 
 
 def _attend_pool_grouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
@@ -1754,52 +1799,10 @@ attend_pool_grouped_fwd = _op("attend_pool_grouped_fwd", "(Tensor t, Tensor h, T
 
 
 def _attend_pool_grouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
-    """Backward of the grouped node from the pooled gradient g [B, T, D].  Per group: weighted rowdot (the first one clears dw2 | db2) and
-    the dz pass; ONCE over all rows: the two weight-gradient GEMMs and the two side-projection dX GEMMs (_attn_bwd_once); per group again:
-    the contraction launches in the form _attn_bwd_core would choose for the group's own shape, and the pool's history gradient, whose
-    last row alone carries the weight, added onto the attention's.  The dW_p slabs of all groups lie in one buffer and reduce into the ONE dw1."""
+    """Backward of the grouped node from the pooled gradient g [B, T, D]: _attn_blocks_bwd over the plan's groups."""
     _require_gpu(g, t, h, w1, w2, s, z)
-    B, T, D = t.shape
-    groups, R, S, Z = _group_layout(group_b0, group_h, T)
-    st = native.stream_ptr()
-    w1_arg = w1
-    t, h, w1, s = _f32c(t), _f32c(h), _f32c(w1), _f32c(s)
-    own = w1 if w1 is w1_arg else None
-    w2v = _f32c(w2).reshape(-1)
-    dev = t.device
-    g, ldg = _pooled_grad_rows(g, B, T, D)
-    lib = native.load()
-    rw = mma != MMA_F32 and bool(lib.nrm_pwattn_bwd_rw_supported(D, mma))
-    acc = torch.empty(D + 4, dtype=torch.float32, device=dev)
-    dw2, db2 = acc[:D], acc[D:D + 1]
-    du = torch.empty(R, D, dtype=torch.float32, device=dev)
-    dv = torch.empty(B, T, D, dtype=torch.float32, device=dev)
-    for i, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in enumerate(groups):
-        n = b_hi - b_lo
-        ds = torch.empty(n, T, H_g, dtype=torch.float32, device=dev)
-        native.call("nrm_pool_rowdot_wlast", native.ptr(g[b_lo:b_hi]), ldg, native.ptr(h[r_lo:r_hi]), native.ptr(ds), n, T, H_g, D,
-                    native.ptr(acc) if i == 0 else None, D + 4 if i == 0 else 0, float(H - H_g + 1), st)
-        native.call("nrm_pwattn_bwd_dz", native.ptr(z[z_lo * D:]), native.ptr(ds), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
-                    native.ptr(du[r_lo:r_hi]), native.ptr(dv[b_lo:b_hi]), n, T, H_g, D, DZ_HL4 if rw else DZ_F32, st)
-    dw1, db1, dh, dt2 = _attn_bwd_once(du, dv.reshape(B * T, D), h, t.reshape(B * T, D), w1, w1_arg, own, mma, need_dt, need_dh)
-    dt = dt2.reshape(B, T, D) if need_dt else dt2
-    nsplits = [lib.nrm_pwattn_bwd_nsplit(b_hi - b_lo, T, H_g, D, mma) for b_lo, b_hi, H_g, *_ in groups]
-    wsp = torch.empty(sum(nsplits), D, D, dtype=torch.float32, device=dev)
-    none = torch.empty(0, dtype=torch.float32, device=dev)
-    k = 0
-    for ns, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in zip(nsplits, groups):
-        n = b_hi - b_lo
-        _attn_bwd_contract(lib, z[z_lo * D:], t[b_lo:b_hi], h[r_lo:r_hi].view(n, H_g, D), w1, dt[b_lo:b_hi] if need_dt else none,
-                           dh[r_lo:r_hi].view(n, H_g, D) if need_dh else none, wsp[k:k + ns], mma, rw, need_dt, need_dh, st, z_elems=Z * D)
-        k += ns
-    if need_dt or need_dh:
-        _note_chain_end()                              # after the last group
-    if need_dh:
-        for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
-            native.call("nrm_pool_bmm_wlast", native.ptr(s[s_lo:]), T * H_g, 1, H_g, native.ptr(g[b_lo:b_hi]), ldg, native.ptr(dh[r_lo:r_hi]),
-                        b_hi - b_lo, H_g, T, D, 1, float(H - H_g + 1), 1, st)
-    _slab_reduce(wsp, sum(nsplits), D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)
-    return dt, dh, dw1, db1, acc
+    groups, _, _, Z = _group_layout(group_b0, group_h, t.shape[1])
+    return _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, pool=(*_pooled_grad_rows(g, *t.shape), s))
 
 
 def _attend_pool_grouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
@@ -1813,41 +1816,7 @@ attend_pool_grouped_bwd = _op("attend_pool_grouped_bwd", "(Tensor g, Tensor t, T
                               _attend_pool_grouped_bwd_impl, _attend_pool_grouped_bwd_fake)
 
 
-def _attend_pool_grouped_setup(ctx, inputs, output):
-    t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma = inputs
-    pooled, s, z = output
-    ctx.set_materialize_grads(False)
-    ctx.save_z, ctx.mma, ctx.consumed = save_z, mma, False
-    ctx.groups = (list(group_b0), list(group_h), H)
-    ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
-    ctx.mark_non_differentiable(s, z)
-    if save_z:
-        ctx.save_for_backward(t, h, w1, w2, s, z)
-
-
-def _attend_pool_grouped_backward(ctx, g, _ds, _dz):
-    if g is None:
-        return (None,) * 11
-    if not ctx.save_z:
-        raise RuntimeError("grouped attention: the forward ran with save_z=False (no-grad / inference call); there is nothing to "
-                           "differentiate through")
-    t, h, w1, w2, s, z = ctx.saved_tensors
-    if _retain_attention_graph:
-        z = z.detach().clone()
-    elif ctx.consumed:
-        raise RuntimeError("grouped attention: a second backward through the same graph finds the saved pre-activation overwritten by the "
-                           "first one's dz (the grouped node does not recompute it); call ops.set_retain_attention_graph(True) before "
-                           "the forward's backward passes to work on a copy instead")
-    else:
-        ctx.consumed, z = True, z.detach()
-    need = ctx.needs_input_grad
-    dt, dh, dw1, db1, dw2b2 = attend_pool_grouped_bwd(g, t, h, w1, w2, s, z, *ctx.groups, ctx.mma, bool(need[0]), bool(need[1]))
-    D = t.shape[2]
-    return ((dt if need[0] else None), (dh if need[1] else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
-            dw2b2[D:D + 1].reshape(ctx.b2_shape), None, None, None, None, None)
-
-
-torch.library.register_autograd("nrm::attend_pool_grouped_fwd", _attend_pool_grouped_backward, setup_context=_attend_pool_grouped_setup, lib=_LIB)
+_attention_node("attend_pool_grouped_fwd", attend_pool_grouped_bwd, 5, True, False)
 
 
 def attend_and_pool_grouped(target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
@@ -2379,21 +2348,13 @@ def _attend_pool_ragged_fwd_impl(t, h, w1, b1, w2, b2, cand_imp, cand_off, max_c
     if h.shape[2] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or tuple(cand_imp.shape) != (N,) or tuple(cand_off.shape) != (B + 1,):
         raise RuntimeError(f"ragged attention: target {tuple(t.shape)}, history {tuple(h.shape)}, fc1 {tuple(w1.shape)}, cand_imp "
                            f"{tuple(cand_imp.shape)}, cand_off {tuple(cand_off.shape)} do not agree (feature width must be a multiple of 4)")
-    w1_arg = w1
-    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
-    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
     s = torch.empty(N, H, dtype=torch.float32, device=t.device)
     pooled = torch.empty(N, D, dtype=torch.float32, device=t.device)
     if N == 0 or B * H == 0:
         return pooled.zero_(), s.zero_()
     cand_imp, cand_off = _tab(cand_imp), _tab(cand_off)
-    own = w1 if w1 is w1_arg else None
-    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
-    u, _ = _gemm_nt(h.reshape(B * H, D), w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)     # [B*H, D]
-    v, _ = _gemm_nt(t, w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)                      # [N, D]
+    t, h, u, v, packed, w2v, b2 = _attn_operands(t, h, w1, b1, w2, b2, mma)       # u [B*H, D], v [N, D]
     st = native.stream_ptr()
-    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
-    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
     _count_flops("contraction", 2.0 * N * H * D * D)
     native.call("nrm_pwattn_fwd_ragged", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v), native.ptr(packed), native.ptr(w2v),
                 native.ptr(b2), native.ptr(s), native.ptr(cand_imp), native.ptr(cand_off), B, N, int(max_count), H, D, mma, st,
@@ -2414,14 +2375,8 @@ def attend_pool_ragged(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bi
     D = target.shape[-1]
     args = (target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
     _require_gpu(*args)
-    if D % 4:
-        P = _pad4(D) - D
-        pad = torch.nn.functional.pad
-        blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]
-        args = (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
-                pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
     with torch.no_grad():
-        return attend_pool_ragged_fwd(*args, cand_imp, cand_off, int(max_count), resolve_mma(mma))[0][:, :D]
+        return attend_pool_ragged_fwd(*_pad_feature_width(*args), cand_imp, cand_off, int(max_count), resolve_mma(mma))[0][:, :D]
 
 
 # ---- history compaction: the trailing all-zero history rows are dropped like the padded candidates.  Tables (int32,
@@ -2499,21 +2454,13 @@ def _attend_pool_hragged_fwd_impl(t, h, w1, b1, w2, b2, cand_imp, cand_off, hist
         raise RuntimeError(f"history-ragged attention: target {tuple(t.shape)}, history {tuple(h.shape)}, fc1 {tuple(w1.shape)}, cand_imp "
                            f"{tuple(cand_imp.shape)}, cand_off {tuple(cand_off.shape)}, hist_off {tuple(hist_off.shape)}, hist_mult {tuple(hist_mult.shape)}, "
                            f"tile_pre {tuple(tile_pre.shape)}, tile_tab {tuple(tile_tab.shape)} do not agree (feature width must be a multiple of 4)")
-    w1_arg = w1
-    t, h, w1, b1 = _f32c(t), _f32c(h), _f32c(w1), _f32c(b1)
-    w2v, b2 = _f32c(w2).reshape(-1), _f32c(b2).reshape(-1)
     s = torch.empty(16 * Mt, dtype=torch.float32, device=t.device)
     pooled = torch.empty(N, D, dtype=torch.float32, device=t.device)
     if N == 0 or R == 0 or Mt == 0 or B == 0:
         return pooled.zero_(), s.zero_()
     cand_imp, cand_off, hist_off, hist_mult, tile_pre = _tab(cand_imp), _tab(cand_off), _tab(hist_off), _tab(hist_mult), _tab(tile_pre)
-    own = w1 if w1 is w1_arg else None
-    w_h, w_t, w_d = w1[:, :D], w1[:, D:2 * D], w1[:, 2 * D:3 * D]
-    u, _ = _gemm_nt(h, w_h, 4 * D, 1, D, D, b1, EPI_BIAS, src2=w_d, sign2=-1.0, owner=own, mma=mma)                       # [R, D]
-    v, _ = _gemm_nt(t, w_t, 4 * D, 1, D, D, None, EPI_BIAS, src2=w_d, sign2=1.0, owner=own, mma=mma)                      # [N, D]
+    t, h, u, v, packed, w2v, b2 = _attn_operands(t, h, w1, b1, w2, b2, mma)       # u [R, D], v [N, D]
     st = native.stream_ptr()
-    packed = torch.empty(native.load().nrm_pwattn_packed_floats(D), dtype=torch.float32, device=t.device)
-    native.call("nrm_pwattn_pack_wp", native.ptr(w1), 4 * D, D, mma, native.ptr(packed), st)
     _count_flops("contraction", 2.0 * 16 * Mt * D * D)
     native.call("nrm_pwattn_fwd_hragged", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v), native.ptr(packed), native.ptr(w2v),
                 native.ptr(b2), native.ptr(s), native.ptr(cand_imp), native.ptr(cand_off), native.ptr(hist_off), native.ptr(tile_pre),
@@ -2536,14 +2483,8 @@ def attend_pool_hragged(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_b
     D = target.shape[-1]
     args = (target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
     _require_gpu(*args)
-    if D % 4:
-        P = _pad4(D) - D
-        pad = torch.nn.functional.pad
-        blocks = [pad(fc1_weight[:, i * D:(i + 1) * D], (0, P, 0, P)) for i in range(4)]
-        args = (pad(target.to(torch.float32), (0, P)), pad(history.to(torch.float32), (0, P)), torch.cat(blocks, dim=1),
-                pad(fc1_bias, (0, P)), pad(fc2_weight.reshape(1, D), (0, P)), fc2_bias)
     with torch.no_grad():
-        return attend_pool_hragged_fwd(*args, tabs["cand_imp"], tabs["cand_off"], tabs["hist_off"], tabs["hist_mult"], tabs["tile_pre"],
+        return attend_pool_hragged_fwd(*_pad_feature_width(*args), tabs["cand_imp"], tabs["cand_off"], tabs["hist_off"], tabs["hist_mult"], tabs["tile_pre"],
                                        tabs["tile_tab"], int(max_count), int(k_max), resolve_mma(mma))[0][:, :D]
 
 
