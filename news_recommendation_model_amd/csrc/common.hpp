@@ -19,6 +19,21 @@ inline int device_cus() {
     return cus > 0 ? cus : 256;
 }
 
+// XCD-aware block order.  Hardware deals consecutive linear block ids round-robin over the 8 XCDs, each with its own L2; this maps
+// linear id `lin` of `nblk` blocks to a logical id such that consecutive logical ids run on ONE XCD (blocks that read the same
+// bytes then share an L2).  Bijective for any nblk; pure speed, any mapping is correct.
+__device__ __forceinline__ int xcd_logical_block(int lin, int nblk) {
+    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
+    return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+}
+
+// Raw buffer descriptor over `bytes` bytes at ptr (stride 0: offsets are plain bytes, checked against the extent -- a load past it
+// returns 0, a store is dropped), and the per-lane offset that is out of range for every extent.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* ptr, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, bytes, 0x00020000);
+}
+constexpr unsigned BUF_OOB = 0x80000000u;
+
 // D(16x16) += A(16x4) * B(4x16), f32 in / f32 accumulate.
 // lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15];
 // it receives D[row = 4*(l>>4) + r][col = l&15] in element r of the accumulator.

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.hpp"
+#include "tn_tile.hpp"
 #include "gemm.hpp"
 // timing diagnostics only (scripts/_diag): results are WRONG with any bit set -- 1: no barrier in the K loop of gemm_nt,
 // 2: gemm_nt without its epilogue stores, 4: gemm_nt DMAs only its first K-chunk, 8: gemm_tn never reloads its operands
@@ -130,26 +131,22 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
     const int nc = blockIdx.y;                                       // N-chunk of this workgroup
     const int n0 = nc * WROWS;
 
-    constexpr unsigned OOB = 0x80000000u;
     const int rows_here = min(BM, M - m0);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, p.wp_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wp, p.wp_bytes);
     // per-workgroup descriptors: base = first row of the block, extent = its valid rows -> rows >= M read 0 /
     // are not stored, and every offset fits 32 bits whatever M is
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x) + (size_t)m0 * p.ldx, 0, ((rows_here - 1) * p.ldx + p.xcols) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.ldy, 0, rows_here * p.ldy * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-        p.z ? p.z + (size_t)m0 * p.ldz : nullptr, 0, p.z ? rows_here * p.ldz * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (p.N + 3) / 4 * 16 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(EPI == EPI_MUL ? p.m + (size_t)m0 * p.ldm : nullptr), 0, EPI == EPI_MUL ? rows_here * p.ldm * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.x + (size_t)m0 * p.ldx, ((rows_here - 1) * p.ldx + p.xcols) * 4);
+    const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(p.y + (size_t)m0 * p.ldy, rows_here * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(p.z ? p.z + (size_t)m0 * p.ldz : nullptr, p.z ? rows_here * p.ldz * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rs_b = buffer_rsrc(p.bias, p.bias ? (p.N + 3) / 4 * 16 : 0);
+    const __amdgpu_buffer_rsrc_t rs_m = buffer_rsrc(EPI == EPI_MUL ? p.m + (size_t)m0 * p.ldm : nullptr, EPI == EPI_MUL ? rows_here * p.ldm * 4 : 0);
 
     unsigned voff_x[MT];
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
         const int rl = (wave * MT + j) * 16 + (lane >> 2);
         const unsigned slot = (unsigned)((lane & 3) ^ swz4(lane >> 2));
-        voff_x[j] = rl < rows_here ? (unsigned)(rl * p.ldx + 4 * slot) * 4u : OOB;
+        voff_x[j] = rl < rows_here ? (unsigned)(rl * p.ldx + 4 * slot) * 4u : BUF_OOB;
     }
     const int rslot = 4 * (q ^ swz4(r16));
 
@@ -366,39 +363,7 @@ hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, 
 // gemm_tn: every wave owns a (KT*16 i) x (DT*16 j) tile of C[i,j] = sum_r A[r,i] B[r,j] and a row range.
 // slab layout: ws[split][j][ldws] (transposed, float4 along i);  colsum[split][i] = sum_r A[r,i] (tiles j0 == 0).
 //
-// Column layout of an operand block of W MFMA tiles (W in {2, 4, 5, 8}; as in the backward contractions, pwattn_bwd.hip
-// tile_col): fragment index r (0..15) of tile t is block column
-//     W = 2:  2 r + t            (one  8-byte load per lane and reduction step)
-//     W = 4:  4 r + t            (one 16-byte load)
-//     W = 5:  4 r + t | 64 + r   (16 + 4 bytes)
-//     W = 8:  4 r + t | 64 + 4 r + (t - 4)      (two 16-byte loads)
-// so a lane's loads feed W MFMA operands without any shuffle.  Round 4 added W = 2 and 8: the head's weight gradients are
-// 26 x 101 tiles of 16 (402 x 1608), which 4 x 4 wave tiles cover with 10.4 % padding and 2 x 8 with 3 % (13 x 13 exactly
-// in i); w1's 25 x 26 tiles are exact in 5 x 2.
-template <int W> __device__ __forceinline__ int tn_col(int t, int r) {
-    if (W == 2) return 2 * r + t;
-    if (W == 5 && t == 4) return 64 + r;
-    if (W == 8 && t >= 4) return 64 + 4 * r + (t - 4);
-    return 4 * r + t;
-}
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int W> __device__ __forceinline__ void tn_load(float (&v)[W], const __amdgpu_buffer_rsrc_t rs, unsigned vlo, unsigned vhi, int soff) {
-    if constexpr (W == 2) {
-        const auto x = __builtin_amdgcn_raw_buffer_load_b64(rs, vlo, soff, 0);
-        v[0] = __uint_as_float(x[0]); v[1] = __uint_as_float(x[1]);
-    } else {
-        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, vlo, soff, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __uint_as_float(x[e]);
-        if constexpr (W == 5) v[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vhi, soff, 0));
-        if constexpr (W == 8) {
-            const u32x4 y = __builtin_amdgcn_raw_buffer_load_b128(rs, vhi, soff, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 + e] = __uint_as_float(y[e]);
-        }
-    }
-}
-#endif
+// Column layout and loads of an operand block of W MFMA tiles: tn_col / tn_load (tn_tile.hpp).
 constexpr int tn_waves_per_simd(int KT, int DT) { return KT * DT <= 16 ? 4 : 3; }      // 64 accumulator VGPRs: 4 waves; 100: 3
 
 template <int KT, int DT>
@@ -411,8 +376,7 @@ __global__ __launch_bounds__(256, tn_waves_per_simd(KT, DT)) void gemm_tn_kernel
     // XCD-aware order (as in the backward contractions): the nti*ntj output tiles of one row split read the SAME rows of
     // A and B; consecutive logical ids go to one XCD, so those rows come from HBM once instead of once per XCD.
     const int nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+    const int logical = xcd_logical_block(lin, nblk);
     const int bx = logical % gridDim.x, by = logical / gridDim.x;
     const int ti = bx % p.nti, tj = bx / p.nti;
     const int i0 = ti * (KT * 16), j0 = tj * (DT * 16);

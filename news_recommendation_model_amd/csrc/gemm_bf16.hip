@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const GemmTnParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, q = lane >> 4;
     const int nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+    const int logical = xcd_logical_block(lin, nblk);
     const int bx = logical % gridDim.x, by = logical / gridDim.x;
     const int ti = bx % p.nti, tj = bx / p.nti;
     const int i0 = ti * 64, j0 = tj * 64;
@@ -69,9 +68,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const GemmTnParams
         const_cast<float*>(p.B) + (size_t)r_lo * p.ldb, 0, nrows > 0 ? ((nrows - 1) * p.ldb + p.bcols) * 4 : 0, 0x00020000);
     // lane (r16, q) holds columns 4 r16 + tile of tiles 0..3 (one 16-byte load feeds four MFMA operands); load j of a super-step
     // is row 4 j + q
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned va4 = i0 + 4 * r16 < p.acols ? (unsigned)(q * p.lda + i0 + 4 * r16) * 4u : OOB;
-    const unsigned vb4 = j0 + 4 * r16 < p.bcols ? (unsigned)(q * p.ldb + j0 + 4 * r16) * 4u : OOB;
+    const unsigned va4 = i0 + 4 * r16 < p.acols ? (unsigned)(q * p.lda + i0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vb4 = j0 + 4 * r16 < p.bcols ? (unsigned)(q * p.ldb + j0 + 4 * r16) * 4u : BUF_OOB;
     const int astep = p.lda * 16, bstep = p.ldb * 16;                  // 4 rows, bytes
 
     f32x4 C[KT][DT];
@@ -177,16 +175,12 @@ __global__ __launch_bounds__(RX_WAVES * 64, RT <= 2 ? RX_WAVES / 2 : RX_WAVES / 
     const int m0 = blockIdx.x * BM;
     const int rows_here = min(BM, p.M - m0);
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x) + (size_t)m0 * p.ldx, 0, ((rows_here - 1) * p.ldx + p.xcols) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wq), 0, p.wq_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.ldy, 0, rows_here * p.ldy * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-        p.z ? p.z + (size_t)m0 * p.ldz : nullptr, 0, p.z ? rows_here * p.ldz * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (p.N + 3) / 4 * 16 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(EPI == EPI_MUL ? p.m + (size_t)m0 * p.ldm : nullptr), 0, EPI == EPI_MUL ? rows_here * p.ldm * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.x + (size_t)m0 * p.ldx, ((rows_here - 1) * p.ldx + p.xcols) * 4);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wq, p.wq_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(p.y + (size_t)m0 * p.ldy, rows_here * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(p.z ? p.z + (size_t)m0 * p.ldz : nullptr, p.z ? rows_here * p.ldz * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rs_b = buffer_rsrc(p.bias, p.bias ? (p.N + 3) / 4 * 16 : 0);
+    const __amdgpu_buffer_rsrc_t rs_m = buffer_rsrc(EPI == EPI_MUL ? p.m + (size_t)m0 * p.ldm : nullptr, EPI == EPI_MUL ? rows_here * p.ldm * 4 : 0);
 
     // ---- prologue: the block's rows, 4 columns per thread and turn (four turns in flight), split once and written as 8-byte
     // halves of a slot
@@ -200,7 +194,7 @@ __global__ __launch_bounds__(RX_WAVES * 64, RT <= 2 ? RX_WAVES / 2 : RX_WAVES / 
             const int idx = base + u * RX_WAVES * 64;
             rowv[u] = idx / g4_per_row; g4v[u] = idx - rowv[u] * g4_per_row;
             const bool ok = idx < nunit && rowv[u] < rows_here && 4 * g4v[u] + 3 < p.xcols;
-            v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? (unsigned)((rowv[u] * p.ldx + 4 * g4v[u]) * 4) : OOB, 0, 0));
+            v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? (unsigned)((rowv[u] * p.ldx + 4 * g4v[u]) * 4) : BUF_OOB, 0, 0));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -241,7 +235,7 @@ __global__ __launch_bounds__(RX_WAVES * 64, RT <= 2 ? RX_WAVES / 2 : RX_WAVES / 
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             const int cc = g * G + j;
-            const unsigned vo = (f < total && cc < K32) ? wlane : OOB;
+            const unsigned vo = (f < total && cc < K32) ? wlane : BUF_OOB;
             const int so = ((tile * K32 + cc) * WIMG) * 1024;
             wh[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo, so, 0);
             if (MMA == 2) wl[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo, so + 1024, 0);

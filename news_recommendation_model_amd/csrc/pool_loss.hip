@@ -55,7 +55,6 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
     const int ig = (int)((task / nslab) % nig);
     const int b = (int)(task / ((long)nslab * nig));
     const int d0 = slab * 64, i0 = ig * 64;
-    constexpr unsigned OOB = 0x80000000u;
     if (RAGGED) {
         const int c0 = min(max(cand_off[b], 0), N);
         I = min(max(cand_off[b + 1], c0), N) - c0;                      // this impression's rows
@@ -80,9 +79,8 @@ __global__ __launch_bounds__(256) void bmm_rows_kernel(const float* __restrict__
         if (mult > 0) wlast = (float)mult;
     }
     const float* Wb = W + b * wsb;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(X) + b * xsb, 0, ((J - 1) * ldx + D) * 4, 0x00020000);
-    const unsigned vx = d0 + 4 * r16 < D ? (unsigned)(q * ldx + d0 + 4 * r16) * 4u : OOB;      // D % 4 == 0
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(X + b * xsb, ((J - 1) * ldx + D) * 4);
+    const unsigned vx = d0 + 4 * r16 < D ? (unsigned)(q * ldx + d0 + 4 * r16) * 4u : BUF_OOB;      // D % 4 == 0
     f32x4 acc[4][4];
 #pragma unroll
     for (int it = 0; it < 4; ++it)
@@ -178,27 +176,24 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ g
     if (tile >= B * ntt) return;
     const int b = tile / ntt, t0 = (tile - b * ntt) * 16;
     const int trows = min(16, T - t0);
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g) + b * gsb + (long)t0 * ldg, 0, ((trows - 1) * ldg + D) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(h) + b * hsb, 0, ((H - 1) * ldh + D) * 4, 0x00020000);
-    const unsigned va = r16 < trows ? (unsigned)(r16 * ldg + 4 * q) * 4u : OOB;
+    const __amdgpu_buffer_rsrc_t rs_g = buffer_rsrc(g + b * gsb + (long)t0 * ldg, ((trows - 1) * ldg + D) * 4);
+    const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(h + b * hsb, ((H - 1) * ldh + D) * 4);
+    const unsigned va = r16 < trows ? (unsigned)(r16 * ldg + 4 * q) * 4u : BUF_OOB;
     const int nchunk = (D + 15) >> 4;
     for (int h0 = 0; h0 < H; h0 += 64) {
         unsigned vb[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) vb[j] = h0 + 16 * j + r16 < H ? (unsigned)((h0 + 16 * j + r16) * ldh + 4 * q) * 4u : OOB;
+        for (int j = 0; j < 4; ++j) vb[j] = h0 + 16 * j + r16 < H ? (unsigned)((h0 + 16 * j + r16) * ldh + 4 * q) * 4u : BUF_OOB;
         f32x4 acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         // columns >= D of the last chunk (D % 16 != 0): D % 4 == 0, so a lane's four columns are all in or all out
         auto load_chunk = [&](int c, f32x4& a4, f32x4 (&b4)[4]) {
             const bool ok = 16 * c + 4 * q < D;
-            a4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_g, ok ? va : OOB, c * 64, 0));
+            a4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_g, ok ? va : BUF_OOB, c * 64, 0));
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                b4[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_h, ok ? vb[j] : OOB, c * 64, 0));
+                b4[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_h, ok ? vb[j] : BUF_OOB, c * 64, 0));
         };
         auto mfma_chunk = [&](const f32x4& a4, const f32x4 (&b4)[4]) {
 #pragma unroll

@@ -69,10 +69,10 @@ struct BwdEParams {
     int gps;                              // groups per split
     int nkw, ndcol;                       // k-ranges and d-columns of the wave-tile grid
     int nsplit;
-    int interleave;                       // serial kernel: the 4 waves of a workgroup walk one group range round-robin
+    int interleave;                       // the 4 waves of a workgroup walk one group range round-robin (serial and one-accumulator kernels; the pipelined and 32-row kernels always walk blocked)
     int x_hl4;                            // X is in the NRM_DZ_HL4 format (bf16 forms only): no conversion of the dz operand
     int with_dt;                          // 0: the (b,t)-grouped pass only accumulates dW_p (dt comes from pwattn_bwd_rw.hip)
-    int order;                            // serial kernel, block order inside an XCD: 0 = (split group, k-range, d-column), 1 = (k-range, split group, d-column)
+    int order;                            // block order inside an XCD: 0 = (split group, k-range, d-column), 1 = (k-range, split group, d-column) (serial and one-accumulator kernels; the pipelined and 32-row kernels always take 0 -- e_tile / e_groups in pwattn_bwd.hip)
 };
 struct BwdEPlan { int DT, KT, ndcol, nkw, nsplit, gps; };
 BwdEPlan bwd_e_plan(int D, int G, int target_waves, int min_gps = 1, int mma = 0);

@@ -40,6 +40,7 @@
 #endif
 #include "common.hpp"
 #include "pwattn.hpp"
+#include "tn_tile.hpp"
 
 namespace nrm {
 
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(256) void bwd_dz_kernel(float* __restrict__ z, cons
     // boundaries at 400-B multiples), and hardware deals consecutive block ids round-robin over the 8 XCDs.  Consecutive
     // LOGICAL ids (the slabs of one b) go to one XCD, so a shared line is fetched / written back once, not once per L2.
     const int nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+    const int logical = xcd_logical_block(lin, nblk);
     const int b = logical / gridDim.x, slab = logical - b * gridDim.x;
     const int col = slab * slab_cols + 4 * tx;
     const bool cok = ty < ny && col < D;                             // D % 4 == 0
@@ -230,9 +230,8 @@ __global__ __launch_bounds__(THREADS, 4) void bwd_dz_rows_kernel(float* __restri
     float ab = 0.f;
     const bool sum_ds = db2 != nullptr && tx == 0;
     // one buffer descriptor per workgroup (base = the impression's first row): 32-bit offsets, rows past T*H read 0
-    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(z + (size_t)b * T * H * D, 0, (unsigned)((size_t)T * H * D * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ds) + (size_t)b * T * H, 0, (unsigned)(T * H * 4), 0x00020000);
-    constexpr unsigned OOB = 0x80000000u;
+    const __amdgpu_buffer_rsrc_t rz = buffer_rsrc(z + (size_t)b * T * H * D, (unsigned)((size_t)T * H * D * 4));
+    const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(ds + (size_t)b * T * H, (unsigned)(T * H * 4));
 
     f32x4 zb[3][RC];
     float gb[3][RC];
@@ -242,8 +241,8 @@ __global__ __launch_bounds__(THREADS, 4) void bwd_dz_rows_kernel(float* __restri
             const int h = ty + ny * (c * RC + u);
             const bool ok = act && t < T && h < H;
             const unsigned row = (unsigned)(t * H + h);
-            g[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, ok ? row * 4u : OOB, 0, 0));
-            zz[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, ok ? (row * (unsigned)D + (unsigned)col) * 4u : OOB, 0, 0));
+            g[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rg, ok ? row * 4u : BUF_OOB, 0, 0));
+            zz[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, ok ? (row * (unsigned)D + (unsigned)col) * 4u : BUF_OOB, 0, 0));
         }
     };
     auto compute_rows = [&](int t, int c, const f32x4 (&zz)[RC], const float (&g)[RC], f32x4 (&acc)[RC], f32x4& av) {
@@ -412,8 +411,96 @@ hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2,
 // Column layout of the wide-load contraction kernel: local column c of an 80-wide (or 64-wide) wave tile lives in MFMA
 // tile c&3 at lane-row c>>2 for c < 64 and in tile 4 at lane-row c-64 above; tile_pos is where that column sits in the
 // tile-major order (16*tile + row) the LDS W_p^T image and the accumulators are indexed by.
-__device__ __forceinline__ int tile_col(int tile, int row) { return tile < 4 ? 4 * row + tile : 64 + row; }
+// (the column of (tile, lane-row) is tn_col<5>, or tn_col<4> on 64-wide tiles: tn_tile.hpp)
 __device__ __forceinline__ int tile_pos(int c) { return c < 64 ? 16 * (c & 3) + (c >> 2) : c; }
+
+// ---- One walk, four loops.  The four contraction kernels below share their walk; each keeps its reduction loop and its own
+// copy of the lane offsets and of the ways results leave the wave.  Which kernel uses which shared piece:
+//                          e_tile  e_groups  e_open  tn_load_*  e_mfma
+//   bwd_e_kernel            yes     yes       yes     yes        yes (fp32 arithmetic)
+//   bwd_e_pipe_kernel       yes     yes       yes     --         yes
+//   bwd_dw_direct_kernel    yes     yes       yes     --         yes
+//   bwd_dw_r32_kernel       yes     yes       yes     --         --  (its own 32-deep bf16 step)
+// NOT shared (a copy per kernel that needs it): the per-lane offsets, extents and steps, the W_p^T tile -> LDS prologue, the
+// out-row flush, the scale-row load and the transposed slab store; the pipelined and the direct kernel also keep their operand
+// load.  Each of these was tried as a __forceinline__ function: it compiles to the same arithmetic, but hipcc then allocates
+// registers and schedules differently (DESIGN.md section 4g lists what moved).  With the pieces above the pipelined and the r32
+// kernel assemble exactly as before and the other two within one scalar division of the code they replace (e_tile as a
+// function -- in any form, a lambda included -- costs that division; written in place it does not).
+//
+// Two launch parameters are honoured by the serial and the direct kernel ONLY (HONOUR = true there, false in the pipelined and
+// the r32 kernel, which always take order 0 and the blocked walk): p.order and p.interleave.  Any bijective block order and
+// either walk is correct, so this is a matter of speed alone.
+
+// The wave tile of this workgroup and its group of four splits.  XCD-aware: the ndcol tiles that share one (split group, k-range)
+// read the SAME dz bytes; they get consecutive logical ids, hence one XCD, so that four of the five reads of a dz line are L2
+// hits instead of HBM / fabric fetches.
+// order 1 (big groups, C5): k-range-major -- an XCD then holds few k-ranges (nkw / 8 of them), so the dz columns it streams
+// are ITS columns: every dz byte is fetched by one XCD only, and its co-resident workgroups (a k-range's d-columns of a few
+// split groups) share each dz slice while it is hot.  With order 0 the ndcol * nkw tile kinds of one split group exceed the
+// XCD's resident workgroups (144 kinds against 64 at D = 768), so the kinds run in batches and every batch streams the
+// groups' history rows again.
+struct ETile { int d0, k0, sgrp; };
+template <int KT, int DT, bool HONOUR>
+__device__ __forceinline__ ETile e_tile(const BwdEParams& p) {
+    const int nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
+    const int logical = xcd_logical_block(lin, nblk);
+    const int dcol = logical % p.ndcol;
+    int kw, sgrp;
+    if (HONOUR && p.order == 1) {
+        const int nsg = nblk / (p.ndcol * p.nkw);
+        sgrp = (logical / p.ndcol) % nsg;
+        kw = logical / (p.ndcol * nsg);
+    } else {
+        kw = (logical / p.ndcol) % p.nkw;
+        sgrp = logical / (p.ndcol * p.nkw);
+    }
+    return {dcol * (DT * 16), kw * (KT * 16), sgrp};
+}
+
+// Group walk of a wave.  Blocked: the gps consecutive groups of its split.  Interleaved (p.interleave): the 4 waves of the
+// workgroup walk ONE range of 4*gps groups round-robin, so at any time they sit on neighbouring groups -- mostly the
+// same g1, i.e. the same Y rows, and a quarter of the distinct rows in flight per XCD (what the L2 has to hold).
+struct EGroups { int lo, hi, step; };
+template <bool HONOUR>
+__device__ __forceinline__ EGroups e_groups(const BwdEParams& p, int sgrp, int wave) {
+    const int lo = (sgrp * 4 + wave) * p.gps;
+    EGroups r = {lo, min(p.G, lo + p.gps), 1};
+    if (HONOUR && p.interleave) {
+        const int nact = min(4, p.nsplit - sgrp * 4);
+        r = {sgrp * 4 * p.gps + wave, min(p.G, (sgrp * 4 + nact) * p.gps), nact};
+    }
+    return r;
+}
+
+// Operands stream from global memory straight into MFMA operand registers through buffer descriptors
+// rebuilt per group (uniform base = the group's first row, extent = R rows): the per-lane part of the
+// address is a loop-invariant 32-bit offset (row q of the step, columns of the lane), the step advances
+// the scalar offset, and rows >= R read as 0 by the hardware bounds check -- no masks, no address VALU.
+// Column layout (tn_col): ONE 16-byte load per lane feeds tiles 0..3 and one dword load tile 4, i.e. 4
+// vector-memory instructions per reduction step, each a set of whole 256-B / 64-B row segments.
+// Columns >= D (general shapes) get the out-of-range offset and read as 0.
+#if defined(__HIP_DEVICE_COMPILE__)      // buffer-descriptor builtins: device pass only
+// the operand rows of group g: xbytes / ybytes = extent of one group's X / Y rows
+struct EOperands { __amdgpu_buffer_rsrc_t x, y; };
+__device__ __forceinline__ EOperands e_open(const BwdEParams& p, int g, unsigned xbytes, unsigned ybytes) {
+    const int g1 = g / p.G2, g2 = g - g1 * p.G2;
+    return {buffer_rsrc(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2, xbytes), buffer_rsrc(p.Y + (long)g1 * p.ys1, ybytes)};
+}
+#endif
+// E += a (x) b over the KT x DT tiles, the tiles fed by the two 16-byte loads first.  FIRST: onto an inline-constant 0 (no
+// accumulator clearing).
+template <int KT, int DT, bool FIRST = false>
+__device__ __forceinline__ void e_mfma(f32x4 (&E)[KT][DT], const float (&a)[KT], const float (&b)[DT]) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) E[it][jt] = mfma16(a[it], b[jt], FIRST ? f32x4{0.f, 0.f, 0.f, 0.f} : E[it][jt]);
+#pragma unroll
+    for (int it = 0; it < KT; ++it)
+#pragma unroll
+        for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) E[it][jt] = mfma16(a[it], b[jt], FIRST ? f32x4{0.f, 0.f, 0.f, 0.f} : E[it][jt]);
+}
 
 // BF16 (NRM_MMA_BF16): the same grouped contraction on v_mfma_f32_16x16x32_bf16.  Operands are read exactly as in the fp32
 // form (fp32 rows, the same lane -> column map); eight 4-row reduction steps are rounded to bf16 and packed into ONE
@@ -443,32 +530,8 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
     float* bounce = smem + (WITH_DT ? DT * 16 * LDK + wave * (DT * 16) : 0);   // wave-private
     const int r16 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R;
-
-    // XCD-aware block order.  The ndcol tiles that share one (split group, k-range) read the SAME dz bytes:
-    // give them consecutive logical ids and map consecutive logical ids to one XCD (hardware deals linear
-    // block ids round-robin over the 8 XCDs, each with its own L2), so that four of the five reads of a dz
-    // line are L2 hits instead of HBM/fabric fetches.  Pure speed: any mapping is correct.
-    const int nblk = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;         // bijective for any nblk
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
-    // order 1 (big groups, C5): k-range-major -- an XCD then holds few k-ranges (nkw / 8 of them), so the dz columns it streams
-    // are ITS columns: every dz byte is fetched by one XCD only, and its co-resident workgroups (a k-range's d-columns of a few
-    // split groups) share each dz slice while it is hot.  With order 0 the ndcol * nkw tile kinds of one split group exceed the
-    // XCD's resident workgroups (144 kinds against 64 at D = 768), so the kinds run in batches and every batch streams the
-    // groups' history rows again.
-    const int dcol = logical % p.ndcol;
-    int kw, sgrp;
-    if (p.order == 1) {
-        const int nsg = nblk / (p.ndcol * p.nkw);
-        sgrp = (logical / p.ndcol) % nsg;
-        kw = logical / (p.ndcol * nsg);
-    } else {
-        kw = (logical / p.ndcol) % p.nkw;
-        sgrp = logical / (p.ndcol * p.nkw);
-    }
-    const int d0 = dcol * (DT * 16);
-    const int k0 = kw * (KT * 16);
+    const ETile tl = e_tile<KT, DT, true>(p);
+    const int d0 = tl.d0, k0 = tl.k0, sgrp = tl.sgrp;
 
     // ---- prologue: W_p^T tile -> LDS (zero padded), one barrier
     if (WITH_DT) {
@@ -485,30 +548,15 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
 
     const int split = sgrp * 4 + wave;
     if (split >= p.nsplit) return;
-    // Group walk of a wave.  Blocked: the gps consecutive groups of its split.  Interleaved (p.interleave): the 4 waves of the
-    // workgroup walk ONE range of 4*gps groups round-robin, so at any time they sit on neighbouring groups -- mostly the
-    // same g1, i.e. the same Y rows, and a quarter of the distinct rows in flight per XCD (what the L2 has to hold).
-    int g_lo = split * p.gps, g_step = 1;
-    int g_hi = min(p.G, g_lo + p.gps);
-    if (p.interleave) {
-        const int nact = min(4, p.nsplit - sgrp * 4);
-        g_lo = sgrp * 4 * p.gps + wave; g_step = nact;
-        g_hi = min(p.G, (sgrp * 4 + nact) * p.gps);
-    }
+    const EGroups gr = e_groups<true>(p, sgrp, wave);
+    const int g_lo = gr.lo, g_hi = gr.hi, g_step = gr.step;
     const int nsteps = (R + 3) >> 2;
 
-    // Operands stream from global memory straight into MFMA operand registers through buffer descriptors
-    // rebuilt per group (uniform base = the group's first row, extent = R rows): the per-lane part of the
-    // address is a loop-invariant 32-bit offset (row q of the step, columns of the lane), the step advances
-    // the scalar offset, and rows >= R read as 0 by the hardware bounds check -- no masks, no address VALU.
-    // Column layout (tile_col): ONE 16-byte load per lane feeds tiles 0..3 and one dword load tile 4, i.e. 4
-    // vector-memory instructions per reduction step, each a set of whole 256-B / 64-B row segments.
-    // Columns >= D (general shapes) get the out-of-range offset and read as 0.
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : OOB;
-    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : OOB;
-    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : OOB;
-    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : OOB;
+    // per-lane operand offsets (see e_open)
+    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : BUF_OOB;
+    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : BUF_OOB;
     const unsigned xbytes = (unsigned)(((long)(R - 1) * p.xrs + D) * 4);
     const unsigned ybytes = (unsigned)(((long)(R - 1) * p.yrs + D) * 4);
     const int xstep = (int)(p.xrs * 16), ystep = (int)(p.yrs * 16);     // 4 rows, bytes
@@ -524,30 +572,17 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
     // two operand register sets (ping-pong, no copies)
     float a0[KT], b0[DT], a1[KT], b1[DT];
     __amdgpu_buffer_rsrc_t rx, ry;
-    auto open_group = [&](int gg) {
-        const int g1 = gg / p.G2, g2 = gg - g1 * p.G2;
-        rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2), 0, xbytes, 0x00020000);
-        ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Y + (long)g1 * p.ys1), 0, ybytes, 0x00020000);
-    };
+    auto open_group = [&](int gg) { const EOperands o = e_open(p, gg, xbytes, ybytes); rx = o.x; ry = o.y; };
     // operands of reduction step s (rows 4s..4s+3) of the open group
     bool diag_first = true;
     auto load_step = [&](float (&a)[KT], float (&b)[DT], int s) {
         if (NRM_DIAG_NOLOAD == 1 && !diag_first) return;
         if (NRM_DIAG_NOLOAD == 4) s = 0;                              // same instruction stream, always the same (L1-resident) rows
-        if (!(NRM_DIAG_NOLOAD == 2 && !diag_first)) {
-            const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(rx, vx4, s * xstep, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] = __uint_as_float(va[e]);
-        }
-        if (!(NRM_DIAG_NOLOAD == 3 && !diag_first)) {
-            const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(ry, vy4, s * ystep, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b[e] = __uint_as_float(vb[e]);
-        }
-        if (KT > 4 && !(NRM_DIAG_NOLOAD == 2 && !diag_first))
-            a[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, vx1, s * xstep, 0));
-        if (DT > 4 && !(NRM_DIAG_NOLOAD == 3 && !diag_first))
-            b[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vy1, s * ystep, 0));
+        const bool lx = !(NRM_DIAG_NOLOAD == 2 && !diag_first), ly = !(NRM_DIAG_NOLOAD == 3 && !diag_first);
+        if (lx) tn_load_lo<KT>(a, rx, vx4, s * xstep);
+        if (ly) tn_load_lo<DT>(b, ry, vy4, s * ystep);
+        if (lx) tn_load_hi<KT>(a, rx, vx1, s * xstep);
+        if (ly) tn_load_hi<DT>(b, ry, vy1, s * ystep);
         if (NRM_DIAG_GELU_AT_LOAD) {
 #pragma unroll
             for (int e = 0; e < KT; ++e) a[e] = b[0] * gelu_grad_f(a[e]);       // ds * w2 * gelu'(z): one multiply stands in for the scale
@@ -619,27 +654,10 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
             }
             if (gn < g_hi) open_group(gn);
         }
-        auto mfma_batch = [&](const float (&a)[KT], const float (&b)[DT]) {
-#pragma unroll
-            for (int it = 0; it < 4; ++it)                              // fed by the two 16-byte loads
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) E[it][jt] = mfma16(a[it], b[jt], E[it][jt]);
-#pragma unroll
-            for (int it = 0; it < KT; ++it)
-#pragma unroll
-                for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) E[it][jt] = mfma16(a[it], b[jt], E[it][jt]);
-        };
+        auto mfma_batch = [&](const float (&a)[KT], const float (&b)[DT]) { e_mfma<KT, DT>(E, a, b); };
         if (!BF16) {
         if (NRM_PRIO) __builtin_amdgcn_s_setprio(NRM_PRIO);           // reduction steps above the co-resident wave's epilogue
-        // step 0 accumulates onto an inline-constant 0 (no accumulator clearing)
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) E[it][jt] = mfma16(a0[it], b0[jt], f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-        for (int it = 0; it < KT; ++it)
-#pragma unroll
-            for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) E[it][jt] = mfma16(a0[it], b0[jt], f32x4{0.f, 0.f, 0.f, 0.f});
+        e_mfma<KT, DT, true>(E, a0, b0);                              // step 0
         if (2 < nsteps) load_step(a0, b0, 2);
         if (1 < nsteps) {
             mfma_batch(a1, b1);
@@ -664,7 +682,7 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
         if (NRM_PRIO) __builtin_amdgcn_s_setprio(0);
         }
 
-        // epilogue: lane holds E[k = k0 + tile_col(it, 4q+e)][d = d0 + tile_col(jt, r16)]; the LDS image of W_p^T is
+        // epilogue: lane holds E[k = k0 + tn_col<DT>(it, 4q+e)][d = d0 + tn_col<DT>(jt, r16)]; the LDS image of W_p^T is
         // in tile-major order (tile_pos), so its rows/columns are addressed by 16*tile + lane-row as the accumulators are
         if (NRM_DIAG_NOEPI && gn < g_hi) {                           // timing diagnostic: one cheap use keeps E alive
             float keep = 0.f;
@@ -697,7 +715,7 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
                 dW[it][jt] += e4 * sr[jt];
                 if (it == KT - 1) {
                     acc = sum_rows4(acc);
-                    if (q == 0) bounce[tile_col(jt, r16)] = acc;
+                    if (q == 0) bounce[tn_col<DT>(jt, r16)] = acc;
                     acc = 0.f;
                 }
                 wa = wb; wb = wc;
@@ -728,7 +746,7 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
                 if (WITH_DW) dW[it][jt] += e4 * sr[jt];
             }
             acc = sum_rows4(acc);
-            if (q == 0) bounce[tile_col(jt, r16)] = acc;
+            if (q == 0) bounce[tn_col<DT>(jt, r16)] = acc;
         }
     };
 
@@ -759,13 +777,13 @@ __global__ __launch_bounds__(256, (MMA && KT > 4) || (MMA == 2 && WITH_DW && WIT
     }
 
     if (WITH_DW) {      // slab layout is TRANSPOSED: ws[split][d][k]
-        // lane holds dW[it][jt][e] = dW_p[k0 + tile_col(it, 4q+e)][d0 + tile_col(jt, r16)]: for one d, tiles 0..3 cover
+        // lane holds dW[it][jt][e] = dW_p[k0 + tn_col<DT>(it, 4q+e)][d0 + tn_col<DT>(jt, r16)]: for one d, tiles 0..3 cover
         // the 16 consecutive k  k0 + 16q + 4e + it  (a float4 per e, gathered across the four accumulators) and tile 4
         // the 4 consecutive k  k0 + 64 + 4q + e.
         float* wsp = p.ws + (long)split * D * D;
 #pragma unroll
         for (int jt = 0; jt < DT; ++jt) {
-            const int d = d0 + tile_col(jt, r16);
+            const int d = d0 + tn_col<DT>(jt, r16);
             if (!(EXACT || d < D)) continue;
             float* row = wsp + (long)d * D + k0;
 #pragma unroll
@@ -803,39 +821,18 @@ __global__ __launch_bounds__(256, DW_WPE) void bwd_dw_direct_kernel(const BwdEPa
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R;
-    // XCD-aware block order, as bwd_e_kernel
-    const int nblk = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
-    const int dcol = logical % p.ndcol;
-    int kw, sgrp;
-    if (p.order == 1) {
-        const int nsg = nblk / (p.ndcol * p.nkw);
-        sgrp = (logical / p.ndcol) % nsg;
-        kw = logical / (p.ndcol * nsg);
-    } else {
-        kw = (logical / p.ndcol) % p.nkw;
-        sgrp = logical / (p.ndcol * p.nkw);
-    }
-    const int d0 = dcol * (DT * 16);
-    const int k0 = kw * (KT * 16);
+    const ETile tl = e_tile<KT, DT, true>(p);
+    const int d0 = tl.d0, k0 = tl.k0, sgrp = tl.sgrp;
     const int split = sgrp * 4 + wave;
     if (split >= p.nsplit) return;
-    int g_lo = split * p.gps, g_step = 1;
-    int g_hi = min(p.G, g_lo + p.gps);
-    if (p.interleave) {
-        const int nact = min(4, p.nsplit - sgrp * 4);
-        g_lo = sgrp * 4 * p.gps + wave; g_step = nact;
-        g_hi = min(p.G, (sgrp * 4 + nact) * p.gps);
-    }
+    const EGroups gr = e_groups<true>(p, sgrp, wave);
+    const int g_lo = gr.lo, g_hi = gr.hi, g_step = gr.step;
     const int nsteps = (R + 3) >> 2;                                     // >= 2 (launcher)
 
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : OOB;
-    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : OOB;
-    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : OOB;
-    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : OOB;
+    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : BUF_OOB;
+    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : BUF_OOB;
     const unsigned xbytes = (unsigned)(((long)(R - 1) * p.xrs + D) * 4);
     const unsigned ybytes = (unsigned)(((long)(R - 1) * p.yrs + D) * 4);
     const int xstep = (int)(p.xrs * 16), ystep = (int)(p.yrs * 16);     // 4 rows, bytes
@@ -853,9 +850,8 @@ __global__ __launch_bounds__(256, DW_WPE) void bwd_dw_direct_kernel(const BwdEPa
         __amdgpu_buffer_rsrc_t rx, ry;
         int lg = g_lo, ls = 0;                                          // request pointer: (group, step); lg >= g_hi: nothing left
         auto open_group = [&](int gg) {
-            const int g1 = gg / p.G2, g2 = gg - g1 * p.G2;
-            rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2), 0, xbytes, 0x00020000);
-            ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Y + (long)g1 * p.ys1), 0, ybytes, 0x00020000);
+            const EOperands o = e_open(p, gg, xbytes, ybytes);
+            rx = o.x; ry = o.y;
             const float* srow = p.srow + (long)gg * p.lds_;
             const f32x4 s4 = *reinterpret_cast<const f32x4*>(srow + s4off);
 #pragma unroll
@@ -883,14 +879,7 @@ __global__ __launch_bounds__(256, DW_WPE) void bwd_dw_direct_kernel(const BwdEPa
             float bs[DT];
 #pragma unroll
             for (int jt = 0; jt < DT; ++jt) bs[jt] = b[jt] * sr_cur[jt];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)                              // fed by the two 16-byte loads
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) dW[it][jt] = mfma16(a[it], bs[jt], dW[it][jt]);
-#pragma unroll
-            for (int it = 0; it < KT; ++it)
-#pragma unroll
-                for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) dW[it][jt] = mfma16(a[it], bs[jt], dW[it][jt]);
+            e_mfma<KT, DT>(dW, a, bs);
             if (++cs == nsteps) cs = 0;
         };
         const int ngroups = (g_hi - g_lo + g_step - 1) / g_step;
@@ -911,7 +900,7 @@ __global__ __launch_bounds__(256, DW_WPE) void bwd_dw_direct_kernel(const BwdEPa
     float* wsp = p.ws + (long)split * D * D;
 #pragma unroll
     for (int jt = 0; jt < DT; ++jt) {
-        const int d = d0 + tile_col(jt, r16);
+        const int d = d0 + tn_col<DT>(jt, r16);
         if (!(EXACT || d < D)) continue;
         float* row = wsp + (long)d * D + k0;
 #pragma unroll
@@ -947,15 +936,8 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
     const int r16 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R;
 
-    const int nblk = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
-    const int dcol = logical % p.ndcol;
-    const int kw = (logical / p.ndcol) % p.nkw;
-    const int sgrp = logical / (p.ndcol * p.nkw);
-    const int d0 = dcol * (DT * 16);
-    const int k0 = kw * (KT * 16);
+    const ETile tl = e_tile<KT, DT, false>(p);
+    const int d0 = tl.d0, k0 = tl.k0, sgrp = tl.sgrp;
 
     for (int idx = tid; idx < KT * 16 * DT * 4; idx += 256) {
         const int kl = idx / (DT * 4), d4 = idx - kl * (DT * 4);
@@ -969,20 +951,19 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
 
     const int split = sgrp * 4 + wave;
     if (split >= p.nsplit) return;
-    const int g_lo = split * p.gps;
-    const int g_hi = min(p.G, g_lo + p.gps);
+    const EGroups gr = e_groups<false>(p, sgrp, wave);
+    const int g_lo = gr.lo, g_hi = gr.hi;
     if (g_lo >= g_hi) return;
     const int nsteps = (R + 3) >> 2;
 
-    // Lane (r16, q) of MFMA tile `it` holds local column tile_col(it, r16): tiles 0..3 interleave over the first 64
+    // Lane (r16, q) of MFMA tile `it` holds local column tn_col<DT>(it, r16): tiles 0..3 interleave over the first 64
     // columns (4*r16 + it) and tile 4 is the tail (64 + r16), so that ONE 16-byte load per lane feeds tiles 0..3 and
     // one dword load tile 4 -- 4 vector-memory instructions per reduction step instead of 10, all of them whole
     // 256-B / 64-B row segments.  Columns >= D (general shapes) get the out-of-range offset and read as 0.
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : OOB;
-    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : OOB;
-    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : OOB;
-    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : OOB;
+    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 64 + r16) * 4u : BUF_OOB;
+    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vy1 = (EXACT || d0 + 64 + r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 64 + r16) * 4u : BUF_OOB;
     const unsigned xbytes = (unsigned)(((long)(R - 1) * p.xrs + D) * 4);
     const unsigned ybytes = (unsigned)(((long)(R - 1) * p.yrs + D) * 4);
     const int xstep = (int)(p.xrs * 16), ystep = (int)(p.yrs * 16);
@@ -990,9 +971,8 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
     float a0[KT], b0[DT], a1[KT], b1[DT];
     __amdgpu_buffer_rsrc_t rx, ry, rxn, ryn;                           // current / next group
     auto open_group = [&](int gg, __amdgpu_buffer_rsrc_t& ox, __amdgpu_buffer_rsrc_t& oy) {
-        const int g1 = gg / p.G2, g2 = gg - g1 * p.G2;
-        ox = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2), 0, xbytes, 0x00020000);
-        oy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Y + (long)g1 * p.ys1), 0, ybytes, 0x00020000);
+        const EOperands o = e_open(p, gg, xbytes, ybytes);
+        ox = o.x; oy = o.y;
     };
     bool diag_first = true;
     auto load_step = [&](__amdgpu_buffer_rsrc_t dx, __amdgpu_buffer_rsrc_t dy, float (&a)[KT], float (&b)[DT], int s) {
@@ -1004,16 +984,7 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
         if (KT > 4) a[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dx, vx1, s * xstep, 0));
         if (DT > 4) b[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dy, vy1, s * ystep, 0));
     };
-    auto mfma_batch = [&](f32x4 (&E)[KT][DT], const float (&a)[KT], const float (&b)[DT]) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it)                                  // fed by the two 16-byte loads
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) E[it][jt] = mfma16(a[it], b[jt], E[it][jt]);
-#pragma unroll
-        for (int it = 0; it < KT; ++it)
-#pragma unroll
-            for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) E[it][jt] = mfma16(a[it], b[jt], E[it][jt]);
-    };
+    auto mfma_batch = [&](f32x4 (&E)[KT][DT], const float (&a)[KT], const float (&b)[DT]) { e_mfma<KT, DT>(E, a, b); };
     // epilogue slice: d tile jt of a finished accumulator set -> bounce[16*jt .. 16*jt+15]
     auto slice = [&](const f32x4 (&E)[KT][DT], int jt) {
         const int dl = 16 * jt + r16;
@@ -1027,7 +998,7 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
             acc = fmaf(w4[it][0], e4[0], fmaf(w4[it][1], e4[1], fmaf(w4[it][2], e4[2], fmaf(w4[it][3], e4[3], acc))));
         }
         acc = sum_rows4(acc);
-        if (q == 0) bounce[tile_col(jt, r16)] = acc;
+        if (q == 0) bounce[tn_col<DT>(jt, r16)] = acc;
     };
     auto flush = [&](int grow) {
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
@@ -1049,14 +1020,7 @@ __global__ __launch_bounds__(256, 2) void bwd_e_pipe_kernel(const BwdEParams p) 
 #pragma unroll
         for (int s = 0; s < PE; ++s) {                                  // nsteps >= PE + 2: loads stay in group g
             if (s == 0 && !NRM_DIAG_NOEPI) {                            // C = inline 0: no accumulator clearing
-#pragma unroll
-                for (int it = 0; it < 4; ++it)
-#pragma unroll
-                    for (int jt = 0; jt < 4; ++jt) Ec[it][jt] = mfma16(a0[it], b0[jt], f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-                for (int it = 0; it < KT; ++it)
-#pragma unroll
-                    for (int jt = (it < 4 ? 4 : 0); jt < DT; ++jt) Ec[it][jt] = mfma16(a0[it], b0[jt], f32x4{0.f, 0.f, 0.f, 0.f});
+                e_mfma<KT, DT, true>(Ec, a0, b0);
                 load_step(rx, ry, a0, b0, 2);
             }
             else if (s & 1) { mfma_batch(Ec, a1, b1); load_step(rx, ry, a1, b1, s + 2); }
@@ -1137,21 +1101,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dw_r32_kernel(const BwdEParams p) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R;
-    const int nblk = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xq = nblk >> 3, xr_ = nblk & 7, xcd = lin & 7;
-    const int logical = (xcd < xr_ ? xcd * (xq + 1) : xr_ * (xq + 1) + (xcd - xr_) * xq) + (lin >> 3);
-    const int dcol = logical % p.ndcol;
-    const int kw = (logical / p.ndcol) % p.nkw;
-    const int sgrp = logical / (p.ndcol * p.nkw);
-    const int d0 = dcol * 64, k0 = kw * 64;
+    const ETile tl = e_tile<KT, DT, false>(p);
+    const int d0 = tl.d0, k0 = tl.k0, sgrp = tl.sgrp;
     const int split = sgrp * 4 + wave;
     if (split >= p.nsplit) return;
-    const int g_lo = split * p.gps, g_hi = min(p.G, g_lo + p.gps);
+    const EGroups gr = e_groups<false>(p, sgrp, wave);
+    const int g_lo = gr.lo, g_hi = gr.hi;
 
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : OOB;
-    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : OOB;
+    const unsigned vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)((long)q * p.xrs + k0 + 4 * r16) * 4u : BUF_OOB;
+    const unsigned vy4 = (EXACT || d0 + 4 * r16 < D) ? (unsigned)((long)q * p.yrs + d0 + 4 * r16) * 4u : BUF_OOB;
     const unsigned xbytes = (unsigned)(((long)(R - 1) * p.xrs + D) * 4);
     const unsigned ybytes = (unsigned)(((long)(R - 1) * p.yrs + D) * 4);
     const int xstep = (int)(p.xrs * 16), ystep = (int)(p.yrs * 16);     // 4 rows, bytes
@@ -1165,8 +1123,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dw_r32_kernel(const BwdEParams p) 
     // reduction position (lane quarter q, element j) is row 4 j + q of the group, for both operands
     u32x4 xraw[8];
     auto load_x = [&](int g) {
-        const int g1 = g / p.G2, g2 = g - g1 * p.G2;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2), 0, xbytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = e_open(p, g, xbytes, ybytes).x;
 #pragma unroll
         for (int j = 0; j < 8; ++j) xraw[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, vx4, j * xstep, 0);
     };
@@ -1177,7 +1134,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dw_r32_kernel(const BwdEParams p) 
         const int g1 = g / p.G2;
         if (g1 != y_g1) {                                                // a new impression: its history rows, split once
             y_g1 = g1;
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Y + (long)g1 * p.ys1), 0, ybytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ry = e_open(p, g, xbytes, ybytes).y;
             f32x4 yraw[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) yraw[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, vy4, j * ystep, 0));

@@ -116,10 +116,9 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
     const int s_lo = (int)(S * g / G), s_hi = (int)(S * (g + 1) / G);
     if (s_lo >= s_hi) return;
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wimg), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t), 0, p.t_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wimg, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t, p.t_bytes);
     const int rslot = 4 * (q ^ swz4(c16));
     const int zstep = H * D * 4;                                          // bytes between candidates of one impression in dz
 
@@ -127,9 +126,9 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
     int rb = -1, nc = -1, colbase = 0;
     unsigned live = 0;                                                    // bit it: tile it holds columns < D
     __amdgpu_buffer_rsrc_t rs_z = rs_w;                                   // dz, based at the first impression of the row block
-    unsigned voff_z = OOB;                                                // DMA: this lane's row (lane >> 2) and 16-byte slot
+    unsigned voff_z = BUF_OOB;                                                // DMA: this lane's row (lane >> 2) and 16-byte slot
     unsigned voff_h4[4], voff_h1[4];                                      // multiplier rows 4q + r: 16-byte units / single columns
-    unsigned voff_tA4 = OOB, voff_tB4 = OOB, voff_tA1 = OOB, voff_tB1 = OOB;
+    unsigned voff_tA4 = BUF_OOB, voff_tB4 = BUF_OOB, voff_tA1 = BUF_OOB, voff_tB1 = BUF_OOB;
     bool isB[4];
     bool has_b = false;                                                   // (uniform) the wave's 16 rows reach into a second impression
     int b_lo = 0;                                                         // (uniform) impression of the wave's first row
@@ -148,13 +147,13 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
         const int b_first = r0 / H;
         const size_t imp = (size_t)T * H * D;                             // floats of one impression's dz block
         const int span = min(p.B - b_first, (BM - 1) / H + 2);
-        rs_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dz) + (size_t)b_first * imp, 0, (unsigned)(span * imp * 4), 0x00020000);
+        rs_z = buffer_rsrc(p.dz + (size_t)b_first * imp, (unsigned)(span * imp * 4));
         {   // DMA lane: row rl of the wave's 16 rows
             const int rl = lane >> 2;
             const int r = r0 + wave * 16 + rl;
             const int b = r / H, hh = r - b * H;
             const unsigned slot = (unsigned)((lane & 3) ^ swz4(rl));
-            voff_z = r < R ? (unsigned)(((size_t)(b - b_first) * T * H + hh) * D + 4 * slot) * 4u : OOB;
+            voff_z = r < R ? (unsigned)(((size_t)(b - b_first) * T * H + hh) * D + 4 * slot) * 4u : BUF_OOB;
         }
         const int rw0 = r0 + wave * 16;                                   // uniform
         b_lo = rw0 / H;
@@ -164,13 +163,13 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
         for (int r = 0; r < 4; ++r) {
             const int rr = rw0 + 4 * q + r;
             isB[r] = rr >= (b_lo + 1) * H;
-            voff_h4[r] = rr < R ? (unsigned)(rr * D + 4 * c16) * 4u : OOB;
-            voff_h1[r] = rr < R ? (unsigned)(rr * D + c16) * 4u : OOB;
+            voff_h4[r] = rr < R ? (unsigned)(rr * D + 4 * c16) * 4u : BUF_OOB;
+            voff_h1[r] = rr < R ? (unsigned)(rr * D + c16) * 4u : BUF_OOB;
         }
-        voff_tA4 = rw0 < R ? (unsigned)(b_lo * T * D + 4 * c16) * 4u : OOB;
-        voff_tA1 = rw0 < R ? (unsigned)(b_lo * T * D + c16) * 4u : OOB;
-        voff_tB4 = has_b ? voff_tA4 + (unsigned)(T * D * 4) : OOB;
-        voff_tB1 = has_b ? voff_tA1 + (unsigned)(T * D * 4) : OOB;
+        voff_tA4 = rw0 < R ? (unsigned)(b_lo * T * D + 4 * c16) * 4u : BUF_OOB;
+        voff_tA1 = rw0 < R ? (unsigned)(b_lo * T * D + c16) * 4u : BUF_OOB;
+        voff_tB4 = has_b ? voff_tA4 + (unsigned)(T * D * 4) : BUF_OOB;
+        voff_tB1 = has_b ? voff_tA1 + (unsigned)(T * D * 4) : BUF_OOB;
 #pragma unroll
         for (int it = 0; it < NT; ++it) dhacc[it] = f32x4{0.f, 0.f, 0.f, 0.f};
     };
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
             const int dl = 64 * gg + 4 * c16 + q;
             const bool dok = colbase + dl < D;
             const float vA = rs4(xA);
-            if (dok && voff_tA4 != OOB) atomicAdd(dtA + dl, vA);
+            if (dok && voff_tA4 != BUF_OOB) atomicAdd(dtA + dl, vA);
             if (has_b) {
                 const float vB = rs4(xB);
                 if (dok) atomicAdd(dtB + dl, vB);
@@ -337,7 +336,7 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
             const int dl = 64 * NG4 + 16 * i + c16;
             const bool dok = colbase + dl < D && q == 0;
             const float vA = sum_rows4(sa);
-            if (dok && voff_tA4 != OOB) atomicAdd(dtA + dl, vA);
+            if (dok && voff_tA4 != BUF_OOB) atomicAdd(dtA + dl, vA);
             if (has_b) {
                 const float vB = sum_rows4(sb);
                 if (dok) atomicAdd(dtB + dl, vB);

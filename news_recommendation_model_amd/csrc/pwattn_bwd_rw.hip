@@ -118,8 +118,7 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
     const int c0 = ks * KC;                                              // first reduction chunk of the slice
     const int kc_here = EXACT ? KC : min(KC, pl.k32 - c0);
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wimg), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wimg, p.w_bytes);
 
     // ---- once per workgroup: the slice's image -> LDS in 1-KiB pieces of 16 rows, then ONE barrier
     const int npiece = kc_here * WIMG * (ROWS / 16);
@@ -146,25 +145,22 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
         const int g_base = gsel * NG;
         const int t_lo = tp * tlen, t_hi = min(T, t_lo + tlen);
         if (t_lo >= t_hi) continue;
-        const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.dz) + (size_t)b * T * H * D, 0, (unsigned)((size_t)T * H * D * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.t) + (size_t)b * T * D, 0, (unsigned)(T * D * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.h) + (size_t)b * H * D, 0, (unsigned)(H * D * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(p.dz + (size_t)b * T * H * D, (unsigned)((size_t)T * H * D * 4));
+        const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t + (size_t)b * T * D, (unsigned)(T * D * 4));
+        const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h + (size_t)b * H * D, (unsigned)(H * D * 4));
 
         // this lane's dz row (h0 + r16) and its 8 reduction positions k = 32c + 8q + {0..7}: two hl4 units per chunk.
         // Units at k >= D (ragged last chunk) are masked: the bytes behind a row's end belong to the next row.
         const bool rok = h0 + r16 < H;
         const int zrow = ((h0 + r16) * D + 32 * c0 + 8 * q) * 4;        // byte offset inside candidate 0; + t * H*D*4 per step
         unsigned vz0[KC], vz1[KC];
-        const unsigned vzx = rok ? (unsigned)zrow : OOB;
+        const unsigned vzx = rok ? (unsigned)zrow : BUF_OOB;
         if (!EXACT) {
 #pragma unroll
             for (int cl = 0; cl < KC; ++cl) {
                 const int k = 32 * (c0 + cl) + 8 * q;
-                vz0[cl] = (rok && cl < kc_here && k < D) ? (unsigned)(zrow + cl * 128) : OOB;
-                vz1[cl] = (rok && cl < kc_here && k + 4 < D) ? (unsigned)(zrow + cl * 128 + 16) : OOB;
+                vz0[cl] = (rok && cl < kc_here && k < D) ? (unsigned)(zrow + cl * 128) : BUF_OOB;
+                vz1[cl] = (rok && cl < kc_here && k + 4 < D) ? (unsigned)(zrow + cl * 128 + 16) : BUF_OOB;
             }
         }
         const int zstep = H * D * 4;
@@ -179,7 +175,7 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
             for (int r = 0; r < 4; ++r) {
                 const bool ok = h0 + 4 * q + r < H && dbase + 64 * g < D;
                 hreg[g][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    rs_h, ok ? (unsigned)(((h0 + 4 * q + r) * D + dbase + 64 * g) * 4) : OOB, 0, 0));
+                    rs_h, ok ? (unsigned)(((h0 + 4 * q + r) * D + dbase + 64 * g) * 4) : BUF_OOB, 0, 0));
             }
 
         f32x4 dhacc[NT];
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
 #pragma unroll
             for (int g = 0; g < NG; ++g)
                 t4s[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    rs_t, dbase + 64 * g < D ? (unsigned)((dbase + 64 * g) * 4) : OOB, t * D * 4, 0));
+                    rs_t, dbase + 64 * g < D ? (unsigned)((dbase + 64 * g) * 4) : BUF_OOB, t * D * 4, 0));
             f32x4 acc[NT];
 #pragma unroll
             for (int it = 0; it < NT; ++it) acc[it] = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -88,8 +88,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
     // consecutive ROW TILES share their impression's h / u rows and their candidate's t / v row, so give each XCD a
     // contiguous range of tiles (bijective for any grid size) instead of every eighth one.
     const int nblk = gridDim.x, lin = blockIdx.x;
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = lin & 7;
-    const int tile_id = XCD_REMAP ? (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3) : lin;
+    const int tile_id = XCD_REMAP ? xcd_logical_block(lin, nblk) : lin;
     const int m0 = tile_id * BM;
     const int T = p.T, H = p.H, D = p.D;
     const int rows_here = min(BM, M - m0);
@@ -105,15 +104,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
     // All global traffic goes through buffer descriptors: 32-bit lane offsets (no 64-bit pointers to keep
     // live or spill) and hardware bounds checking -- an offset >= num_records reads 0 / drops the store,
     // which is how out-of-range rows (m >= M) are masked.
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, p.wp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t), 0, p.t_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v), 0, p.t_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, D * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-        SAVE_Z ? p.z + (size_t)m0 * D : nullptr, 0, SAVE_Z ? rows_here * D * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wp, p.wp_bytes);
+    const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t rs_u = buffer_rsrc(p.u, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(p.v, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w2 = buffer_rsrc(p.w2, D * 4);
+    const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(SAVE_Z ? p.z + (size_t)m0 * D : nullptr, SAVE_Z ? rows_here * D * 4 : 0);
 
     // --- staging (LDS-DMA): a wave copies its OWN MT*16 t rows and h rows (one 1-KiB piece = 16 rows x 64 B
     // per wave-instruction, lane -> row lane>>2, 16-B slot lane&3) and every 4th 1-KiB piece of the W chunk.
@@ -128,14 +125,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
         if constexpr (HRAG) {
             unsigned bt, hr;
             const bool ok = hrow((int)mm, bt, hr) && m < M;
-            voff_t[j] = (!CT && ok) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
-            voff_h[j] = ok ? (hr * p.ldh + 4 * slot) * 4u : OOB;
+            voff_t[j] = (!CT && ok) ? (bt * p.ldt + 4 * slot) * 4u : BUF_OOB;
+            voff_h[j] = ok ? (hr * p.ldh + 4 * slot) * 4u : BUF_OOB;
         } else {
             const unsigned bt = mm / (unsigned)H;
             const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
             const unsigned hr = b * H + (mm - bt * H);
-            voff_t[j] = (!CT && m < M) ? (bt * p.ldt + 4 * slot) * 4u : OOB;
-            voff_h[j] = m < M ? (hr * p.ldh + 4 * slot) * 4u : OOB;
+            voff_t[j] = (!CT && m < M) ? (bt * p.ldt + 4 * slot) * 4u : BUF_OOB;
+            voff_h[j] = m < M ? (hr * p.ldh + 4 * slot) * 4u : BUF_OOB;
         }
     }
     // CT: image row r (lane >> 2) holds candidate bt0 + r while that candidate has rows in this block (slots swizzled as in every
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
         bt0 = (unsigned)m0 / (unsigned)H;
         bt_last = (unsigned)(m0 + rows_here - 1) / (unsigned)H;
     }
-    const unsigned voff_tc = (CT && bt0 + (unsigned)(lane >> 2) <= bt_last) ? ((bt0 + (unsigned)(lane >> 2)) * p.ldt + 4u * (unsigned)((lane & 3) ^ swz4(lane >> 2))) * 4u : OOB;
+    const unsigned voff_tc = (CT && bt0 + (unsigned)(lane >> 2) <= bt_last) ? ((bt0 + (unsigned)(lane >> 2)) * p.ldt + 4u * (unsigned)((lane & 3) ^ swz4(lane >> 2))) * 4u : BUF_OOB;
     int tfrag[MT];
 #pragma unroll
     for (int jt = 0; jt < MT; ++jt) {
@@ -167,14 +164,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
             unsigned bt, hr;
             const bool ok = hrow((int)mm, bt, hr) && m < M;
             row_ok[jt] = ok;
-            voff_u[jt] = ok ? (hr * p.ldu + 4 * q) * 4u : OOB;
-            voff_v[jt] = ok ? (bt * p.ldv + 4 * q) * 4u : OOB;
+            voff_u[jt] = ok ? (hr * p.ldu + 4 * q) * 4u : BUF_OOB;
+            voff_v[jt] = ok ? (bt * p.ldv + 4 * q) * 4u : BUF_OOB;
         } else {
             const unsigned bt = mm / (unsigned)H;
             const unsigned b = RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T;
             const unsigned hr = b * H + (mm - bt * H);
-            voff_u[jt] = m < M ? (hr * p.ldu + 4 * q) * 4u : OOB;
-            voff_v[jt] = m < M ? (bt * p.ldv + 4 * q) * 4u : OOB;
+            voff_u[jt] = m < M ? (hr * p.ldu + 4 * q) * 4u : BUF_OOB;
+            voff_v[jt] = m < M ? (bt * p.ldv + 4 * q) * 4u : BUF_OOB;
         }
     }
     const int rslot = 4 * (q ^ swz4(r16));          // swizzled float offset of this lane's fragment slot

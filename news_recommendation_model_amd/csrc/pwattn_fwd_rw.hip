@@ -112,13 +112,12 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
     const int k0 = split * SROWS;                                       // first output column of the slice
     const int K = pl.k32;
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, p.wp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t), 0, p.t_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v), 0, p.t_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, D * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wp, p.wp_bytes);
+    const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t rs_u = buffer_rsrc(p.u, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(p.v, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w2 = buffer_rsrc(p.w2, D * 4);
 
     // ---- once per workgroup: the slice's W_p image -> LDS (1-KiB pieces of 16 rows), then ONE barrier
     const int npiece = K * WIMG * NTS;
@@ -151,10 +150,10 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
             bt = mm / (unsigned)H;
             hr = (RAGGED ? (unsigned)min(max(rg.cand_imp[bt], 0), rg.B - 1) : bt / (unsigned)T) * H + (mm - bt * H);
         }
-        const unsigned voff_t = ok ? (bt * p.ldt + 4 * q) * 4u : OOB;
-        const unsigned voff_h = ok ? (hr * p.ldh + 4 * q) * 4u : OOB;
-        const unsigned voff_u = ok ? (hr * p.ldu + 4 * q) * 4u : OOB;
-        const unsigned voff_v = ok ? (bt * p.ldv + 4 * q) * 4u : OOB;
+        const unsigned voff_t = ok ? (bt * p.ldt + 4 * q) * 4u : BUF_OOB;
+        const unsigned voff_h = ok ? (hr * p.ldh + 4 * q) * 4u : BUF_OOB;
+        const unsigned voff_u = ok ? (hr * p.ldu + 4 * q) * 4u : BUF_OOB;
+        const unsigned voff_v = ok ? (bt * p.ldv + 4 * q) * 4u : BUF_OOB;
 
         f32x4 ta[3], tb[3], ha[3], hb[3];                              // three chunk sets of this lane's operand columns (requested two chunks ahead)
         auto load_th = [&](int c, int set) {
@@ -164,8 +163,8 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
             unsigned vt = voff_t, vh = voff_h, vt2 = voff_t, vh2 = voff_h;
             if (ragged) {
                 const int col = (CB / 4) * c + 4 * q;
-                if (col >= D) vt = vh = OOB;
-                if (col + 16 >= D) vt2 = vh2 = OOB;
+                if (col >= D) vt = vh = BUF_OOB;
+                if (col + 16 >= D) vt2 = vh2 = BUF_OOB;
             }
             ta[set] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_t, vt, c * CB, 0));
             ha[set] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_h, vh, c * CB, 0));
@@ -240,8 +239,7 @@ __global__ __launch_bounds__(FB_WAVES * 64, FB_WAVES / 4) void pwattn_fwd_rw_ker
 
         // ---- epilogue: optional z store ; GELU ; partial fc2 dot over the slice's columns
         const int rows_here = min(16, M - tile * 16);
-        const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-            SAVE_Z ? p.z + (size_t)tile * 16 * D : nullptr, 0, SAVE_Z ? rows_here * D * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(SAVE_Z ? p.z + (size_t)tile * 16 * D : nullptr, SAVE_Z ? rows_here * D * 4 : 0);
         // fc2 weights of the slice's columns (0 beyond D; L1-resident): requested together, one round trip
         f32x4 ww[NTS];
 #pragma unroll
@@ -290,9 +288,8 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_kernel(const FwdParams
     const int split = blockIdx.x % pl.nsplit, g = blockIdx.x / pl.nsplit;
     const int k0 = split * SROWS;
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, p.wp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, D * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wp, p.wp_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w2 = buffer_rsrc(p.w2, D * 4);
     const int npiece = KCH * WIMG * NTS;
     for (int pc = wave; pc < npiece; pc += NW) {
         const int ci = pc / NTS, rt = pc - ci * NTS;
@@ -314,17 +311,16 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_kernel(const FwdParams
         const int t_lo = tp * tlen, t_hi = min(T, t_lo + tlen);
         if (t_lo >= t_hi) continue;
         const bool rok = h0 + r16 < H;
-        const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t) + (size_t)b * T * p.ldt, 0, (unsigned)(T * p.ldt * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v) + (size_t)b * T * p.ldv, 0, (unsigned)(T * p.ldv * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h) + (size_t)b * H * p.ldh, 0, (unsigned)(H * p.ldh * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u) + (size_t)b * H * p.ldu, 0, (unsigned)(H * p.ldu * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-            SAVE_Z ? p.z + (size_t)b * T * H * D : nullptr, 0, SAVE_Z ? (unsigned)((size_t)T * H * D * 4) : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t + (size_t)b * T * p.ldt, (unsigned)(T * p.ldt * 4));
+        const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(p.v + (size_t)b * T * p.ldv, (unsigned)(T * p.ldv * 4));
+        const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h + (size_t)b * H * p.ldh, (unsigned)(H * p.ldh * 4));
+        const __amdgpu_buffer_rsrc_t rs_u = buffer_rsrc(p.u + (size_t)b * H * p.ldu, (unsigned)(H * p.ldu * 4));
+        const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(SAVE_Z ? p.z + (size_t)b * T * H * D : nullptr, SAVE_Z ? (unsigned)((size_t)T * H * D * 4) : 0);
 
         // ---- once per task: this lane's h row (its 8 reduction columns of every chunk) and u row (its 4 columns of every tile)
         f32x4 ha[KCH], hb[KCH], ureg[NTS];
-        const unsigned vh = rok ? (unsigned)(((h0 + r16) * p.ldh + 4 * q) * 4) : OOB;
-        const unsigned vu = rok ? (unsigned)(((h0 + r16) * p.ldu + k0 + 4 * q) * 4) : OOB;
+        const unsigned vh = rok ? (unsigned)(((h0 + r16) * p.ldh + 4 * q) * 4) : BUF_OOB;
+        const unsigned vu = rok ? (unsigned)(((h0 + r16) * p.ldu + k0 + 4 * q) * 4) : BUF_OOB;
 #pragma unroll
         for (int c = 0; c < KCH; ++c) {
             ha[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_h, vh, c * 128, 0));
@@ -344,7 +340,7 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_kernel(const FwdParams
         load_t(0, t_lo, 0);
         load_t(1, t_lo, 1);
         const unsigned vv_off = (unsigned)((k0 + 4 * q) * 4);
-        const unsigned vz = rok ? (unsigned)(((h0 + r16) * D + k0 + 4 * q) * 4) : OOB;
+        const unsigned vz = rok ? (unsigned)(((h0 + r16) * D + k0 + 4 * q) * 4) : BUF_OOB;
 
         for (int t = t_lo; t < t_hi; ++t) {
             f32x4 acc[NTS];
@@ -439,9 +435,8 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
     const int r16 = lane & 15, q = lane >> 4;
     const int T = p.T, H = p.H, D = p.D;
 
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, p.wp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, D * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.wp, p.wp_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w2 = buffer_rsrc(p.w2, D * 4);
     for (int pc = wave; pc < KCH * NTS; pc += NW) {
         const int c = pc / NTS, rt = pc - c * NTS;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(wres + pc * 256), 16, lane * 16,
@@ -484,17 +479,16 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
         const int ntl = (hk + 15) >> 4;                                 // (HRAG) tiles per candidate of this impression
         const bool rok = h0 + r16 < hk;
         const size_t trow = RAGGED ? (size_t)cbase : (size_t)b * T;    // first candidate row of the task's impression
-        const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t) + trow * p.ldt, 0, (unsigned)(cnt * p.ldt * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.v) + trow * p.ldv, 0, (unsigned)(cnt * p.ldv * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.h) + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldh, 0, (unsigned)(hk * p.ldh * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u) + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldu, 0, (unsigned)(hk * p.ldu * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(
-            SAVE_Z ? p.z + (size_t)b * T * H * D : nullptr, 0, SAVE_Z ? (unsigned)((size_t)T * H * D * 4) : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_t = buffer_rsrc(p.t + trow * p.ldt, (unsigned)(cnt * p.ldt * 4));
+        const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(p.v + trow * p.ldv, (unsigned)(cnt * p.ldv * 4));
+        const __amdgpu_buffer_rsrc_t rs_h = buffer_rsrc(p.h + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldh, (unsigned)(hk * p.ldh * 4));
+        const __amdgpu_buffer_rsrc_t rs_u = buffer_rsrc(p.u + (HRAG ? (size_t)hbase : (size_t)b * H) * p.ldu, (unsigned)(hk * p.ldu * 4));
+        const __amdgpu_buffer_rsrc_t rs_z = buffer_rsrc(SAVE_Z ? p.z + (size_t)b * T * H * D : nullptr, SAVE_Z ? (unsigned)((size_t)T * H * D * 4) : 0);
 
         // once per task: this lane's h row (its 4 reduction columns of every chunk) and u row (its 4 columns of every tile)
         f32x4 hreg[KCH], ureg[NTS];
-        const unsigned vh = rok ? (unsigned)(((h0 + r16) * p.ldh + 4 * q) * 4) : OOB;
-        const unsigned vu = rok ? (unsigned)(((h0 + r16) * p.ldu + 4 * q) * 4) : OOB;
+        const unsigned vh = rok ? (unsigned)(((h0 + r16) * p.ldh + 4 * q) * 4) : BUF_OOB;
+        const unsigned vu = rok ? (unsigned)(((h0 + r16) * p.ldu + 4 * q) * 4) : BUF_OOB;
 #pragma unroll
         for (int c = 0; c < KCH; ++c) hreg[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_h, vh, c * 64, 0));
 #pragma unroll
@@ -509,7 +503,7 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
         load_t(0, t_lo, 0);
         load_t(1, t_lo, 1);
         const unsigned vv_off = (unsigned)(4 * q * 4);
-        const unsigned vz = rok ? (unsigned)(((h0 + r16) * D + 4 * q) * 4) : OOB;
+        const unsigned vz = rok ? (unsigned)(((h0 + r16) * D + 4 * q) * 4) : BUF_OOB;
 
         for (int t = t_lo; t < t_hi; ++t) {
             f32x4 acc[NTS];

@@ -87,7 +87,12 @@ SHAPES = [
 ]
 
 
-@pytest.mark.parametrize("B,T,H,D", SHAPES)
+# the pipelined dh kernel (T >= 21 on 4x4 tiles, T >= 29 on 5x5) at widths that fill no whole wave tile, with a group count that is no
+# multiple of 4 (a last workgroup with fewer than four live waves): the two instantiations no other shape of this file reaches
+PIPE_RAGGED_SHAPES = [(3, 21, 5, 100), (3, 29, 7, 72)]
+
+
+@pytest.mark.parametrize("B,T,H,D", SHAPES + PIPE_RAGGED_SHAPES)
 def test_scores_and_grads_match_oracle(lib, B, T, H, D):
     rng = np.random.default_rng(B * 1000 + T * 100 + H * 10 + D)
     w = _weights(rng, D)
@@ -307,7 +312,11 @@ BF16_SHAPES = [
 ]
 
 
-@pytest.mark.parametrize("B,T,H,D", BF16_SHAPES)
+# an exact width above 256 (no resident-W backward there) with 21 groups: the bf16 arithmetics on the EXACT serial contraction, both passes
+BF16_E_EXACT_SHAPES = [(3, 7, 5, 320)]
+
+
+@pytest.mark.parametrize("B,T,H,D", BF16_SHAPES + BF16_E_EXACT_SHAPES)
 @pytest.mark.parametrize("mma", ["bf16x3", "bf16"])
 def test_bf16_mfma_scores_and_grads_match_fp32_oracle(lib, mma, B, T, H, D):
     """bf16x3 (hi/lo split operands, three MFMAs per product) must meet the fp32 gates with a wide margin: it is the

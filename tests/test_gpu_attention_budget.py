@@ -85,7 +85,8 @@ def test_attend_and_pool_within_budget(lib, monkeypatch, family, mma, B, T, H, D
     _judge(ab.get_case((B, T, H, D), family, pool=True), mma, "default")
 
 
-@pytest.mark.parametrize("B,T,H,D", [(2, 30, 50, 400), (3, 7, 19, 72), (2, 15, 200, 64)])
+# (3, 7, 5, 320): an exact width above 256 -- bf16x3 takes the EXACT serial contraction for dW_p alone, from fp32 dz
+@pytest.mark.parametrize("B,T,H,D", [(2, 30, 50, 400), (3, 7, 19, 72), (2, 15, 200, 64), (3, 7, 5, 320)])
 @pytest.mark.parametrize("mma,direct", [("f32", "0"), ("f32", "1"), ("bf16x3", None)])
 def test_weight_only_backward_within_budget(lib, monkeypatch, mma, direct, B, T, H, D):
     """t and h without requires_grad (the text+image attention's path): no row gradients are formed, every weight piece is judged.

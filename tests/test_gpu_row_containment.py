@@ -146,14 +146,19 @@ def test_attention_f32_keeps_rows_apart(lib, monkeypatch, form, B, T, H, D):
     _attn_case("scores", "f32", B, T, H, D)
 
 
-@pytest.mark.parametrize("B,T,H,D", [(3, 3, 20, 72), (3, 2, 17, 388), (3, 2, 20, 400), (3, 2, 20, 64)])
+# plain bf16 above D = 256 (no resident-W backward): the serial contraction for dW_p alone from fp32 dz, ragged and exact width
+WEIGHT_ONLY_CASES = [(3, 3, 20, 72, "f32"), (3, 2, 17, 388, "f32"), (3, 2, 20, 400, "f32"), (3, 2, 20, 64, "f32"),
+                     (3, 2, 17, 388, "bf16"), (3, 2, 20, 320, "bf16")]
+
+
+@pytest.mark.parametrize("B,T,H,D,mma", WEIGHT_ONLY_CASES, ids=["-".join(map(str, c[:4] if c[4] == "f32" else c)) for c in WEIGHT_ONLY_CASES])
 @pytest.mark.parametrize("direct", ["0", "1"])
 @pytest.mark.parametrize("interleave", ["0", "1"])
-def test_attention_weight_only_backward_keeps_rows_apart(lib, monkeypatch, direct, interleave, B, T, H, D):
+def test_attention_weight_only_backward_keeps_rows_apart(lib, monkeypatch, direct, interleave, B, T, H, D, mma):
     """The text+image attention's backward (no row gradients): the direct dW_p pass and the E-form, both group walks."""
     monkeypatch.setenv("NRM_DW_DIRECT", direct)
     monkeypatch.setenv("NRM_BT_INTERLEAVE", interleave)
-    _attn_case("scores", "f32", B, T, H, D, rowgrads=False)
+    _attn_case("scores", mma, B, T, H, D, rowgrads=False)
 
 
 @pytest.mark.parametrize("B,T,H,D", [(3, 3, 20, 72), (3, 2, 20, 64), (3, 2, 17, 128), (3, 2, 16, 256), (3, 2, 17, 388), (3, 2, 20, 400),
