@@ -98,6 +98,11 @@ int nrm_pwattn_bwd_contract(const float* dz, const float* t, const float* h, con
  *   bit 2     EXACT (D fills whole wave tiles: no column guards)       bit 3  wave tile 5x5 (clear: 4x4)
  *   bit 4     the pass writes dW_p slabs     bit 5  it forms a row gradient (dt or dh)     bit 6  it reads NRM_DZ_HL4 */
 int nrm_pwattn_bwd_form(int T, int H, int D, int pass, int mma, int dz_format);
+/* How many consecutive (b,t) groups the fp32 dW_p-only launch (passes = 4, NRM_DZ_F32) of nrm_pwattn_bwd_contract reduces together
+ * in whole 4-row steps (additive entry point, the ABI version is unchanged; no device call, the environment knobs applied -- NRM_DW_PACK=0
+ * keeps every group on its own).  1: per group, its last step padded -- H % 4 == 0, splits shorter than a super-group, every launch that
+ * is not the one-accumulator kernel; 2 for H = 2 mod 4, 4 for odd H.  Depends on B through the groups per split.  -1: bad arguments. */
+int nrm_pwattn_bwd_dw_pack(int B, int T, int H, int D, int mma);
 /* backward, step 2 in the "resident W_p" form (bf16 arithmetics, D <= 256): the same dt / dh as above from ONE contraction
  * dP = dz W_p whose W_p image stays in LDS and whose dz operand (NRM_DZ_HL4) is read exactly once; autograd of
  * models/attention_model.py:81-92 w.r.t. target and history.  nrm_pwattn_bwd_rw_supported: 1 if (D, mma) has this form;

@@ -297,6 +297,13 @@ int nrm_pwattn_bwd_form(int T, int H, int D, int pass, int mma, int dz_format) {
     return f.family | (f.exact ? 4 : 0) | (a.pl.DT == 5 ? 8 : 0) | (f.with_dw ? 16 : 0) | (f.with_dt ? 32 : 0) | (f.xhl4 ? 64 : 0);
 }
 
+int nrm_pwattn_bwd_dw_pack(int B, int T, int H, int D, int mma) {
+    if (B <= 0 || check_dims("nrm_pwattn_bwd_dw_pack", B, T, H, D) || check_mma("nrm_pwattn_bwd_dw_pack", mma)) return -1;
+    const BwdPass a = bwd_pass(4, nullptr, nullptr, nullptr, nullptr, D, nullptr, nullptr, nullptr, B, T, H, D, mma, NRM_DZ_F32);
+    const nrm::BwdEForm f = nrm::bwd_e_select(a.p, a.pl, a.with_dw, mma, nrm::bwd_e_knobs());
+    return f.family == nrm::BWD_DW_DIRECT ? f.pack : 1;
+}
+
 // ------------------------------------------------------------------------------------------- dense layers
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 

@@ -78,12 +78,13 @@ struct BwdEPlan { int DT, KT, ndcol, nkw, nsplit, gps; };
 BwdEPlan bwd_e_plan(int D, int G, int target_waves, int min_gps = 1, int mma = 0);
 // Which contraction kernel a launch takes: chosen by bwd_e_select (host arithmetic only, no HIP call), launched by bwd_e_launch
 enum BwdEFamily { BWD_E_REFUSED = -1, BWD_E_SERIAL = 0, BWD_E_PIPE = 1, BWD_DW_DIRECT = 2, BWD_DW_R32 = 3 };
-struct BwdEKnobs { bool pipe, dw_direct, dw_r32; };       // NRM_BH_PIPE, NRM_DW_DIRECT, NRM_DW_R32: each on unless set to 0
+struct BwdEKnobs { bool pipe, dw_direct, dw_r32, dw_pack; };   // NRM_BH_PIPE, NRM_DW_DIRECT, NRM_DW_R32, NRM_DW_PACK: each on unless set to 0
 BwdEKnobs bwd_e_knobs();                                  // the environment as it is NOW (every launch asks again)
 struct BwdEForm {
     int family;                                           // BwdEFamily; BWD_E_REFUSED: a combination the kernels cannot express
     bool with_dw, with_dt, xhl4; int ks;                  // what the pass forms and reads (bwd_e_kernel's WITH_DW, WITH_DT, XHL4, KS)
     bool exact; int mma;                                  // EXACT: D fills whole wave tiles; MMA: 0 fp32, 1 bf16, 2 bf16x3
+    int pack = 1;                                         // BWD_DW_DIRECT: groups reduced together in whole steps (bwd_dw_pack_kernel); 1: per group
 };
 BwdEForm bwd_e_select(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, const BwdEKnobs& knobs);
 hipError_t bwd_e_launch(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, hipStream_t st);

@@ -414,12 +414,13 @@ hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2,
 // (the column of (tile, lane-row) is tn_col<5>, or tn_col<4> on 64-wide tiles: tn_tile.hpp)
 __device__ __forceinline__ int tile_pos(int c) { return c < 64 ? 16 * (c & 3) + (c >> 2) : c; }
 
-// ---- One walk, four loops.  The four contraction kernels below share their walk; each keeps its reduction loop and its own
+// ---- One walk, four loops (five kernels: the packed dW_p pass is the direct one's loop over P groups at a time).  The contraction kernels below share their walk; each keeps its reduction loop and its own
 // copy of the lane offsets and of the ways results leave the wave.  Which kernel uses which shared piece:
 //                          e_tile  e_groups  e_open  tn_load_*  e_mfma
 //   bwd_e_kernel            yes     yes       yes     yes        yes (fp32 arithmetic)
 //   bwd_e_pipe_kernel       yes     yes       yes     --         yes
 //   bwd_dw_direct_kernel    yes     yes       yes     --         yes
+//   bwd_dw_pack_kernel      yes     yes       --      --         yes (e_groups blocked; a descriptor pair per P groups, dw_pack_walk)
 //   bwd_dw_r32_kernel       yes     yes       yes     --         --  (its own 32-deep bf16 step)
 // NOT shared (a copy per kernel that needs it): the per-lane offsets, extents and steps, the W_p^T tile -> LDS prologue, the
 // out-row flush, the scale-row load and the transposed slab store; the pipelined and the direct kernel also keep their operand
@@ -915,6 +916,157 @@ __global__ __launch_bounds__(256, DW_WPE) void bwd_dw_direct_kernel(const BwdEPa
 }
 
 // ---------------------------------------------------------------------------------------------
+// (2a') the same pass without padded reduction steps.  bwd_dw_direct_kernel cuts every group into (R + 3) / 4 steps of four rows and
+// reads the rows >= R of the last one as zeros: at R = 50 one step in 26 multiplies zeros (one in 7 at R = 17).  The dz rows of
+// consecutive groups are contiguous and the sum runs over (g, r) anyway, so P = 4 / gcd(R, 4) consecutive groups of a wave's blocked
+// range -- a super-group of P R rows -- are reduced together in S = P R / 4 WHOLE steps.  Lane quarter q owns the contiguous rows
+// [q S, (q + 1) S) of the super-group: group g0 + (q >> 1) from row (q & 1) S on for P = 2, group g0 + q from row 0 on for P = 4;
+// at step s every quarter is on row s of its own chunk, so the scalar step offset advances ONE row and the per-lane offsets stay
+// loop invariants.  What becomes per lane: the Y offset (the lane's group may lie in a later impression than g0: set when the
+// super-group is opened, one descriptor from impression b(g0) to the last one the super-group touches) and the scale row (each
+// lane loads the row of ITS group, through a descriptor over the P rows).  A step is what it was: 4 vector-memory instructions,
+// DT multiplies, KT DT MFMAs, requested NSET steps ahead across super-group boundaries.  The < P groups left at the end of the
+// range go through per-group padded steps (the same walk with one group per unit) after the super-groups have drained.
+// Needs the blocked walk, contiguous dz / history / scale rows over the super-group (bwd_e_select checks all of it) and S >= NSET.
+// Summation order differs from bwd_dw_direct_kernel's (a lane quarter's chain takes other rows): the same products, rounding apart.
+#if defined(__HIP_DEVICE_COMPILE__)
+// one phase of the walk: the units of PP groups in [g_lo, g_hi) -- (g_hi - g_lo) % PP == 0.  PP == 1 is the padded per-group walk.
+template <int KT, int DT, bool EXACT, int PP, int NSET>
+__device__ __forceinline__ void dw_pack_walk(const BwdEParams& p, f32x4 (&dW)[KT][DT], int g_lo, int g_hi, int d0, int k0, int lane) {
+    const int D = p.D, R = p.R;
+    const int steps = PP == 1 ? (R + 3) >> 2 : (PP * R) >> 2;              // >= NSET (launcher)
+    const int rstep = PP == 1 ? 4 : 1;                                     // rows a step advances
+    // lane quarter q: group j of the unit, from row row0 on (the step adds 4 s or s)
+    auto group_of = [](int q) { return PP == 1 ? 0 : PP == 2 ? q >> 1 : q; };
+    auto row_of = [&](int q) { return PP == 1 ? q : PP == 2 ? (q & 1) * steps : 0; };
+    unsigned vx4, vx1;                                                     // loop invariants (X rows of a unit are contiguous)
+    {
+        const int r16 = lane & 15, q = lane >> 4;
+        const long xrow = (long)(group_of(q) * R + row_of(q)) * p.xrs;
+        vx4 = (EXACT || k0 + 4 * r16 < D) ? (unsigned)(xrow + k0 + 4 * r16) * 4u : BUF_OOB;
+        vx1 = (EXACT || k0 + 64 + r16 < D) ? (unsigned)(xrow + k0 + 64 + r16) * 4u : BUF_OOB;
+    }
+    const unsigned xbytes = (unsigned)(((long)(PP * R - 1) * p.xrs + D) * 4);
+    const unsigned ybytes = (unsigned)(((long)(R - 1) * p.yrs + D) * 4);   // of the last impression a unit touches
+    const unsigned sbytes = (unsigned)(((long)(PP - 1) * p.lds_ + D) * 4);
+    const unsigned yimp = (unsigned)(p.ys1 * 4);                           // one impression of Y, bytes
+    const int xstep = (int)(p.xrs * 4) * rstep, ystep = (int)(p.yrs * 4) * rstep;
+    if (g_lo >= g_hi) return;
+
+    float a[NSET][KT], b[NSET][DT];                                     // operand register sets (round-robin, no copies)
+    float sr_cur[DT], sr_nxt[DT];                                       // scale rows: unit being consumed / unit being requested
+    __amdgpu_buffer_rsrc_t rx, ry;
+    unsigned vy4 = BUF_OOB, vy1 = BUF_OOB;                              // set per unit
+    int lg = g_lo, ls = 0;                                              // request pointer: (first group of the unit, step)
+    auto open_unit = [&](int gg) {
+        // The Y and scale-row offsets of the lane are formed HERE, from the lane id, once per unit: as loop invariants they would
+        // be carried through the step loop beside the accumulators (six registers the 5x5 forms do not have).
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        const int r16 = l & 15, q = l >> 4, j = group_of(q);
+        const int g1 = gg / p.G2, g2 = gg - g1 * p.G2;
+        rx = buffer_rsrc(p.X + (long)g1 * p.xs1 + (long)g2 * p.xs2, xbytes);
+        unsigned mine = 0, last = 0;                                    // impressions behind g1: this lane's group / the unit's last group
+        if (PP > 1) {
+            int rl = g2 + j, ru = g2 + PP - 1;                          // their t index, unwrapped
+#pragma unroll
+            for (int i = 1; i < PP; ++i) {                              // (T < P: a unit wraps more than once)
+                if (rl >= p.G2) { rl -= p.G2; ++mine; }
+                if (ru >= p.G2) { ru -= p.G2; ++last; }
+            }
+            last = __builtin_amdgcn_readfirstlane(last);                // uniform, and provably so: no waterfall loop around the Y loads
+        }
+        const unsigned yrow = mine * yimp + (unsigned)(row_of(q) * (int)p.yrs) * 4u, srw = (unsigned)(j * p.lds_) * 4u;
+        const bool ok4 = EXACT || d0 + 4 * r16 < D, ok1 = EXACT || d0 + 64 + r16 < D;
+        vy4 = ok4 ? yrow + (unsigned)(d0 + 4 * r16) * 4u : BUF_OOB;
+        vy1 = ok1 ? yrow + (unsigned)(d0 + 64 + r16) * 4u : BUF_OOB;
+        ry = buffer_rsrc(p.Y + (long)g1 * p.ys1, last * yimp + ybytes);
+        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(p.srow + (long)gg * p.lds_, sbytes);
+        const u32x4 s4 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok4 ? srw + (unsigned)(d0 + 4 * r16) * 4u : BUF_OOB, 0, 0);   // columns >= D read 0
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sr_nxt[e] = __uint_as_float(s4[e]);
+        if (DT > 4) sr_nxt[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, ok1 ? srw + (unsigned)(d0 + 64 + r16) * 4u : BUF_OOB, 0, 0));
+    };
+    auto request = [&](float (&a)[KT], float (&b)[DT]) {
+        if (lg >= g_hi) return;
+        if (ls == 0) open_unit(lg);
+        const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(rx, vx4, ls * xstep, 0);
+        const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(ry, vy4, ls * ystep, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { a[e] = __uint_as_float(va[e]); b[e] = __uint_as_float(vb[e]); }
+        if (KT > 4) a[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, vx1, ls * xstep, 0));
+        if (DT > 4) b[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vy1, ls * ystep, 0));
+        if (++ls == steps) { ls = 0; lg += PP; }
+    };
+    int cs = 0;                                                          // step of the unit being consumed
+    auto consume = [&](const float (&a)[KT], const float (&b)[DT]) {
+        if (cs == 0) {
+#pragma unroll
+            for (int jt = 0; jt < DT; ++jt) sr_cur[jt] = sr_nxt[jt];
+        }
+        float bs[DT];
+#pragma unroll
+        for (int jt = 0; jt < DT; ++jt) bs[jt] = b[jt] * sr_cur[jt];
+        e_mfma<KT, DT>(dW, a, bs);
+        if (++cs == steps) cs = 0;
+    };
+    const int total = (g_hi - g_lo) / PP * steps;
+#pragma unroll
+    for (int u = 0; u < NSET; ++u) request(a[u], b[u]);
+    for (int n = 0; n < total; n += NSET) {
+#pragma unroll
+        for (int u = 0; u < NSET; ++u)
+            if (u == 0 || n + u < total) {
+                consume(a[u], b[u]);
+                request(a[u], b[u]);
+            }
+    }
+}
+#endif
+
+template <int KT, int DT, bool EXACT, int P, int NSET = DW_SETS>
+__global__ __launch_bounds__(256, DW_WPE) void bwd_dw_pack_kernel(const BwdEParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(P == 2 || P == 4, "P = 4 / gcd(R, 4) groups per super-group; P = 1 is bwd_dw_direct_kernel");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    const int D = p.D;
+    const ETile tl = e_tile<KT, DT, true>(p);
+    const int d0 = tl.d0, k0 = tl.k0, sgrp = tl.sgrp;
+    const int split = sgrp * 4 + wave;
+    if (split >= p.nsplit) return;
+    const EGroups gr = e_groups<false>(p, sgrp, wave);                  // blocked (launcher)
+    const int g_mid = gr.lo + (gr.hi > gr.lo ? (gr.hi - gr.lo) / P * P : 0);   // super-groups [lo, mid), per-group tail [mid, hi)
+
+    f32x4 dW[KT][DT];
+#pragma unroll
+    for (int it = 0; it < KT; ++it)
+#pragma unroll
+        for (int jt = 0; jt < DT; ++jt) dW[it][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dw_pack_walk<KT, DT, EXACT, P, NSET>(p, dW, gr.lo, g_mid, d0, k0, lane);
+    dw_pack_walk<KT, DT, EXACT, 1, NSET>(p, dW, g_mid, gr.hi, d0, k0, lane);
+
+    // slab layout is TRANSPOSED: ws[split][d][k] (as bwd_e_kernel)
+    float* wsp = p.ws + (long)split * D * D;
+#pragma unroll
+    for (int jt = 0; jt < DT; ++jt) {
+        const int d = d0 + tn_col<DT>(jt, r16);
+        if (!(EXACT || d < D)) continue;
+        float* row = wsp + (long)d * D + k0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int kk = 16 * q + 4 * e;
+            if (EXACT || k0 + kk < D)
+                *reinterpret_cast<f32x4*>(row + kk) = f32x4{dW[0][jt][e], dW[1][jt][e], dW[2][jt][e], dW[3][jt][e]};
+        }
+        if (KT > 4 && (EXACT || k0 + 64 + 4 * q < D)) *reinterpret_cast<f32x4*>(row + 64 + 4 * q) = dW[KT - 1][jt];
+    }
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------
 // (2b) software-pipelined variant of the contraction WITHOUT dW_p (the dh pass).  The epilogue of a group
 // (LDS reads of W_p^T, FMAs, row reduction, bounce, atomics) costs several times its instruction time when it
 // runs as one serial block between two MFMA streams (DESIGN.md "stamp findings").  Here a wave keeps TWO
@@ -1233,7 +1385,19 @@ BwdEPlan bwd_e_plan(int D, int G, int target_waves, int min_gps, int mma) {
 
 BwdEKnobs bwd_e_knobs() {                                              // (read per launch: tests switch forms inside one process)
     auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
-    return {on("NRM_BH_PIPE"), on("NRM_DW_DIRECT"), on("NRM_DW_R32")};
+    return {on("NRM_BH_PIPE"), on("NRM_DW_DIRECT"), on("NRM_DW_R32"), on("NRM_DW_PACK")};
+}
+
+// Groups per super-group the one-accumulator dW_p pass reduces together (bwd_dw_pack_kernel), 1 = per group.  The packed walk needs:
+// the blocked walk; P = 4 / gcd(R, 4) > 1; a split of at least P groups; S = P R / 4 >= DW_SETS steps per super-group; the X rows
+// of consecutive groups, the Y blocks of consecutive g1 and the scale rows contiguous in that order, and a super-group's rows
+// (X: P R of them, Y: up to P blocks) inside the 2^31 bytes a buffer offset addresses.
+static int bwd_dw_pack(const BwdEParams& p, const BwdEPlan& pl) {
+    const int P = p.R % 4 == 0 ? 1 : p.R % 2 == 0 ? 2 : 4;
+    if (P == 1 || p.interleave || pl.gps < P || P * p.R / 4 < DW_SETS) return 1;
+    if (p.xs2 != (long)p.R * p.xrs || p.xs1 != (long)p.G2 * p.xs2 || p.xrs < p.D || p.ys1 < (long)(p.R - 1) * p.yrs + p.D || p.lds_ < p.D) return 1;
+    if ((long)P * p.R * p.xrs * 4 >= (1L << 31) || (long)P * p.ys1 * 4 >= (1L << 31) || (long)P * p.lds_ * 4 >= (1L << 31)) return 1;
+    return P;
 }
 
 // Which kernel a contraction launch takes.  p: with_dt, x_hl4, R, D; pl: the tile shape; with_dw: the (b,t)-grouped pass.
@@ -1260,6 +1424,7 @@ BwdEForm bwd_e_select(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int
         if (p.x_hl4) return refused;
         f.with_dt = false;
         if (knobs.dw_direct && (p.R + 3) / 4 >= DW_SETS) f.family = BWD_DW_DIRECT;   // one accumulator set, the scale row folded into the operand
+        if (f.family == BWD_DW_DIRECT && knobs.dw_pack) f.pack = bwd_dw_pack(p, pl);   // ... and no padded steps where R % 4 != 0
     } else if (!with_dw && knobs.pipe && (p.R + 3) / 4 >= ((DT + 1) & ~1) + 2) {
         f.family = BWD_E_PIPE;
     }
@@ -1304,7 +1469,10 @@ hipError_t bwd_e_launch(const BwdEParams& params, const BwdEPlan& pl, bool with_
             else return;
         } else if constexpr (MMA == 0) {
             if (f.family == BWD_E_PIPE) hipLaunchKernelGGL((bwd_e_pipe_kernel<KT, DT, EXACT>), grid, block, 0, st, p);
-            else if (f.family == BWD_DW_DIRECT) hipLaunchKernelGGL((bwd_dw_direct_kernel<KT, DT, EXACT>), grid, block, 0, st, p);
+            else if (f.family != BWD_DW_DIRECT) return;
+            else if (f.pack == 1) hipLaunchKernelGGL((bwd_dw_direct_kernel<KT, DT, EXACT>), grid, block, 0, st, p);
+            else if (f.pack == 2) hipLaunchKernelGGL((bwd_dw_pack_kernel<KT, DT, EXACT, 2>), grid, block, 0, st, p);
+            else if (f.pack == 4) hipLaunchKernelGGL((bwd_dw_pack_kernel<KT, DT, EXACT, 4>), grid, block, 0, st, p);
             else return;
         } else {
             if (f.family == BWD_DW_R32) hipLaunchKernelGGL((bwd_dw_r32_kernel<EXACT, MMA>), grid, block, 0, st, p);
