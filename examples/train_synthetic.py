@@ -5,6 +5,7 @@ launch), host float64 batches staged one ahead, per-impression AUC on the device
 
     python examples/train_synthetic.py --workload C1-demo --batches 20 --epochs 2
     python examples/train_synthetic.py --workload ref-default --compact-history --history-lengths uniform      
+    python examples/train_synthetic.py --workload ref-default --compact-candidates --candidate-counts percentile    (section 5f)
 """
 import argparse
 import os
@@ -17,6 +18,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from news_recommendation_model_amd import data_io, evaluation, synth, trainer  # noqa: E402
 from news_recommendation_model_amd.config import Dims, WORKLOADS               # noqa: E402
+sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from compact_util import pad_batch, percentile_counts                          # noqa: E402  (the count distribution the tests use)
 
 
 def main():
@@ -31,6 +34,11 @@ def main():
     ap.add_argument("--compact-history", action="store_true", help="do not compute the padded history rows (train_step(compact_history=True))")
     ap.add_argument("--history-lengths", default="full", choices=["full", "uniform", "tenth"],
                     help="cut the synthetic histories the way the ETL pads them: rows past a user's own are all-zero (uniform in [1, H] / all H/10)")
+    ap.add_argument("--compact-candidates", action="store_true",
+                    help="do not compute the padded candidates (train_step(compact_candidates=True)); reads every batch's empty_num")
+    ap.add_argument("--candidate-counts", default="full", choices=["full", "percentile"],
+                    help="pad the synthetic candidate lists the way the ETL does: all-zero rows past a list's own candidates, label 0 (percentile: "
+                         "list lengths drawn from the percentiles the reference records, 70 %% of the lists at most 12 candidates)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
@@ -52,6 +60,9 @@ def main():
             lengths = rng.integers(1, wl["H"] + 1, B) if args.history_lengths == "uniform" else np.full(B, max(wl["H"] // 10, 1))
             for b in range(B):
                 batch["x_history"][b, int(lengths[b]):] = 0.0
+        if args.candidate_counts == "percentile":
+            # (at least two live candidates: the validation below depads a list before its AUC, and one candidate has none)
+            pad_batch(batch, np.maximum(percentile_counts(rng, B, wl["T"], one_long=False), 2))
         records += data_io.records_from_batch(batch)
     head = data_io.write_processed_dataset(records, os.path.join(ckpt_dir, "synthetic_train_processed"), subvolume_item_num=4 * B)
     records, max_user_id = data_io.load_processed_dataset(head)
@@ -62,7 +73,8 @@ def main():
         return (b for b in data_io.iter_batches(records, B, shuffle=True, seed=args.seed + epoch_no[0]) if len(b["user_id"]) == B)
     hosts = list(data_io.iter_batches(records, B, shuffle=False))
     hist = trainer.train_epochs(model, opt, loader, args.epochs,
-                                ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"), compact_history=args.compact_history)
+                                ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"), compact_history=args.compact_history,
+                                compact_candidates=args.compact_candidates)
     for rec in hist:
         print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec))
     # the checkpoint round-trips into a fresh model (test.py:159-160) and validates (verify.py:19-43)

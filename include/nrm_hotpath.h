@@ -441,6 +441,38 @@ int nrm_pool_bmm_wlast(const float* W, long wsb, long wsi, long wsj, const float
 int nrm_pool_rowdot_wlast(const float* g, int ldg, const float* h, float* ds, int B, int T, int H, int D, float* zero_out, int zero_n,
                           float wlast, nrm_stream_t stream);
 
+/* ---- training on compacted candidate lists: row weights for BatchNorm and the loss
+ * The training ETL pads every candidate list with all-zero rows (reference tool/process_data.py:214-217, 249-252).  The batch is sorted by
+ * n_b = T - empty_b and cut into G contiguous groups; group g keeps T_g = min(T, max n_b + 1) columns.  Where T_g < T, column T_g - 1 of
+ * every impression of the group is a padded candidate that stands for w_g = T - T_g + 1 equal ones.  Everything but BatchNorm's batch
+ * statistics (models/user_model.py:18,32) and the loss (:37-43) is row-wise in the candidate; those two take the weight.
+ *
+ * nrm_candidate_gather_groups: the grouped candidate arenas, arena[row_off[g] + (b - b0_g) T_g + t, :] = x[src_imp[b], t, :] for t < T_g, of
+ *   x_target [B, T, target_cols], x_global [B, T, global_cols] and label [B, T] (bitwise, float64 or float32 each), and row_weight [N]
+ *   (w_g on a group's last column, 1 elsewhere).  Every dropped cell (t >= T_g) is compared bitwise with column T_g - 1 of its impression in
+ *   all three tensors; a difference (or tables that place a row outside the arena) sets flag[0] = 1 (the pad-error flag of
+ *   nrm_compact_gather).  Tables (int32, device): src_imp [B], group_b0 [G + 1], group_row_off [G + 1], group_t [G]; N = group_row_off[G];
+ *   G <= 64.  One wave per cell, one launch for all groups; table entries are clamped to the arrays.
+ * nrm_colreduce_roww: nrm_colreduce modes 0 and 1 with a row weight: s0 += sum_r w_r x;  s0 += sum_r w_r (x - mean)^2.  nrm_bn_finalize
+ *   then takes R = the rows of the batch (sum_r w_r).  All weights 1 is bitwise nrm_colreduce.
+ * nrm_bn_backward_roww: the train-mode nrm_bn_backward with dx_r = gamma rstd (dy_r - w_r s0/n - w_r xhat_r s1/n) + add_r, n = n_rows, the
+ *   rows of the batch; s0, s1 are nrm_colreduce mode 2's plain sums over the R rows of the launch (dy carries the weight already).  All
+ *   weights 1 with n_rows = R is bitwise nrm_bn_backward.
+ * nrm_loss_fwd_bwd_wlast: nrm_loss_fwd_bwd for one group: column T - 1 of every impression counts wlast >= 1 times in both softmax
+ *   denominators and both BCE sums, dout[b, T - 1] is the sum over the copies, and the mean is inv_n = 1 / (rows of the batch) -- loss_sum and
+ *   ddelta accumulate over one call per group.  wlast = 1 with inv_n = 1 / (B T) is bitwise nrm_loss_fwd_bwd. */
+int nrm_candidate_gather_groups(const void* x_target, int target_cols, int target_is_f64, const void* x_global, int global_cols, int global_is_f64,
+                                const void* label, int label_is_f64, const int* src_imp, const int* group_b0, const int* group_row_off,
+                                const int* group_t, int G, int B, int T, int N, void* xt_arena, void* xg_arena, void* label_arena, float* row_weight,
+                                int* flag, nrm_stream_t stream);
+int nrm_colreduce_roww(int mode, const float* x, const float* mean, const float* row_weight, float* s0, int R, int N, int ld, nrm_stream_t stream);
+int nrm_bn_backward_roww(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, const float* s0,
+                         const float* s1, const float* add, const float* row_weight, float* dx, int R, int n_rows, int N, int ld,
+                         nrm_stream_t stream);
+int nrm_loss_fwd_bwd_wlast(const float* out, int out_stride, const void* label, int label_is_f64, const long* user_id, const float* delta,
+                           long n_delta, float alpha, int B, int T, float wlast, float inv_n, float* loss_sum, float* dout, int dout_stride,
+                           float* ddelta, int* err, nrm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

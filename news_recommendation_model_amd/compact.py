@@ -188,10 +188,12 @@ class HistoryGroupPlan:
       R                  ``row_off[G]``: history rows the step computes instead of B * H
       saving             ``1 - R / (B * H)``
       dense              nothing worth dropping: every H_g == H, or saving < MIN_SAVING
+      cand               None, or the ``CandidateGroupPlan`` cut along these groups (``plan_candidate_groups(..., history_plan=)``,
+                         DESIGN.md section 5f): the step then trims every group in the candidate axis as well
     """
 
     __slots__ = ("B", "H", "G", "quantum", "hist_len", "perm", "inverse", "bounds", "H_g", "w_g", "row_off", "R", "saving", "dense",
-                 "device_tables")
+                 "device_tables", "cand")
 
     def upload(self, device):
         """-> dict of int32 device views (perm, inverse, bounds, row_off, H_g) of ONE buffer copied from pinned host memory
@@ -213,26 +215,11 @@ class HistoryGroupPlan:
         return tabs
 
 
-def plan_history_groups(hist_len, H, max_groups=None, quantum=16):
-    """``hist_len`` [B]: ``L_b`` as ``ops.history_len`` measures it (host array or tensor; entries are clamped to [0, H]).  Sorts the
-    impressions by length (stable) and cuts the sorted order into at most ``max_groups`` contiguous groups that minimise the kept rows
-    ``sum_g B_g * H_g`` -- contiguous groups of the sorted order are optimal (a group's height is set by its longest member), and the
-    dynamic programme over the cut points is exact.  A group only ever ends where the quantised height changes: a cut inside a run
-    of equal heights saves nothing.  Ties go to fewer groups (every group multiplies the launches)."""
-    if hasattr(hist_len, "detach"):
-        hist_len = hist_len.detach().cpu().numpy()
-    H, q = int(H), int(quantum)
-    max_groups = MAX_GROUPS if max_groups is None else int(max_groups)
-    if H < 1 or q < 1 or not 1 <= max_groups <= GROUPS_CAP:
-        raise ValueError(f"plan_history_groups: H={H} quantum={q} max_groups={max_groups} (H, quantum >= 1, 1 <= max_groups <= {GROUPS_CAP})")
-    L = np.clip(np.asarray(hist_len).reshape(-1).astype(np.int64), 0, H)
-    B = int(L.shape[0])
-    if B * H >= 2 ** 31:
-        raise ValueError("plan_history_groups: more than 2^31 history rows")
-    perm = np.argsort(L, kind="stable")
-    inverse = np.empty(B, dtype=np.int64)
-    inverse[perm] = np.arange(B)
-    height = np.minimum(H, q * ((L[perm] + q) // q))                 # q * ceil((L + 1) / q) of each sorted impression: non-decreasing
+def _cut_sorted(height, max_groups):
+    """The dynamic programme both group planners share.  ``height`` [B]: the non-decreasing kept height of each sorted impression; -> the
+    ascending end points of at most ``max_groups`` contiguous groups that minimise ``sum_g B_g * height of the group's last member``.  A
+    group only ever ends where the height changes; ties go to fewer groups."""
+    B = len(height)
     ends = (np.flatnonzero(np.diff(height)) + 1).tolist() + [B] if B else []      # where a group may end
     K = len(ends)
     h_end = [int(height[e - 1]) for e in ends]
@@ -255,7 +242,31 @@ def plan_history_groups(hist_len, H, max_groups=None, quantum=16):
         while k >= 0 and g >= 0:
             cuts.append(ends[k])
             k, g = back[g][k], g - 1
-    bounds = np.array([0] + cuts[::-1], dtype=np.int64)
+    return cuts[::-1]
+
+
+def plan_history_groups(hist_len, H, max_groups=None, quantum=16):
+    """``hist_len`` [B]: ``L_b`` as ``ops.history_len`` measures it (host array or tensor; entries are clamped to [0, H]).  Sorts the
+    impressions by length (stable) and cuts the sorted order into at most ``max_groups`` contiguous groups that minimise the kept rows
+    ``sum_g B_g * H_g`` -- contiguous groups of the sorted order are optimal (a group's height is set by its longest member), and the
+    dynamic programme over the cut points is exact.  A group only ever ends where the quantised height changes: a cut inside a run
+    of equal heights saves nothing.  Ties go to fewer groups (every group multiplies the launches)."""
+    if hasattr(hist_len, "detach"):
+        hist_len = hist_len.detach().cpu().numpy()
+    H, q = int(H), int(quantum)
+    max_groups = MAX_GROUPS if max_groups is None else int(max_groups)
+    if H < 1 or q < 1 or not 1 <= max_groups <= GROUPS_CAP:
+        raise ValueError(f"plan_history_groups: H={H} quantum={q} max_groups={max_groups} (H, quantum >= 1, 1 <= max_groups <= {GROUPS_CAP})")
+    L = np.clip(np.asarray(hist_len).reshape(-1).astype(np.int64), 0, H)
+    B = int(L.shape[0])
+    if B * H >= 2 ** 31:
+        raise ValueError("plan_history_groups: more than 2^31 history rows")
+    perm = np.argsort(L, kind="stable")
+    inverse = np.empty(B, dtype=np.int64)
+    inverse[perm] = np.arange(B)
+    height = np.minimum(H, q * ((L[perm] + q) // q))                 # q * ceil((L + 1) / q) of each sorted impression: non-decreasing
+    cuts = _cut_sorted(height, max_groups)
+    bounds = np.array([0] + cuts, dtype=np.int64)
     G = len(bounds) - 1
     H_g = np.array([int(height[bounds[g + 1] - 1]) for g in range(G)], dtype=np.int64)
     row_off = np.zeros(G + 1, dtype=np.int64)
@@ -268,4 +279,131 @@ def plan_history_groups(hist_len, H, max_groups=None, quantum=16):
     plan.saving = 1.0 - plan.R / (B * H) if B else 0.0
     plan.dense = bool((H_g == H).all()) or plan.saving < MIN_SAVING
     plan.device_tables = None
+    plan.cand = None
+    return plan
+
+
+# ------------------------------------------------------------------------------------------------ training: candidate count groups
+#   The training ETL pads every candidate list with all-zero rows to T columns; all padded candidates of one impression
+# have the same inputs and the same label.  The batch is sorted by n_b = T - empty_b and cut into a few contiguous groups, each trimmed to
+# T_g = min(T, max n_b + 1) columns: where T_g < T the group's last column is a padded candidate that stands for w_g = T - T_g + 1 equal ones,
+# which BatchNorm's batch statistics and the loss see as a row weight.  MAX_GROUPS and MIN_SAVING are the defaults here too: both unmeasured.
+class CandidateGroupPlan:
+    """Candidate count groups of one batch (host numpy; ``upload`` puts the tables on a device with ONE pinned copy).
+
+      B, T, G            impressions, candidate columns of the input, groups
+      count [B]          ``n_b = T - empty_b`` with empty_b clamped to [0, T], in the CALLER's order
+      perm [B]           stable argsort of count: sorted impression i is impression perm[i] of the batch
+      inverse [B]        ``inverse[perm] == arange(B)``
+      bounds [G + 1]     group g = sorted impressions bounds[g] .. bounds[g + 1] - 1
+      T_g [G]            columns kept per impression of the group: min(T, max n_b + 1)
+      w_g [G]            ``T - T_g + 1``: how many equal candidates column T_g - 1 stands for (1 where T_g == T: the dense computation)
+      row_off [G + 1]    first row of each group in the candidate arena, ``row_off[g + 1] - row_off[g] = B_g * T_g``
+      N                  ``row_off[G]``: candidate rows the step computes instead of B * T
+      expand [B * T]     arena row of dense cell ``b * T + t`` in the caller's order (a dropped cell maps to its group's last column)
+      saving             ``1 - N / (B * T)``
+      dense              nothing worth dropping: every T_g == T, or saving < MIN_SAVING
+    """
+
+    __slots__ = ("B", "T", "G", "count", "perm", "inverse", "bounds", "T_g", "w_g", "row_off", "N", "expand", "saving", "dense", "device_tables")
+
+    def upload(self, device):
+        """-> dict of int32 device views (perm, bounds, row_off, T_g, expand) of ONE buffer copied from pinned host memory (non-blocking)."""
+        import torch
+        if self.device_tables is not None and self.device_tables["perm"].device == torch.device(device):
+            return self.device_tables
+        parts = [("perm", self.perm), ("bounds", self.bounds), ("row_off", self.row_off), ("T_g", self.T_g), ("expand", self.expand)]
+        host = torch.empty(sum(len(p) for _, p in parts), dtype=torch.int32)
+        if torch.cuda.is_available():
+            host = host.pin_memory()
+        host.numpy()[:] = np.concatenate([p for _, p in parts])
+        dev = host.to(device, non_blocking=True)
+        tabs, o = {"_host": host}, 0
+        for name, p in parts:
+            tabs[name] = dev[o:o + len(p)]
+            o += len(p)
+        self.device_tables = tabs
+        return tabs
+
+
+def plan_candidate_groups(empty_num, T, max_groups=None, history_plan=None):
+    """``empty_num`` [B]: trailing all-padding candidates per impression (the DataLoader's HOST tensor or array; a device tensor costs one
+    ``.cpu()``); entries are clamped to [0, T].  Sorts the impressions by ``n_b = T - empty_b`` (stable) and cuts the sorted order with the
+    dynamic programme of ``plan_history_groups`` (cost ``sum_g B_g * T_g``, quantum 1, cuts only where n_b changes, ties to fewer groups).
+    ``history_plan`` (a ``HistoryGroupPlan`` of the same batch): no joint planner -- order and cuts stay the history plan's, every group
+    additionally gets ``T_g = min(T, max n_b + 1)`` of its members, and ``saving`` is ``1 - sum_g B_g T_g H_g / (B T H)``."""
+    if hasattr(empty_num, "detach"):
+        empty_num = empty_num.detach().cpu().numpy()
+    T = int(T)
+    max_groups = MAX_GROUPS if max_groups is None else int(max_groups)
+    if T < 1 or not 1 <= max_groups <= GROUPS_CAP:
+        raise ValueError(f"plan_candidate_groups: T={T} max_groups={max_groups} (T >= 1, 1 <= max_groups <= {GROUPS_CAP})")
+    count = T - np.clip(np.asarray(empty_num).reshape(-1).astype(np.int64), 0, T)
+    B = int(count.shape[0])
+    if B * T >= 2 ** 31:
+        raise ValueError("plan_candidate_groups: more than 2^31 candidate rows")
+    if history_plan is not None:
+        if history_plan.B != B:
+            raise ValueError(f"plan_candidate_groups: empty_num has {B} entries for a history plan of {history_plan.B} impressions")
+        perm, inverse, bounds = (np.asarray(a).astype(np.int64) for a in (history_plan.perm, history_plan.inverse, history_plan.bounds))
+        width = np.minimum(T, count[perm] + 1)
+        G = len(bounds) - 1
+        T_g = np.array([int(width[bounds[g]:bounds[g + 1]].max()) for g in range(G)], dtype=np.int64)
+    else:
+        perm = np.argsort(count, kind="stable")
+        inverse = np.empty(B, dtype=np.int64)
+        inverse[perm] = np.arange(B)
+        width = np.minimum(T, count[perm] + 1)                       # the live candidates and ONE representative padded one
+        bounds = np.array([0] + _cut_sorted(width, max_groups), dtype=np.int64)
+        G = len(bounds) - 1
+        T_g = np.array([int(width[bounds[g + 1] - 1]) for g in range(G)], dtype=np.int64)
+    row_off = np.zeros(G + 1, dtype=np.int64)
+    np.cumsum(np.diff(bounds) * T_g, out=row_off[1:])
+    group = np.repeat(np.arange(G, dtype=np.int64), np.diff(bounds))[inverse] if B else np.zeros(0, dtype=np.int64)     # group of impression b
+    first = (row_off[group] + (inverse - bounds[group]) * T_g[group]) if B else group
+    expand = first[:, None] + np.minimum(np.arange(T, dtype=np.int64)[None, :], (T_g[group] - 1)[:, None]) if B else np.zeros((0, T), dtype=np.int64)
+    plan = CandidateGroupPlan()
+    plan.B, plan.T, plan.G = B, T, G
+    plan.count, plan.perm, plan.inverse = count.astype(np.int32), perm.astype(np.int32), inverse.astype(np.int32)
+    plan.bounds, plan.T_g, plan.w_g, plan.row_off = bounds.astype(np.int32), T_g.astype(np.int32), (T - T_g + 1).astype(np.int32), row_off.astype(np.int32)
+    plan.N = int(row_off[G])
+    plan.expand = expand.reshape(-1).astype(np.int32)
+    plan.saving = 1.0 - plan.N / (B * T) if B else 0.0
+    if history_plan is not None and B:
+        plan.saving = 1.0 - float((np.diff(bounds) * T_g * np.asarray(history_plan.H_g).astype(np.int64)).sum()) / (B * T * history_plan.H)
+    plan.dense = bool((T_g == T).all()) or plan.saving < MIN_SAVING
+    plan.device_tables = None
+    return plan
+
+
+def candidate_saving_bound(empty_num, T):
+    """The share of the B * T candidate rows NO grouping can drop more than: every impression its own group, ``1 - sum_b min(T, n_b + 1) /
+    (B T)``.  One pass over the counts: ``train_step`` asks this first, so a batch with nothing worth dropping pays neither the sort nor the
+    dynamic programme nor the tables (at launch-bound sizes the plan's host time is a measurable part of a step)."""
+    if hasattr(empty_num, "detach"):
+        empty_num = empty_num.detach().cpu().numpy()
+    T = int(T)
+    empty = np.asarray(empty_num).reshape(-1)
+    B = empty.shape[0]
+    if B == 0 or T < 1:
+        return 0.0
+    # min(T, n_b + 1) = T + 1 - clip(empty_b, 1, T)
+    return 1.0 - (B * (T + 1) - float(np.clip(empty, 1, T).sum())) / (B * T)
+
+
+def full_height_history_plan(cand, H):
+    """The ``HistoryGroupPlan`` of a step that compacts the candidate lists only: ``cand``'s order and cuts, every group at the full height H
+    (``w_g = 1``: the dense pool), carrying ``cand``."""
+    H = int(H)
+    if H < 1 or cand.B * H >= 2 ** 31:
+        raise ValueError(f"full_height_history_plan: H={H} for {cand.B} impressions")
+    plan = HistoryGroupPlan()
+    plan.B, plan.H, plan.G, plan.quantum = cand.B, H, cand.G, 1
+    plan.hist_len = np.full(cand.B, H, dtype=np.int32)
+    plan.perm, plan.inverse, plan.bounds = cand.perm, cand.inverse, cand.bounds
+    plan.H_g, plan.w_g = np.full(cand.G, H, dtype=np.int32), np.ones(cand.G, dtype=np.int32)
+    plan.row_off = (cand.bounds.astype(np.int64) * H).astype(np.int32)
+    plan.R, plan.saving, plan.dense = cand.B * H, 0.0, True
+    plan.device_tables = None
+    plan.cand = cand
     return plan

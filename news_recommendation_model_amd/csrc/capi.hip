@@ -728,6 +728,60 @@ int nrm_pool_rowdot_wlast(const float* g, int ldg, const float* h, float* ds, in
                      "pool_rowdot_wlast");
 }
 
+// ---- training on compacted candidate lists
+int nrm_candidate_gather_groups(const void* x_target, int target_cols, int target_is_f64, const void* x_global, int global_cols, int global_is_f64,
+                                const void* label, int label_is_f64, const int* src_imp, const int* group_b0, const int* group_row_off,
+                                const int* group_t, int G, int B, int T, int N, void* xt_arena, void* xg_arena, void* label_arena, float* row_weight,
+                                int* flag, nrm_stream_t stream) {
+    if (B < 0 || T <= 0 || N < 0 || G < 0 || G > nrm::HISTORY_GROUPS_MAX || target_cols <= 0 || global_cols <= 0 || (long)N > (long)B * T ||
+        (long)B * T >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_candidate_gather_groups: B=%d T=%d N=%d G=%d target_cols=%d global_cols=%d (0 <= G <= %d, N <= B*T < 2^31)", B, T, N, G,
+                    target_cols, global_cols, nrm::HISTORY_GROUPS_MAX);
+    if ((long)target_cols * 2 >= (1L << 31) || (long)global_cols * 2 >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_candidate_gather_groups: target_cols=%d global_cols=%d", target_cols, global_cols);
+    if (!flag || (B > 0 && (!x_target || !x_global || !label || !src_imp || !group_b0 || !group_row_off || !group_t || G == 0)) ||
+        (N > 0 && (!xt_arena || !xg_arena || !label_arena || !row_weight)))
+        return fail(NRM_EINVAL, "nrm_candidate_gather_groups: null pointer (or B=%d impressions in G=0 groups)", B);
+    nrm::CandidateGatherParams p;
+    p.xt = (const unsigned*)x_target; p.xg = (const unsigned*)x_global; p.lab = (const unsigned*)label;
+    p.xt_a = (unsigned*)xt_arena; p.xg_a = (unsigned*)xg_arena; p.lab_a = (unsigned*)label_arena; p.roww = row_weight;
+    p.wt = target_cols * (target_is_f64 ? 2 : 1); p.wg = global_cols * (global_is_f64 ? 2 : 1); p.wl = label_is_f64 ? 2 : 1;
+    p.src_imp = src_imp; p.b0 = group_b0; p.row_off = group_row_off; p.tg = group_t; p.G = G; p.B = B; p.T = T; p.N = N; p.flag = flag;
+    return check_hip(nrm::candidate_gather_groups_launch(p, (hipStream_t)stream), "candidate_gather_groups");
+}
+
+int nrm_colreduce_roww(int mode, const float* x, const float* mean, const float* row_weight, float* s0, int R, int N, int ld, nrm_stream_t stream) {
+    if (int rc = check_bn("nrm_colreduce_roww", R, N, ld)) return rc;
+    if (!x || !s0 || !row_weight || (mode == 1 && !mean) || mode < 0 || mode > 1)
+        return fail(NRM_EINVAL, "nrm_colreduce_roww: bad argument for mode %d (modes 0 and 1 have a row-weight form)", mode);
+    return check_hip(nrm::colred_roww_launch(mode, x, mean, row_weight, s0, R, N, ld, (hipStream_t)stream), "colreduce_roww");
+}
+
+int nrm_bn_backward_roww(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, const float* s0,
+                         const float* s1, const float* add, const float* row_weight, float* dx, int R, int n_rows, int N, int ld,
+                         nrm_stream_t stream) {
+    if (int rc = check_bn("nrm_bn_backward_roww", R, N, ld)) return rc;
+    if (!dy || !rstd || !gamma || !dx || !x || !mean || !s0 || !s1 || !row_weight) return fail(NRM_EINVAL, "nrm_bn_backward_roww: null pointer");
+    if (n_rows < R) return fail(NRM_EINVAL, "nrm_bn_backward_roww: n_rows=%d < R=%d (the batch has at least the rows of the launch)", n_rows, R);
+    return check_hip(nrm::bn_bwd_roww_launch(x, dy, mean, rstd, gamma, s0, s1, add, row_weight, dx, R, n_rows, N, ld, (hipStream_t)stream),
+                     "bn_backward_roww");
+}
+
+int nrm_loss_fwd_bwd_wlast(const float* out, int out_stride, const void* label, int label_is_f64, const long* user_id, const float* delta,
+                           long n_delta, float alpha, int B, int T, float wlast, float inv_n, float* loss_sum, float* dout, int dout_stride,
+                           float* ddelta, int* err, nrm_stream_t stream) {
+    if (!out || !label || !user_id || !delta || !loss_sum || !dout || !ddelta || !err) return fail(NRM_EINVAL, "nrm_loss_fwd_bwd_wlast: null pointer");
+    if (B < 0 || T <= 0 || n_delta < 1 || (long)B * T >= (1L << 29))
+        return fail(NRM_EINVAL, "nrm_loss_fwd_bwd_wlast: B=%d T=%d n_delta=%ld (T >= 1, n_delta >= 1, B*T < 2^29)", B, T, n_delta);
+    if (out_stride < 1 || dout_stride < 1 || (dout_stride == 4 && !al16(dout)))
+        return fail(NRM_EINVAL, "nrm_loss_fwd_bwd_wlast: out_stride=%d dout_stride=%d (>= 1; dout 16-byte aligned for stride 4)", out_stride, dout_stride);
+    if (!(wlast >= 1.f) || !(inv_n > 0.f))
+        return fail(NRM_EINVAL, "nrm_loss_fwd_bwd_wlast: wlast=%g inv_n=%g (wlast >= 1: the candidates the last column stands for; inv_n > 0)", (double)wlast,
+                    (double)inv_n);
+    return check_hip(nrm::loss_wlast_launch(out, out_stride, label, label_is_f64, user_id, delta, n_delta, alpha, B, T, wlast, inv_n, loss_sum, dout,
+                                            dout_stride, ddelta, err, (hipStream_t)stream), "loss_wlast");
+}
+
 int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride, int M, const int* cand_off, const int* pad_mult, int N,
                              const float* label, int B, int T, float* score, int* rank, int* live, float* metrics, nrm_stream_t stream) {
     if (!logits || !cand_off || !pad_mult || !score || !rank || !live) return fail(NRM_EINVAL, "nrm_ensemble_rank_ragged: null pointer");

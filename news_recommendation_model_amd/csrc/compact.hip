@@ -164,6 +164,49 @@ hipError_t history_gather_groups_launch(const unsigned* x, unsigned* xh_g, int w
     return hipGetLastError();
 }
 
+// Candidate arena of the compacted training step (section 5f).  One wave per cell (sorted impression bs, column t) of the B * T cells: its
+// group is the last g with b0[g] <= bs (a walk, as above), T_g = tg[g] the columns the group keeps.  A kept cell (t < T_g) is copied to arena
+// row row_off[g] + (bs - b0[g]) * T_g + t of all three tensors and gets its row weight: T - T_g + 1 on the group's last column, 1 elsewhere.
+// A dropped cell (t >= T_g) must be bitwise equal to column T_g - 1 of its impression in all three tensors: the host's empty_num is checked,
+// not trusted.  Every table entry is clamped and a row outside the arena is not written (and raises the flag): tables that do not add up
+// copy a wrong row or none, never read outside the [B, T] inputs or write outside the [N] arenas.
+__global__ __launch_bounds__(256) void candidate_gather_groups_kernel(const CandidateGatherParams p) {
+    const int lane = threadIdx.x & 63;
+    const long cell = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= (long)p.B * p.T) return;
+    const int bs = (int)(cell / p.T), t = (int)(cell - (long)bs * p.T);
+    int g = 0;
+    for (int k = 1; k < p.G; ++k)
+        if (min(max(p.b0[k], 0), p.B) <= bs) g = k;
+    const int bg = min(max(p.b0[g], 0), bs);
+    const int tg = min(max(p.tg[g], 1), p.T);
+    const int b = min(max(p.src_imp[bs], 0), p.B - 1);
+    const long src = (long)b * p.T + t;
+    if (t < tg) {
+        const long dst = (long)min(max(p.row_off[g], 0), p.N) + (long)(bs - bg) * tg + t;
+        if (dst >= p.N) { if (lane == 0) *p.flag = 1; return; }
+        for (int w = lane; w < p.wt; w += 64) p.xt_a[dst * p.wt + w] = p.xt[src * p.wt + w];
+        for (int w = lane; w < p.wg; w += 64) p.xg_a[dst * p.wg + w] = p.xg[src * p.wg + w];
+        for (int w = lane; w < p.wl; w += 64) p.lab_a[dst * p.wl + w] = p.lab[src * p.wl + w];
+        if (lane == 0) p.roww[dst] = t == tg - 1 ? (float)(p.T - tg + 1) : 1.f;
+    } else {
+        const long rep = (long)b * p.T + (tg - 1);
+        bool differs = false;
+        for (int w = lane; w < p.wt; w += 64) differs |= p.xt[src * p.wt + w] != p.xt[rep * p.wt + w];
+        for (int w = lane; w < p.wg; w += 64) differs |= p.xg[src * p.wg + w] != p.xg[rep * p.wg + w];
+        for (int w = lane; w < p.wl; w += 64) differs |= p.lab[src * p.wl + w] != p.lab[rep * p.wl + w];
+        if (differs) *p.flag = 1;
+    }
+}
+
+hipError_t candidate_gather_groups_launch(const CandidateGatherParams& p, hipStream_t st) {
+    const long cells = (long)p.B * p.T;
+    if (cells <= 0 || p.G <= 0) return hipSuccess;
+    if ((cells + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(candidate_gather_groups_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void history_tiles_kernel(const int* __restrict__ cand_imp, const int* __restrict__ cand_off,
                                                             const int* __restrict__ hist_off, const int* __restrict__ tile_pre, int B, int N,
                                                             int R, int Mt, int4* __restrict__ tile_tab) {

@@ -25,6 +25,19 @@ hipError_t history_gather_launch(const unsigned* x, unsigned* xh_c, int words, c
 constexpr int HISTORY_GROUPS_MAX = 64;
 hipError_t history_gather_groups_launch(const unsigned* x, unsigned* xh_g, int words, const int* src_imp, const int* b0, const int* row_off,
                                         const int* hg, int G, int B, int H, int R, hipStream_t st);
+// Grouped candidate arena of the step that trains on compacted candidate lists (section 5f): group g holds the impressions b0[g] .. b0[g + 1] - 1
+// of the sorted batch, each trimmed to tg[g] candidate columns, from arena row row_off[g]; where tg[g] < T the group's last column stands for
+// T - tg[g] + 1 equal padded candidates (its row weight) and every dropped cell is compared with it.  One launch for all G groups.
+struct CandidateGatherParams {
+    const unsigned* xt; const unsigned* xg; const unsigned* lab;     // [B*T, wt] / [B*T, wg] / [B*T, wl] as 32-bit words
+    unsigned* xt_a; unsigned* xg_a; unsigned* lab_a;                 // [N, wt] / [N, wg] / [N, wl]
+    float* roww;                                                     // [N]
+    int wt, wg, wl;
+    const int* src_imp; const int* b0; const int* row_off; const int* tg;     // [B], [G + 1], [G + 1], [G]
+    int G, B, T, N;
+    int* flag;                                                       // the pad-error flag of CompactGatherParams
+};
+hipError_t candidate_gather_groups_launch(const CandidateGatherParams& p, hipStream_t st);
 // Per-tile table of the history-ragged attention: the score rows of compact candidate c (impression b = cand_imp[c], K_b kept history rows)
 // are nt_b = ceil(K_b / 16) whole 16-row tiles, tile_pre[b] + (c - cand_off[b]) nt_b + jt; entry = {c, first row of the tile in h_c / u,
 // valid rows of the tile, b}.  One thread per candidate writes its nt_b entries.

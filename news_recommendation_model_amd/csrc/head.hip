@@ -5,6 +5,10 @@
 //   colred_kernel<2>   s0[n] += sum_r dy ; s1[n] += sum_r dy * (x - mean) * rstd       (d beta, d gamma)
 //   bn_apply_kernel    y = (x - mean) * rstd * gamma + beta
 //   bn_bwd_kernel      dx = gamma * rstd * (dy - s0/R - xhat * s1/R)    (train)   |  gamma * rstd * dy  (eval)
+// ROWW (training on compacted candidate lists): row r of the launch stands for roww[r] >= 1 equal rows of the
+// batch.  Modes 0 and 1 then sum roww[r] * x and roww[r] * (x - mean)^2, and the two column terms of the backward are multiplied by
+// roww[r]; mode 2 sums gradients that already carry the weight and has no such form.  R of the finalisation and of 1/R in the backward is
+// the row count of the BATCH (n_rows), not of the launch.  ROWW = false compiles to the code the kernels had before the flag.
 // Layout: thread = one float4 of columns; blockDim (32, 8); a workgroup sweeps `rpb` rows of a 128-column slab
 // and adds its partial sums with float atomics (R/rpb adds per column).
 #include "common.hpp"
@@ -12,11 +16,11 @@
 
 namespace nrm {
 
-template <int MODE>
+template <int MODE, bool ROWW = false>
 __global__ __launch_bounds__(256) void colred_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      float* __restrict__ s0, float* __restrict__ s1,
-                                                     int R, int N, int ld, int rpb) {
+                                                     int R, int N, int ld, int rpb, const float* __restrict__ roww) {
     __shared__ f32x4 red[2][8][32];
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int col = blockIdx.x * 128 + 4 * tx;
@@ -28,8 +32,8 @@ __global__ __launch_bounds__(256) void colred_kernel(const float* __restrict__ x
     if (cok) {
         for (int r = r_lo + ty; r < r_hi; r += 8) {
             const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)r * ld + col);
-            if (MODE == 0) a0 += xv;
-            else if (MODE == 1) { const f32x4 d = xv - mu; a0 += d * d; }
+            if (MODE == 0) { if (ROWW) a0 += xv * roww[r]; else a0 += xv; }
+            else if (MODE == 1) { const f32x4 d = xv - mu; if (ROWW) a0 += d * (d * roww[r]); else a0 += d * d; }      // weight 1: the same fma
             else {
                 const f32x4 g = *reinterpret_cast<const f32x4*>(dy + (size_t)r * ld + col);
                 a0 += g;
@@ -68,14 +72,16 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
 }
 
+template <bool ROWW = false>
 __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, const float* __restrict__ s0,
                                                      const float* __restrict__ s1, const float* __restrict__ add,
-                                                     float* __restrict__ dx, long R, int N, int ld, int training) {
+                                                     float* __restrict__ dx, long R, int N, int ld, int training,
+                                                     const float* __restrict__ roww, long n_rows) {
     const int n4 = N >> 2;
     const long total = R * n4;
-    const float invR = 1.0f / (float)R;
+    const float invR = 1.0f / (float)(ROWW ? n_rows : R);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long r = i / n4;
         const int col = (int)(i - r * n4) * 4;
@@ -87,7 +93,9 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restrict__ x
             const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + col);
             const f32x4 a = *reinterpret_cast<const f32x4*>(s0 + col), b = *reinterpret_cast<const f32x4*>(s1 + col);
             const f32x4 xh = (xv - mu) * rs;
-            out = ga * rs * (g - a * invR - xh * b * invR);
+            // the weight goes onto the column sums first: with weight 1 the expression below is the unweighted one, operation for operation
+            if (ROWW) { const float w = roww[r]; const f32x4 aw = a * w, bw = b * w; out = ga * rs * (g - aw * invR - xh * bw * invR); }
+            else out = ga * rs * (g - a * invR - xh * b * invR);
         } else {
             out = ga * rs * g;
         }
@@ -145,9 +153,22 @@ hipError_t colred_launch(int mode, const float* x, const float* dy, const float*
     if (R <= 0) return hipSuccess;
     const int rpb = 256;
     const dim3 grid((N + 127) / 128, (R + rpb - 1) / rpb), block(32, 8);
-    if (mode == 0) hipLaunchKernelGGL(colred_kernel<0>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb);
-    else if (mode == 1) hipLaunchKernelGGL(colred_kernel<1>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb);
-    else if (mode == 2) hipLaunchKernelGGL(colred_kernel<2>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb);
+    const float* none = nullptr;
+    if (mode == 0) hipLaunchKernelGGL(colred_kernel<0>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb, none);
+    else if (mode == 1) hipLaunchKernelGGL(colred_kernel<1>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb, none);
+    else if (mode == 2) hipLaunchKernelGGL(colred_kernel<2>, grid, block, 0, st, x, dy, mean, rstd, s0, s1, R, N, ld, rpb, none);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t colred_roww_launch(int mode, const float* x, const float* mean, const float* roww, float* s0, int R, int N, int ld, hipStream_t st) {
+    if (R <= 0) return hipSuccess;
+    const int rpb = 256;
+    const float* none = nullptr;
+    float* nos1 = nullptr;
+    const dim3 grid((N + 127) / 128, (R + rpb - 1) / rpb), block(32, 8);
+    if (mode == 0) hipLaunchKernelGGL((colred_kernel<0, true>), grid, block, 0, st, x, none, mean, none, s0, nos1, R, N, ld, rpb, roww);
+    else if (mode == 1) hipLaunchKernelGGL((colred_kernel<1, true>), grid, block, 0, st, x, none, mean, none, s0, nos1, R, N, ld, rpb, roww);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -172,7 +193,18 @@ hipError_t bn_bwd_launch(const float* x, const float* dy, const float* mean, con
                          const float* s0, const float* s1, const float* add, float* dx, long R, int N, int ld, int training,
                          hipStream_t st) {
     if (R <= 0) return hipSuccess;
-    hipLaunchKernelGGL(bn_bwd_kernel, dim3(ew_blocks(R * (N >> 2))), dim3(256), 0, st, x, dy, mean, rstd, gamma, s0, s1, add, dx, R, N, ld, training);
+    const float* none = nullptr;
+    hipLaunchKernelGGL(bn_bwd_kernel<false>, dim3(ew_blocks(R * (N >> 2))), dim3(256), 0, st, x, dy, mean, rstd, gamma, s0, s1, add, dx, R, N, ld, training,
+                       none, R);
+    return hipGetLastError();
+}
+
+hipError_t bn_bwd_roww_launch(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                              const float* s0, const float* s1, const float* add, const float* roww, float* dx, long R, long n_rows, int N, int ld,
+                              hipStream_t st) {
+    if (R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(bn_bwd_kernel<true>, dim3(ew_blocks(R * (N >> 2))), dim3(256), 0, st, x, dy, mean, rstd, gamma, s0, s1, add, dx, R, N, ld, 1,
+                       roww, n_rows);
     return hipGetLastError();
 }
 

@@ -10,6 +10,11 @@ hipError_t bn_apply_launch(const float* x, const float* mean, const float* rstd,
 hipError_t bn_bwd_launch(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                          const float* s0, const float* s1, const float* add, float* dx, long R, int N, int ld, int training,
                          hipStream_t st);
+// row-weight forms: row r stands for roww[r] equal rows of a batch of n_rows rows; modes 0 and 1 only, training only
+hipError_t colred_roww_launch(int mode, const float* x, const float* mean, const float* roww, float* s0, int R, int N, int ld, hipStream_t st);
+hipError_t bn_bwd_roww_launch(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                              const float* s0, const float* s1, const float* add, const float* roww, float* dx, long R, long n_rows, int N, int ld,
+                              hipStream_t st);
 constexpr int CONCAT_MAX = 8;
 struct ConcatTable { const float* src[CONCAT_MAX]; long ld[CONCAT_MAX]; int start[CONCAT_MAX]; int n; };
 hipError_t concat_cols_launch(const ConcatTable& tab, float* out, long R, int ldo, int total, hipStream_t st);

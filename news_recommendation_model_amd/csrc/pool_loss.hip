@@ -328,11 +328,17 @@ __device__ __forceinline__ float wave_max64(float v) {
 
 // out / dout: element (b, t) at [(b*T + t) * stride] -- stride 4 is the single column of a zero-padded [B*T, 4] matrix (what the
 // GEMM that produces the logits writes and the GEMM that consumes their gradient reads): dout then gets whole float4s (g, 0, 0, 0).
-template <typename LT>
+// WLAST (training on compacted candidate lists): every impression of the launch was trimmed to the same T columns and
+// its last column stands for `wlast` equal padded candidates: column T - 1 enters both softmax denominators and both BCE sums `wlast` times,
+// and its dout is the sum over the copies (wlast times the per-copy gradient).  The mean is over the rows of the whole BATCH: `inv_n` =
+// 1 / (B T) of the batch comes in, loss_sum and ddelta accumulate over one launch per group.  wlast = 1 with inv_n = 1 / (B T) of the launch
+// is bitwise the plain kernel; WLAST = false compiles to the code the kernels had before the flag.
+template <typename LT, bool WLAST = false>
 __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out, int so, const LT* __restrict__ label,
                                                    const long* __restrict__ uid, const float* __restrict__ delta,
                                                    long n_delta, float alpha, int B, int T, float* __restrict__ loss_sum,
-                                                   float* __restrict__ dout, int sd, float* __restrict__ ddelta, int* __restrict__ err) {
+                                                   float* __restrict__ dout, int sd, float* __restrict__ ddelta, int* __restrict__ err,
+                                                   float wlast, float inv_n) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
         id = id < 0 ? 0 : n_delta - 1;
     }
     const float dl = delta[id];
-    const float inv = 1.0f / ((float)B * (float)T);
+    const float inv = WLAST ? inv_n : 1.0f / ((float)B * (float)T);
     float o[4], y[4];
     float mx = -3.0e38f;
 #pragma unroll
@@ -358,6 +364,11 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
     mx = wave_max64(mx);
     float total = 0.f, gsum_shift = 0.f;
     float g[4] = {0.f, 0.f, 0.f, 0.f};
+    float wl[4] = {1.f, 1.f, 1.f, 1.f};
+    if (WLAST) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) wl[v] = (lane + 64 * v == T - 1) ? wlast : 1.f;
+    }
     // the two terms differ by the per-row shift only; softmax(out + c) is computed as written (shift inside exp)
 #pragma unroll
     for (int term = 0; term < 2; ++term) {
@@ -365,7 +376,10 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
         const float wt = term ? alpha : 1.0f - alpha;
         float e[4], se = 0.f;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { e[v] = (lane + 64 * v < T) ? __expf((o[v] + shift) - (mx + shift)) : 0.f; se += e[v]; }
+        for (int v = 0; v < 4; ++v) {
+            e[v] = (lane + 64 * v < T) ? __expf((o[v] + shift) - (mx + shift)) : 0.f;
+            if (WLAST) se += wl[v] * e[v]; else se += e[v];
+        }
         se = wave_sum64(se);
         const float rse = 1.0f / se;
         float dp[4], pdp = 0.f, lsum = 0.f;
@@ -374,10 +388,11 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
             const bool ok = lane + 64 * v < T;
             const float p = e[v] * rse;
             const float lp = fmaxf(__logf(p), -100.f), l1p = fmaxf(__logf(1.0f - p), -100.f);
-            lsum += ok ? -(y[v] * lp + (1.0f - y[v]) * l1p) : 0.f;
+            if (WLAST) lsum += ok ? wl[v] * -(y[v] * lp + (1.0f - y[v]) * l1p) : 0.f;
+            else lsum += ok ? -(y[v] * lp + (1.0f - y[v]) * l1p) : 0.f;
             dp[v] = ok ? (p - y[v]) / fmaxf(p * (1.0f - p), 1e-12f) : 0.f;          // d BCE / dp  (torch BCELoss backward)
-            pdp += p * dp[v];
-            e[v] = p;
+            e[v] = WLAST ? wl[v] * p : p;                                           // the column's share of the softmax: w p
+            pdp += e[v] * dp[v];
         }
         pdp = wave_sum64(pdp);
         lsum = wave_sum64(lsum);
@@ -408,11 +423,12 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
 // More than 256 candidates per impression (the reference takes any T: models/user_model.py:37-43 is shape-agnostic): the same
 // arithmetic with the row re-read from memory in every pass instead of held in four registers per lane -- a lane still owns
 // t = lane, lane + 64, ... and sums them in that order, so for T <= 256 both kernels produce bit-identical results.
-template <typename LT>
+template <typename LT, bool WLAST = false>
 __global__ __launch_bounds__(256) void loss_long_kernel(const float* __restrict__ out, int so, const LT* __restrict__ label,
                                                         const long* __restrict__ uid, const float* __restrict__ delta,
                                                         long n_delta, float alpha, int B, int T, float* __restrict__ loss_sum,
-                                                        float* __restrict__ dout, int sd, float* __restrict__ ddelta, int* __restrict__ err) {
+                                                        float* __restrict__ dout, int sd, float* __restrict__ ddelta, int* __restrict__ err,
+                                                        float wlast, float inv_n) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -423,7 +439,7 @@ __global__ __launch_bounds__(256) void loss_long_kernel(const float* __restrict_
         id = id < 0 ? 0 : n_delta - 1;
     }
     const float dl = delta[id];
-    const float inv = 1.0f / ((float)B * (float)T);
+    const float inv = WLAST ? inv_n : 1.0f / ((float)B * (float)T);
     const float* ob = out + (long)b * T * so;
     const LT* yb = label + (long)b * T;
     float* gb = dout + (long)b * T * sd;
@@ -435,7 +451,10 @@ __global__ __launch_bounds__(256) void loss_long_kernel(const float* __restrict_
         const float shift = term ? dl : 0.f;
         const float wt = term ? alpha : 1.0f - alpha;
         float se = 0.f;
-        for (int t = lane; t < T; t += 64) se += __expf((ob[(long)t * so] + shift) - (mx + shift));
+        for (int t = lane; t < T; t += 64) {
+            const float ex = __expf((ob[(long)t * so] + shift) - (mx + shift));
+            if (WLAST) se += (t == T - 1 ? wlast : 1.f) * ex; else se += ex;
+        }
         se = wave_sum64(se);
         const float rse = 1.0f / se;
         float pdp = 0.f, lsum = 0.f;
@@ -443,8 +462,14 @@ __global__ __launch_bounds__(256) void loss_long_kernel(const float* __restrict_
             const float p = __expf((ob[(long)t * so] + shift) - (mx + shift)) * rse;
             const float y = (float)yb[t];
             const float lp = fmaxf(__logf(p), -100.f), l1p = fmaxf(__logf(1.0f - p), -100.f);
-            lsum += -(y * lp + (1.0f - y) * l1p);
-            pdp += p * ((p - y) / fmaxf(p * (1.0f - p), 1e-12f));
+            if (WLAST) {
+                const float w = t == T - 1 ? wlast : 1.f;
+                lsum += w * -(y * lp + (1.0f - y) * l1p);
+                pdp += (w * p) * ((p - y) / fmaxf(p * (1.0f - p), 1e-12f));
+            } else {
+                lsum += -(y * lp + (1.0f - y) * l1p);
+                pdp += p * ((p - y) / fmaxf(p * (1.0f - p), 1e-12f));
+            }
         }
         pdp = wave_sum64(pdp);
         lsum = wave_sum64(lsum);
@@ -454,7 +479,7 @@ __global__ __launch_bounds__(256) void loss_long_kernel(const float* __restrict_
             const float p = __expf((ob[(long)t * so] + shift) - (mx + shift)) * rse;
             const float y = (float)yb[t];
             const float dp = (p - y) / fmaxf(p * (1.0f - p), 1e-12f);
-            const float gg = wt * inv * p * (dp - pdp);
+            const float gg = wt * inv * ((WLAST && t == T - 1) ? wlast * p : p) * (dp - pdp);
             gs += gg;
             // this lane wrote element t in term 0 and is the only one to touch it: plain read-modify-write in term 1
             if (sd == 4) *reinterpret_cast<f32x4*>(gb + (long)t * 4) = f32x4{term ? gb[(long)t * 4] + gg : gg, 0.f, 0.f, 0.f};
@@ -476,18 +501,43 @@ hipError_t loss_launch(const float* out, int out_stride, const void* label, int 
     if (T > 256 || (force_long && force_long[0] == '1')) {
         if (label_is_f64)
             hipLaunchKernelGGL(loss_long_kernel<double>, dim3((B + 3) / 4), dim3(256), 0, st, out, out_stride, (const double*)label, uid,
-                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err);
+                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, 1.f, 0.f);
         else
             hipLaunchKernelGGL(loss_long_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, st, out, out_stride, (const float*)label, uid,
-                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err);
+                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, 1.f, 0.f);
         return hipGetLastError();
     }
     if (label_is_f64)
         hipLaunchKernelGGL(loss_kernel<double>, dim3((B + 3) / 4), dim3(256), 0, st, out, out_stride, (const double*)label, uid, delta,
-                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err);
+                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, 1.f, 0.f);
     else
         hipLaunchKernelGGL(loss_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, st, out, out_stride, (const float*)label, uid, delta,
-                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err);
+                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, 1.f, 0.f);
+    return hipGetLastError();
+}
+
+// one group of the compacted candidate arena (section 5f): every impression has T columns, the last one weighted by wlast; inv_n = 1 / rows of the batch
+hipError_t loss_wlast_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,
+                             long n_delta, float alpha, int B, int T, float wlast, float inv_n, float* loss_sum, float* dout, int dout_stride,
+                             float* ddelta, int* err, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    const char* force_long = getenv("NRM_LOSS_LONG");
+    const dim3 grid((B + 3) / 4), block(256);
+    if (T > 256 || (force_long && force_long[0] == '1')) {
+        if (label_is_f64)
+            hipLaunchKernelGGL((loss_long_kernel<double, true>), grid, block, 0, st, out, out_stride, (const double*)label, uid,
+                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, wlast, inv_n);
+        else
+            hipLaunchKernelGGL((loss_long_kernel<float, true>), grid, block, 0, st, out, out_stride, (const float*)label, uid,
+                               delta, n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, wlast, inv_n);
+        return hipGetLastError();
+    }
+    if (label_is_f64)
+        hipLaunchKernelGGL((loss_kernel<double, true>), grid, block, 0, st, out, out_stride, (const double*)label, uid, delta,
+                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, wlast, inv_n);
+    else
+        hipLaunchKernelGGL((loss_kernel<float, true>), grid, block, 0, st, out, out_stride, (const float*)label, uid, delta,
+                           n_delta, alpha, B, T, loss_sum, dout, dout_stride, ddelta, err, wlast, inv_n);
     return hipGetLastError();
 }
 

@@ -25,6 +25,9 @@ hipError_t rowdot_wlast_launch(const float* g, long gsb, int ldg, const float* h
 hipError_t loss_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,
                        long n_delta, float alpha, int B, int T, float* loss_sum, float* dout, int dout_stride, float* ddelta, int* err,
                        hipStream_t st);
+hipError_t loss_wlast_launch(const float* out, int out_stride, const void* label, int label_is_f64, const long* uid, const float* delta,
+                             long n_delta, float alpha, int B, int T, float wlast, float inv_n, float* loss_sum, float* dout, int dout_stride,
+                             float* ddelta, int* err, hipStream_t st);
 hipError_t adam_launch(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                        float wd, int step, int zero_grad, hipStream_t st);
 hipError_t adam_dev_launch(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,

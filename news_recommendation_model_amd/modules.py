@@ -187,8 +187,13 @@ class UserInvariantInterestModel(nn.Module):
     def forward_parts_grouped(self, x_history_arena, x_target, plan):
         """forward_parts on length groups: ``x_history_arena`` [R, cols] are the plan's kept history rows
         (``ops.history_gather_groups``), ``x_target`` [B, T, cols] is in the plan's SORTED order; -> the same four blocks in sorted order.
-        The front end and w1 are row-wise and run on the R rows unchanged; only the two attention + pool nodes know about the groups."""
+        The front end and w1 are row-wise and run on the R rows unchanged; only the two attention + pool nodes know about the groups.
+        A plan that carries candidate groups (``plan.cand``) takes ``x_target`` as the candidate arena [N, cols]
+        (``ops.candidate_gather_groups``) and returns the four blocks as arena rows [N, width]."""
         ops._require_gpu(x_history_arena, x_target)
+        cand = getattr(plan, "cand", None)
+        if cand is not None:
+            return self._forward_parts_cgrouped(x_history_arena, x_target, plan, cand)
         B, T = x_target.shape[0], x_target.shape[1]
         if x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or B != plan.B or B * T == 0 or plan.R == 0:
             raise RuntimeError(f"forward_grouped: plan for {plan.B} impressions / {plan.R} kept history rows, got a history arena "
@@ -211,6 +216,45 @@ class UserInvariantInterestModel(nn.Module):
 
         # two streams as in forward_parts; the choice goes by the z elements the groups really have
         side = ops.branch_stream(lab_t) if self.uses_two_streams(plan.R * T * lab_h.shape[1]) else None
+        if side is not None:
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            ti_t.record_stream(side)
+            ti_h.record_stream(side)
+            with torch.cuda.stream(side):
+                pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
+            pooled_lab = attend(self.label_attention, lab_t, lab_h)
+            main.wait_stream(side)
+            pooled_ti.record_stream(main)
+        else:
+            pooled_lab = attend(self.label_attention, lab_t, lab_h)
+            pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
+        return pooled_lab, pooled_ti, lab_t, ti_t
+
+    def _forward_parts_cgrouped(self, x_history_arena, x_target_arena, plan, cand):
+        """forward_parts_grouped on groups trimmed in the candidate axis too: every layer up to the attention is row-wise in the candidate
+        and runs on the N arena rows."""
+        if (x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or x_target_arena.dim() != 2 or x_target_arena.shape[0] != cand.N
+                or cand.B != plan.B or cand.N == 0 or plan.R == 0):
+            raise RuntimeError(f"forward_grouped: plan for {plan.R} kept history rows / {cand.N} candidate rows, got a history arena "
+                               f"{tuple(x_history_arena.shape)} and a candidate arena {tuple(x_target_arena.shape)}")
+        if not self.grouped_attention_applies():
+            raise RuntimeError("forward_grouped: an attention of this model does not take the fused attention + pool node (feature width "
+                               "not a multiple of 4, a non-GELU MLP or a substituted module): run the dense forward")
+        sen = self.sentiment_embedding[0]
+        lab_h, ti_h, lab_t, ti_t = ops.frontend_pair_fwd(
+            x_history_arena, x_target_arena, int(self._dims.n_subcat), int(self._dims.pca_vector),
+            self.category_embedding[0].weight, sen.weight, sen.bias, self.type_embedding[0].weight, self.year_embedding[0].weight,
+            self.month_embedding[0].weight, self.day_embedding[0].weight, self.hour_embedding[0].weight)
+        ti_h, ti_t = ti_h.detach(), ti_t.detach()
+        lab_h = ops.linear(lab_h, self.w1.weight, self.w1.bias)                                       # [R, D_l]
+
+        def attend(att, t, h):
+            m = att.mlp
+            return ops.attend_and_pool_cgrouped(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, plan, mma=att.mma)
+
+        z_rows = sum(int(n) * int(tg) * int(hg) for n, tg, hg in zip(plan.bounds[1:] - plan.bounds[:-1], cand.T_g, plan.H_g))
+        side = ops.branch_stream(lab_t) if self.uses_two_streams(z_rows * lab_h.shape[1]) else None
         if side is not None:
             main = torch.cuda.current_stream()
             side.wait_stream(main)
@@ -336,17 +380,17 @@ class UserModel(nn.Module):
             e = ops.concat_last((eu_H, eu_L, ec))
         return self._head(e)
 
-    def _head(self, e):
-        """BatchNorm gate -> MLP -> MLP on the concatenated rows e [B, T, width] -> logits [B, T] (:32-34)."""
-        B, T, N = e.shape
-        rows = e.reshape(B * T, N)
+    def _head(self, e, row_weight=None, n_rows=None):
+        """BatchNorm gate -> MLP -> MLP on the concatenated rows e [B, T, width] -> logits [B, T] (:32-34).  With ``row_weight`` [N] (DESIGN.md
+        section 5f) e is the [N, width] rows of a candidate arena that stand for ``n_rows`` = B * T rows; -> logits [N]."""
+        rows = e.reshape(-1, e.shape[-1])
         g = self.gate
         if isinstance(g.activation, nn.GELU) and g.activation.approximate == "none":
             # BatchNorm -> gate MLP -> product with the RAW concat as one autograd node
-            gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias)
+            gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias, row_weight, n_rows)
         else:
-            gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)     # the gate multiplies the RAW concat
-        return self._tail(gated).reshape(B, T)
+            gated = g.forward_times(ops.batch_norm(rows, self.bn, row_weight, n_rows), rows)     # the gate multiplies the RAW concat
+        return self._tail(gated).reshape(e.shape[:-1])
 
     def compact_history_applies(self):
         """Whether ``forward_grouped`` can stand in for ``forward``: the plain invariant-interest model (not hooked, not substituted)
@@ -357,7 +401,22 @@ class UserModel(nn.Module):
         return (type(inv) is UserInvariantInterestModel and not (inv._forward_hooks or inv._forward_pre_hooks)
                 and inv.grouped_attention_applies())
 
-    def forward_grouped(self, x_history_arena, x_target_sorted, x_global_sorted, plan):
+    def compact_candidates_applies(self):
+        """Whether ``forward_grouped`` with a plan that carries candidate groups can stand in for a training ``forward`` (DESIGN.md section
+        5f): what ``compact_history_applies`` asks, a BatchNorm configuration and width the column kernels take (the ``nn.BatchNorm1d``
+        fallback has no row-weight form), and the exact-GELU gate."""
+        g = self.gate
+        return (self.compact_history_applies() and type(self.bn) is nn.BatchNorm1d and ops.bn_column_kernels_apply(self.bn, self.bn.num_features)
+                and not (self.bn._forward_hooks or self.bn._forward_pre_hooks)
+                and isinstance(g, MLP) and isinstance(g.activation, nn.GELU) and g.activation.approximate == "none"
+                and g.fc2.weight.shape[0] == self.bn.num_features)
+
+    def loss_grouped(self, id_sorted, out_arena, label_arena, cand, alpha=0.95):
+        """``loss`` of the dense [B, T] batch from the arena logits of ``forward_grouped`` (``cand``: the plan's ``CandidateGroupPlan``;
+        ``id_sorted`` [B] in its sorted order, ``label_arena`` [N] from ``ops.candidate_gather_groups``)."""
+        return ops.softmax_bce_loss_grouped(out_arena, self.delta, label_arena, id_sorted, cand, alpha)
+
+    def forward_grouped(self, x_history_arena, x_target_sorted, x_global_sorted, plan, row_weight=None):
         """forward() on histories cut into length groups, training or eval mode.  ``plan`` is a
         ``compact.HistoryGroupPlan``; ``x_history_arena`` [R, cols] its kept history rows (``ops.history_gather_groups``), ``x_target_sorted``
         / ``x_global_sorted`` the batch's rows in the plan's sorted order (``index_select`` with ``plan.perm``).  -> logits [B, T] in SORTED
@@ -366,7 +425,15 @@ class UserModel(nn.Module):
         w_g in place of w_g equal addends in the pool)."""
         pooled_lab, pooled_ti, lab_t, ti_t = self.invariant_interest_model.forward_parts_grouped(x_history_arena, x_target_sorted, plan)
         eu_L = self.instant_interest_model(x_global_sorted)
-        return self._head(ops.concat_last((pooled_lab, pooled_ti, eu_L, lab_t, ti_t)))
+        cand = getattr(plan, "cand", None)
+        if cand is None:
+            return self._head(ops.concat_last((pooled_lab, pooled_ti, eu_L, lab_t, ti_t)))
+        # candidate groups (section 5f): x_target_sorted / x_global_sorted are the candidate ARENAS [N, cols], row_weight [N] their row
+        # weights (ops.candidate_gather_groups); -> logits [N] in arena order.  Training-mode BatchNorm takes its statistics with the
+        # weights over the cand.B * cand.T rows the dense forward sees; eval mode is row-wise and ignores them.
+        if row_weight is None or row_weight.shape[0] != cand.N:
+            raise RuntimeError(f"forward_grouped: a plan with candidate groups needs the arena's row weights [{cand.N}]")
+        return self._head(ops.concat_last((pooled_lab, pooled_ti, eu_L, lab_t, ti_t)), row_weight, cand.B * cand.T)
 
     def forward_compact(self, x_history, xt_compact, xg_compact, plan):
         """Inference on ragged candidate lists (compact scoring path): ``xt_compact`` [N, cols] and

@@ -79,6 +79,11 @@ SIGNATURES = {
     "nrm_history_gather_groups": (_c_i, [_c_fp, _c_i, _c_i] + [_c_fp] * 4 + [_c_i] * 4 + [_c_fp, _c_fp]),
     "nrm_pool_bmm_wlast": (_c_i, [_c_fp, _c_l, _c_l, _c_l, _c_fp, _c_i, _c_fp] + [_c_i] * 5 + [ctypes.c_float, _c_i, _c_fp]),
     "nrm_pool_rowdot_wlast": (_c_i, [_c_fp, _c_i, _c_fp, _c_fp] + [_c_i] * 4 + [_c_fp, _c_i, ctypes.c_float, _c_fp]),
+    "nrm_candidate_gather_groups": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_fp, _c_i] + [_c_fp] * 4 + [_c_i] * 4 + [_c_fp] * 6),
+    "nrm_colreduce_roww": (_c_i, [_c_i] + [_c_fp] * 4 + [_c_i] * 3 + [_c_fp]),
+    "nrm_bn_backward_roww": (_c_i, [_c_fp] * 10 + [_c_i] * 4 + [_c_fp]),
+    "nrm_loss_fwd_bwd_wlast": (_c_i, [_c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp, _c_l, ctypes.c_float, _c_i, _c_i, ctypes.c_float, ctypes.c_float,
+                                      _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp]),
     "nrm_ensemble_rank_ragged": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i] + [_c_fp] * 5),     # the first two: HOST arrays
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,

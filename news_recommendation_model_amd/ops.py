@@ -492,23 +492,27 @@ def _attn_operands(t, h, w1, b1, w2, b2, mma):
 # The training nodes work on a list of (B_g, T, H_g) blocks (DESIGN.md section 5e): block g -- impressions b0[g] .. b0[g + 1] - 1, each with
 # hg[g] history rows, from row r_lo of the history rows h [R, D] -- runs through the DENSE forward and backward kernels with H = hg[g].  Only
 # the pool knows that where hg[g] < H the block's last row stands for w_g = H - hg[g] + 1 equal rows.  The dense nodes are the one-block case.
-def _group_layout(b0, hg, T):
-    """[(b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo)] per group and the totals (R, S, Z): r = rows of the arena, s = floats of the score buffer
-    (a group's [B_g, T, H_g] block starts on a 256-byte boundary), z = score elements before the group (its z block starts at z_lo * D)."""
+def _group_layout(b0, hg, T, tg=None):
+    """[(b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo, T_g, t_lo)] per group and the totals (R, S, Z): r = rows of the history arena, s = floats of
+    the score buffer (a group's [B_g, T_g, H_g] block starts on a 256-byte boundary), z = score elements before the group (its z block starts
+    at z_lo * D), t = rows of the candidate arena.  ``tg``: the candidate columns each group keeps; None: all T, the
+    candidate rows are then the [B * T] rows of the sorted batch (t_lo = b_lo * T)."""
     b0, hg = [int(x) for x in b0], [int(x) for x in hg]
-    if len(b0) != len(hg) + 1 or b0[0] != 0 or any(b0[g + 1] <= b0[g] for g in range(len(hg))) or any(x < 1 for x in hg):
-        raise RuntimeError(f"grouped attention: group bounds {b0} / heights {hg} are not a partition into non-empty groups")
-    out, r, sf, zr = [], 0, 0, 0
-    for g, H_g in enumerate(hg):
+    tg = [int(T)] * len(hg) if tg is None else [int(x) for x in tg]
+    if (len(b0) != len(hg) + 1 or len(tg) != len(hg) or b0[0] != 0 or any(b0[g + 1] <= b0[g] for g in range(len(hg))) or any(x < 1 for x in hg)
+            or any(not 1 <= x <= T for x in tg)):
+        raise RuntimeError(f"grouped attention: group bounds {b0} / heights {hg} / widths {tg} (T = {T}) are not a partition into non-empty groups")
+    out, r, sf, zr, tr = [], 0, 0, 0, 0
+    for g, (H_g, T_g) in enumerate(zip(hg, tg)):
         n = b0[g + 1] - b0[g]
-        out.append((b0[g], b0[g + 1], H_g, r, r + n * H_g, sf, zr))
-        r, sf, zr = r + n * H_g, (sf + n * T * H_g + 63) // 64 * 64, zr + n * T * H_g
+        out.append((b0[g], b0[g + 1], H_g, r, r + n * H_g, sf, zr, T_g, tr))
+        r, sf, zr, tr = r + n * H_g, (sf + n * T_g * H_g + 63) // 64 * 64, zr + n * T_g * H_g, tr + n * T_g
     return out, r, sf, zr
 
 
 def _one_group(B, T, H):
     """_group_layout of a dense [B, T, H] node: one group of full height at offset 0 of every buffer, its score buffer exactly B*T*H floats."""
-    return [(0, B, H, 0, B * H, 0, 0)], B * H, B * T * H, B * T * H
+    return [(0, B, H, 0, B * H, 0, 0, T, 0)], B * H, B * T * H, B * T * H
 
 
 def _pool_bmm(s, s_b, s_i, s_j, x, ldx, out, B, I, J, D, accumulate, wlast, wlast_row, st):
@@ -532,29 +536,30 @@ def _pool_rowdot(g, ldg, h, ds, B, T, H, D, acc, wlast, st):
 
 
 def _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, pool):
-    """The training forward of every attention node.  t [B, T, D], h: the R history rows of ``groups`` (with S, Z: _group_layout's or
-    _one_group's).  ONE u GEMM over the R rows and ONE v GEMM over the B*T rows; per block the dense forward
+    """The training forward of every attention node.  t [B, T, D] (or the candidate arena [N, D] of groups that keep T_g columns each), h:
+    the R history rows of ``groups`` (with S, Z: _group_layout's or _one_group's).  ONE u GEMM over the R rows and ONE v GEMM over the
+    candidate rows; per block the dense forward
     s[b,t,h] = fc2(GELU(fc1(cat[h, t, t-h, t*h]))), fc1 = [W_h|W_t|W_d|W_p] re-associated as
     z = h(W_h-W_d)^T + b1 + t(W_t+W_d)^T + sum_d W_p[:,d] t_d h_d  (SURVEY.md §8 a7), on pointer-offset views and, with ``pool``,
     pooled[b,t,:] = sum_h s[b,t,h] h[b,h,:] with the weighted last row.  -> (pooled [B, T, D] or None, s [S], z [Z * D] or empty);
     s is UNWEIGHTED (the weight is applied where the pool reads it)."""
     if save_z:
         _chain["end"] = None               # a training forward: whatever an earlier backward left there is stale (see _chain below)
-    B, T, D = t.shape
+    shape_t, D = tuple(t.shape), t.shape[-1]
     t, h, u, v, packed, w2v, b2 = _attn_operands(t, h, w1, b1, w2, b2, mma)
     dev, st = t.device, native.stream_ptr()
     s = torch.empty(S, dtype=torch.float32, device=dev)
     z = torch.empty(Z * D if save_z else 0, dtype=torch.float32, device=dev)
-    pooled = torch.empty(B, T, D, dtype=torch.float32, device=dev) if pool else None
-    for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
+    pooled = torch.empty(t.shape[0], D, dtype=torch.float32, device=dev) if pool else None
+    for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo, T_g, t_lo in groups:
         n = b_hi - b_lo
-        _count_flops("contraction", 2.0 * n * T * H_g * D * D)
-        native.call("nrm_pwattn_fwd", native.ptr(t[b_lo * T:]), native.ptr(h[r_lo:]), native.ptr(u[r_lo:]), native.ptr(v[b_lo * T:]),
+        _count_flops("contraction", 2.0 * n * T_g * H_g * D * D)
+        native.call("nrm_pwattn_fwd", native.ptr(t[t_lo:]), native.ptr(h[r_lo:]), native.ptr(u[r_lo:]), native.ptr(v[t_lo:]),
                     native.ptr(packed), native.ptr(w2v), native.ptr(b2), native.ptr(z[z_lo * D:]) if save_z else None, native.ptr(s[s_lo:]),
-                    n, T, H_g, D, mma, st)
+                    n, T_g, H_g, D, mma, st)
         if pool:
-            _pool_bmm(s[s_lo:], T * H_g, H_g, 1, h[r_lo:], D, pooled[b_lo:], n, T, H_g, D, 0, H - H_g + 1, 0, st)
-    return pooled, s, z
+            _pool_bmm(s[s_lo:], T_g * H_g, H_g, 1, h[r_lo:], D, pooled[t_lo:], n, T_g, H_g, D, 0, H - H_g + 1, 0, st)
+    return (pooled.view(shape_t) if pool else None), s, z
 
 
 def _attn_dense_fwd(t, h, w1, b1, w2, b2, save_z, mma, pool):
@@ -687,10 +692,10 @@ def _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, ds=No
     reference, where those products are never formed -- and the (b,h)-grouped contraction pass, the two side-projection GEMMs and the dt
     epilogue are skipped: the weight gradients only need dz, du, dv and the dW_p pass.  Skipped gradients are returned as empty tensors.
     -> (dt [B, T, D], dh [R, D], dw1 [D, 4D], db1 [D], acc [D + 4] = dw2 | db2 | pad)"""
-    B, T, D = t.shape
+    shape_t, D = tuple(t.shape), t.shape[-1]
     st = native.stream_ptr()
     w1_arg = w1
-    t, h, w1 = _f32c(t), _f32c(h).reshape(-1, D), _f32c(w1)
+    t, h, w1 = _f32c(t).reshape(-1, D), _f32c(h).reshape(-1, D), _f32c(w1)
     own = w1 if w1 is w1_arg else None
     w2v = _f32c(w2).reshape(-1)
     z = z.view(-1)
@@ -703,37 +708,40 @@ def _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, ds=No
         ds = _f32c(ds).reshape(-1)
         acc = torch.zeros(D + 4, dtype=torch.float32, device=dev)
     else:
-        g, ldg, s = pool[0], pool[1], _f32c(pool[2]).reshape(-1)
+        g, ldg, s = pool[0].flatten(0, -2), pool[1], _f32c(pool[2]).reshape(-1)      # g: the candidate rows, row stride ldg (a view)
         acc = torch.empty(D + 4, dtype=torch.float32, device=dev)
     dw2, db2 = acc[:D], acc[D:D + 1]                   # the dz pass accumulates both; returned as ONE tensor
     du = torch.empty(h.shape[0], D, dtype=torch.float32, device=dev)
-    dv = torch.empty(B, T, D, dtype=torch.float32, device=dev)
-    for i, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in enumerate(groups):
+    dv = torch.empty(t.shape[0], D, dtype=torch.float32, device=dev)
+    for i, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo, T_g, t_lo) in enumerate(groups):
         n = b_hi - b_lo
+        t_hi = t_lo + n * T_g
         if pool is None:
             ds_g = ds[s_lo:]
         else:
-            ds_g = torch.empty(n, T, H_g, dtype=torch.float32, device=dev)
-            _pool_rowdot(g[b_lo:b_hi], ldg, h[r_lo:r_hi], ds_g, n, T, H_g, D, acc if i == 0 else None, H - H_g + 1, st)
+            ds_g = torch.empty(n, T_g, H_g, dtype=torch.float32, device=dev)
+            _pool_rowdot(g[t_lo:t_hi], ldg, h[r_lo:r_hi], ds_g, n, T_g, H_g, D, acc if i == 0 else None, H - H_g + 1, st)
         native.call("nrm_pwattn_bwd_dz", native.ptr(z[z_lo * D:]), native.ptr(ds_g), native.ptr(w2v), native.ptr(dw2), native.ptr(db2),
-                    native.ptr(du[r_lo:r_hi]), native.ptr(dv[b_lo:b_hi]), n, T, H_g, D, DZ_HL4 if rw else DZ_F32, st)
-    dw1, db1, dh, dt = _attn_bwd_once(du, dv.reshape(B * T, D), h, t.reshape(B * T, D), w1, w1_arg, own, mma, need_dt, need_dh)
-    if need_dt:
-        dt = dt.reshape(B, T, D)
-    nsplits = [lib.nrm_pwattn_bwd_nsplit(b_hi - b_lo, T, H_g, D, mma) for b_lo, b_hi, H_g, *_ in groups]
+                    native.ptr(du[r_lo:r_hi]), native.ptr(dv[t_lo:t_hi]), n, T_g, H_g, D, DZ_HL4 if rw else DZ_F32, st)
+    dw1, db1, dh, dt = _attn_bwd_once(du, dv, h, t, w1, w1_arg, own, mma, need_dt, need_dh)
+    nsplits = [lib.nrm_pwattn_bwd_nsplit(b_hi - b_lo, T_g, H_g, D, mma) for b_lo, b_hi, H_g, _r, _rh, _s, _z, T_g, _t in groups]
     wsp = torch.empty(sum(nsplits), D, D, dtype=torch.float32, device=dev)
     k = 0
-    for ns, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo) in zip(nsplits, groups):
+    for ns, (b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo, T_g, t_lo) in zip(nsplits, groups):
         n = b_hi - b_lo
-        _attn_bwd_contract(lib, z[z_lo * D:], t[b_lo:b_hi], h[r_lo:r_hi].view(n, H_g, D), w1, dt[b_lo:b_hi] if need_dt else dt,
+        t_hi = t_lo + n * T_g
+        _attn_bwd_contract(lib, z[z_lo * D:], t[t_lo:t_hi].view(n, T_g, D), h[r_lo:r_hi].view(n, H_g, D), w1, dt[t_lo:t_hi] if need_dt else dt,
                            dh[r_lo:r_hi].view(n, H_g, D) if need_dh else dh, wsp[k:k + ns], mma, rw, need_dt, need_dh, st, Z * D)
         k += ns
     if need_dt or need_dh:
         _note_chain_end()                              # the last contraction of a backward that produced a row gradient
     _slab_reduce(wsp, sum(nsplits), D, D, D, dw1[:, 3 * D:], 4 * D, 1, target=w1_arg)    # slabs hold dW_p^T: ws[s][d][k] -> dw1[k, 3D + d]
     if pool is not None and need_dh:
-        for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo in groups:
-            _pool_bmm(s[s_lo:], T * H_g, 1, H_g, g[b_lo:b_hi], ldg, dh[r_lo:r_hi], b_hi - b_lo, H_g, T, D, 1, H - H_g + 1, 1, st)
+        for b_lo, b_hi, H_g, r_lo, r_hi, s_lo, z_lo, T_g, t_lo in groups:
+            n = b_hi - b_lo
+            _pool_bmm(s[s_lo:], T_g * H_g, 1, H_g, g[t_lo:t_lo + n * T_g], ldg, dh[r_lo:r_hi], n, H_g, T_g, D, 1, H - H_g + 1, 1, st)
+    if need_dt:
+        dt = dt.reshape(shape_t)
     return dt, dh, dw1, db1, acc
 
 
@@ -869,7 +877,7 @@ def _attention_node(fwd_name, bwd_op, n_extra, has_pool, recompute):
         need_dt, need_dh = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
         dt, dh, dw1, db1, dw2b2 = bwd_op(grad, t, h, w1, w2, *s, _consume_z(ctx, z, t, h, w1, b1, w2, recompute), *ctx.extra, ctx.mma,
                                          need_dt, need_dh)
-        D = t.shape[2]
+        D = t.shape[-1]
         return ((dt if need_dt else None), (dh if need_dh else None), dw1, db1, dw2b2[:D].reshape(ctx.w2_shape),
                 dw2b2[D:D + 1].reshape(ctx.b2_shape)) + (None,) * n_extra
 
@@ -1416,10 +1424,19 @@ def head_tail(x, w1, b1, wm, bm, wo, bo, w3, b3):
 
 
 # ------------------------------------------------------------------------------------------------ BatchNorm1d
-def _bn_stats_impl(x, running_mean, running_var, momentum, eps):
+def _row_weight(row_weight, n_rows, R):
+    """The fp32 row-weight vector [R] of a launch over R rows that stand for ``n_rows`` >= R rows of the batch."""
+    w = _f32c(row_weight)
+    if w.dim() != 1 or w.shape[0] != R or not R <= int(n_rows) < 2 ** 31:
+        raise RuntimeError(f"row weights {tuple(w.shape)} for {R} rows that stand for n_rows={n_rows} (needs [R] weights, R <= n_rows < 2^31)")
+    return w
+
+
+def _bn_stats_impl(x, running_mean, running_var, momentum, eps, row_weight=None, n_rows=0):
     """Train-mode statistics of the [R, N] rows: mean, rstd = 1/sqrt(biased var + eps) (two-pass variance), and the
     running-statistics update of nn.BatchNorm1d (unbiased variance, momentum) in place -- two column reductions and
-    two finalisation launches, no ATen arithmetic."""
+    two finalisation launches, no ATen arithmetic.  With ``row_weight`` [R] row r stands for that many equal rows of a batch of
+    ``n_rows`` rows: weighted sums, finalised with n_rows."""
     _require_gpu(x, running_mean, running_var)
     x = _rows(x)
     R, N = x.shape
@@ -1429,6 +1446,13 @@ def _bn_stats_impl(x, running_mean, running_var, momentum, eps):
     s = torch.zeros(2, N, dtype=torch.float32, device=dev)
     mean = torch.empty(N, dtype=torch.float32, device=dev)
     rstd = torch.empty(N, dtype=torch.float32, device=dev)
+    if row_weight is not None:
+        w, n = _row_weight(row_weight, n_rows, R), int(n_rows)
+        native.call("nrm_colreduce_roww", 0, native.ptr(x), None, native.ptr(w), native.ptr(s[0]), R, N, ld, st)
+        native.call("nrm_bn_finalize", 0, native.ptr(s[0]), native.ptr(mean), native.ptr(running_mean), n, N, float(momentum), float(eps), st)
+        native.call("nrm_colreduce_roww", 1, native.ptr(x), native.ptr(mean), native.ptr(w), native.ptr(s[1]), R, N, ld, st)
+        native.call("nrm_bn_finalize", 1, native.ptr(s[1]), native.ptr(rstd), native.ptr(running_var), n, N, float(momentum), float(eps), st)
+        return mean, rstd
     native.call("nrm_colreduce", 0, native.ptr(x), None, None, None, native.ptr(s[0]), None, R, N, ld, st)
     native.call("nrm_bn_finalize", 0, native.ptr(s[0]), native.ptr(mean), native.ptr(running_mean), R, N, float(momentum), float(eps), st)
     native.call("nrm_colreduce", 1, native.ptr(x), None, native.ptr(mean), None, native.ptr(s[1]), None, R, N, ld, st)
@@ -1440,6 +1464,10 @@ batch_norm_stats = _op("batch_norm_stats", "(Tensor x, Tensor(a!) running_mean, 
                        "(Tensor, Tensor)", _bn_stats_impl,
                        lambda x, rm, rv, momentum, eps: (x.new_empty((x.shape[1],), dtype=torch.float32),
                                                          x.new_empty((x.shape[1],), dtype=torch.float32)))
+batch_norm_stats_roww = _op("batch_norm_stats_roww", "(Tensor x, Tensor(a!) running_mean, Tensor(b!) running_var, float momentum, float eps, "
+                            "Tensor row_weight, int n_rows) -> (Tensor, Tensor)", _bn_stats_impl,
+                            lambda x, rm, rv, momentum, eps, row_weight, n_rows: (x.new_empty((x.shape[1],), dtype=torch.float32),
+                                                                                  x.new_empty((x.shape[1],), dtype=torch.float32)))
 
 
 def _bn_apply_impl(x, mean, rstd, weight, bias, batch_stats):
@@ -1458,7 +1486,9 @@ batch_norm_apply = _op("batch_norm_apply", "(Tensor x, Tensor mean, Tensor rstd,
                        _bn_apply_impl, lambda x, mean, rstd, weight, bias, batch_stats: _padded_empty(x, x.shape[0], x.shape[1]))
 
 
-def _bn_bwd_impl(dy, x, mean, rstd, weight, training, add=None):
+def _bn_bwd_impl(dy, x, mean, rstd, weight, training, add=None, row_weight=None, n_rows=0):
+    """``row_weight`` / ``n_rows`` (training only): dy carries the row weight already, so d gamma and d beta are the
+    plain sums; the two column terms of dx are multiplied by the row's weight and divided by the rows of the batch."""
     _require_gpu(dy, x)
     x = _rows(x)
     R, N = x.shape
@@ -1481,6 +1511,11 @@ def _bn_bwd_impl(dy, x, mean, rstd, weight, training, add=None):
         buf = torch.zeros(R, ld, dtype=torch.float32, device=dev)
         buf[:, :N] = add
         add = buf[:, :N]
+    if row_weight is not None:
+        native.call("nrm_bn_backward_roww", native.ptr(x), native.ptr(dy), native.ptr(mean), native.ptr(rstd), native.ptr(w),
+                    native.ptr(s0), native.ptr(s1), native.ptr(add) if add is not None else None, native.ptr(_row_weight(row_weight, n_rows, R)),
+                    native.ptr(dx), R, int(n_rows), N, ld, st)
+        return dx[:, :N], s1, s0
     native.call("nrm_bn_backward", native.ptr(x), native.ptr(dy), native.ptr(mean), native.ptr(rstd), native.ptr(w),
                 native.ptr(s0), native.ptr(s1), native.ptr(add) if add is not None else None, native.ptr(dx), R, N, ld,
                 1 if training else 0, st)
@@ -1512,17 +1547,58 @@ def _bn_backward(ctx, dy):
 
 torch.library.register_autograd("nrm::batch_norm_apply", _bn_backward, setup_context=_bn_setup, lib=_LIB)
 
+# the row-weight forms: the forward is batch_norm_apply's (row-wise once mean and rstd are known); the weights ride
+# along for the backward
+batch_norm_apply_roww = _op("batch_norm_apply_roww", "(Tensor x, Tensor mean, Tensor rstd, Tensor weight, Tensor bias, Tensor row_weight, int n_rows) "
+                            "-> Tensor", lambda x, mean, rstd, weight, bias, row_weight, n_rows: _bn_apply_impl(x, mean, rstd, weight, bias, True),
+                            lambda x, mean, rstd, weight, bias, row_weight, n_rows: _padded_empty(x, x.shape[0], x.shape[1]))
+batch_norm_bwd_roww = _op("batch_norm_bwd_roww", "(Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor weight, Tensor row_weight, int n_rows) -> "
+                          "(Tensor, Tensor, Tensor)",
+                          lambda dy, x, mean, rstd, weight, row_weight, n_rows: _bn_bwd_impl(dy, x, mean, rstd, weight, True, None, row_weight, n_rows),
+                          lambda dy, x, mean, rstd, weight, row_weight, n_rows: _bn_bwd_fake(dy, x, mean, rstd, weight, True))
 
-def batch_norm(x, bn):
+
+def _bn_roww_setup(ctx, inputs, output):
+    x, mean, rstd, weight, bias, row_weight, n_rows = inputs
+    ctx.n_rows = n_rows
+    ctx.save_for_backward(x, mean, rstd, weight, row_weight)
+
+
+def _bn_roww_backward(ctx, dy):
+    x, mean, rstd, weight, row_weight = ctx.saved_tensors
+    dx, dgamma, dbeta = batch_norm_bwd_roww(dy, x, mean, rstd, weight, row_weight, ctx.n_rows)
+    return dx, None, None, dgamma, dbeta, None, None
+
+
+torch.library.register_autograd("nrm::batch_norm_apply_roww", _bn_roww_backward, setup_context=_bn_roww_setup, lib=_LIB)
+
+
+def bn_column_kernels_apply(bn, width):
+    """Whether ``batch_norm`` / ``gate_block`` run rows of ``width`` columns through the HIP column kernels (else: the module itself)."""
+    return not (width % 4 or not bn.affine or not bn.track_running_stats or bn.momentum is None)
+
+
+def batch_norm(x, bn, row_weight=None, n_rows=None):
     """nn.BatchNorm1d(x) for a 2-D x through the HIP column kernels.  Non-default module configurations
     (no affine / no running stats / cumulative momentum) and widths that are not a multiple of 4 use the
-    module itself."""
+    module itself.  ``row_weight`` [R] with ``n_rows`` (training mode): row r stands for row_weight[r] equal rows
+    of a batch of n_rows rows -- statistics, running statistics and gradients are those of the expanded batch; the module fallback has
+    no such form and raises."""
+    if row_weight is not None and not bn.training:
+        row_weight = None                                       # eval mode: running statistics, row-wise
     if (x.dim() != 2 or x.shape[1] % 4 or not bn.affine or not bn.track_running_stats or bn.momentum is None):
+        if row_weight is not None:
+            raise RuntimeError("batch_norm: row weights need the column kernels (2-D rows, a width that is a multiple of 4, the default "
+                               "nn.BatchNorm1d configuration)")
         return bn(x)
     training = bn.training
-    if x.shape[0] <= (1 if training else 0):
+    if row_weight is None and x.shape[0] <= (1 if training else 0):
         return bn(x)          # 0/1 rows in training: nn.BatchNorm1d raises its ValueError; 0 rows in eval: empty result
     _require_gpu(x, bn.weight)
+    if row_weight is not None:
+        bn.num_batches_tracked.add_(1)
+        mean, rstd = batch_norm_stats_roww(x.detach(), bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps), row_weight, int(n_rows))
+        return batch_norm_apply_roww(x, mean, rstd, bn.weight, bn.bias, row_weight, int(n_rows))
     if training:
         bn.num_batches_tracked.add_(1)
         mean, rstd = batch_norm_stats(x.detach(), bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
@@ -1551,9 +1627,9 @@ gate_block_fwd = _op("gate_block_fwd", "(Tensor x, Tensor mean, Tensor rstd, Ten
                      _gate_block_fwd_impl, _gate_block_fwd_fake)
 
 
-def _gate_block_bwd_impl(dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, batch_stats):
+def _gate_block_bwd_impl(dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, batch_stats, row_weight=None, n_rows=0):
     dc, dw1, db1, dw2, db2, dmul = _mlp_gelu_bwd_impl(dy, c, w1, w2, hidden, z, pre, x, has_b1, has_b2, True)
-    dx, dgamma, dbeta = _bn_bwd_impl(dc, x, mean, rstd, bn_w, batch_stats, add=dmul)
+    dx, dgamma, dbeta = _bn_bwd_impl(dc, x, mean, rstd, bn_w, batch_stats, add=dmul, row_weight=row_weight, n_rows=n_rows)
     return dx, dgamma, dbeta, dw1, db1, dw2, db2
 
 
@@ -1587,14 +1663,56 @@ def _gate_block_backward(ctx, dy, _dc, _dh, _dz, _dp):
 
 torch.library.register_autograd("nrm::gate_block_fwd", _gate_block_backward, setup_context=_gate_block_setup, lib=_LIB)
 
+# the row-weight form of the node (training on compacted candidate lists): batch statistics always
+gate_block_roww_fwd = _op("gate_block_roww_fwd", "(Tensor x, Tensor mean, Tensor rstd, Tensor bn_weight, Tensor bn_bias, Tensor fc1_weight, "
+                          "Tensor? fc1_bias, Tensor fc2_weight, Tensor? fc2_bias, Tensor row_weight, int n_rows) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+                          lambda x, mean, rstd, bn_w, bn_b, w1, b1, w2, b2, row_weight, n_rows:
+                          _gate_block_fwd_impl(x, mean, rstd, bn_w, bn_b, w1, b1, w2, b2, True),
+                          lambda x, mean, rstd, bn_w, bn_b, w1, b1, w2, b2, row_weight, n_rows:
+                          _gate_block_fwd_fake(x, mean, rstd, bn_w, bn_b, w1, b1, w2, b2, True))
+gate_block_roww_bwd = _op("gate_block_roww_bwd", "(Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor bn_weight, Tensor c, Tensor fc1_weight, "
+                          "Tensor fc2_weight, Tensor hidden, Tensor z, Tensor pre, bool has_b1, bool has_b2, Tensor row_weight, int n_rows) -> "
+                          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+                          lambda dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, row_weight, n_rows:
+                          _gate_block_bwd_impl(dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, True, row_weight, n_rows),
+                          lambda dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, row_weight, n_rows:
+                          _gate_block_bwd_fake(dy, x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, has_b1, has_b2, True))
 
-def gate_block(x, bn, fc1_weight, fc1_bias, fc2_weight, fc2_bias):
+
+def _gate_block_roww_setup(ctx, inputs, output):
+    x, mean, rstd, bn_w, bn_b, w1, b1, w2, b2, row_weight, n_rows = inputs
+    y, c, hidden, z, pre = output
+    ctx.set_materialize_grads(False)
+    ctx.flags = (b1 is not None, b2 is not None, n_rows)
+    ctx.save_for_backward(x, mean, rstd, bn_w, c, w1, w2, hidden, z, pre, row_weight)
+
+
+def _gate_block_roww_backward(ctx, dy, _dc, _dh, _dz, _dp):
+    if dy is None:
+        return (None,) * 11
+    has_b1, has_b2, n_rows = ctx.flags
+    *saved, row_weight = ctx.saved_tensors
+    dx, dgamma, dbeta, dw1, db1, dw2, db2 = gate_block_roww_bwd(dy, *saved, has_b1, has_b2, row_weight, n_rows)
+    return dx, None, None, dgamma, dbeta, dw1, (db1 if has_b1 else None), dw2, (db2 if has_b2 else None), None, None
+
+
+torch.library.register_autograd("nrm::gate_block_roww_fwd", _gate_block_roww_backward, setup_context=_gate_block_roww_setup, lib=_LIB)
+
+
+def gate_block(x, bn, fc1_weight, fc1_bias, fc2_weight, fc2_bias, row_weight=None, n_rows=None):
     """gate(bn(x)) * x for 2-D rows x (models/user_model.py:32-33; the gate is MLP with the default exact GELU).  Falls back to
-    the separate ops for BatchNorm configurations / widths the column kernels do not take."""
+    the separate ops for BatchNorm configurations / widths the column kernels do not take.  ``row_weight`` / ``n_rows``: as in
+    ``batch_norm`` (the gate MLP and the product are row-wise: only BatchNorm sees the weight)."""
+    if row_weight is not None and not bn.training:
+        row_weight = None
     if (x.dim() != 2 or x.shape[1] % 4 or not bn.affine or not bn.track_running_stats or bn.momentum is None
-            or x.shape[0] <= (1 if bn.training else 0) or fc2_weight.shape[0] != x.shape[1]):
-        return mlp_gelu(batch_norm(x, bn), fc1_weight, fc1_bias, fc2_weight, fc2_bias, mul=x)
+            or (row_weight is None and x.shape[0] <= (1 if bn.training else 0)) or fc2_weight.shape[0] != x.shape[1]):
+        return mlp_gelu(batch_norm(x, bn, row_weight, n_rows), fc1_weight, fc1_bias, fc2_weight, fc2_bias, mul=x)
     _require_gpu(x, bn.weight, fc1_weight)
+    if row_weight is not None:
+        bn.num_batches_tracked.add_(1)
+        mean, rstd = batch_norm_stats_roww(x.detach(), bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps), row_weight, int(n_rows))
+        return gate_block_roww_fwd(x, mean, rstd, bn.weight, bn.bias, fc1_weight, fc1_bias, fc2_weight, fc2_bias, row_weight, int(n_rows))[0]
     if bn.training:
         bn.num_batches_tracked.add_(1)
         mean, rstd = batch_norm_stats(x.detach(), bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
@@ -1833,6 +1951,70 @@ def attend_and_pool_grouped(target, history_arena, fc1_weight, fc1_bias, fc2_wei
     return attend_pool_grouped_fwd(*args, [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], int(plan.H), save_z, resolve_mma(mma))[0]
 
 
+#   The same node on groups that are trimmed in the candidate axis as well: group g keeps group_t[g] <= T candidate
+# columns, t is the candidate arena [N, D] (N = sum_g B_g T_g; compact.plan_candidate_groups + candidate_gather_groups).  The attention and
+# the pool are row-wise in the candidate: a group is the dense [B_g, T_g, H_g] problem, and nothing here knows the candidate weight.
+def _attend_pool_cgrouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
+    """t [N, D] (the candidate arena), h [R, D] (the history arena) -> (pooled [N, D], s [S], z [Z * D] or empty)."""
+    _require_gpu(t, h, w1, b1, w2, b2)
+    groups, R, S, Z = _group_layout(group_b0, group_h, T, group_t)
+    D = t.shape[-1]
+    N = groups[-1][8] + (groups[-1][1] - groups[-1][0]) * groups[-1][7]
+    if (t.dim() != 2 or t.shape[0] != N or h.dim() != 2 or h.shape[0] != R or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4
+            or max(group_h) > H):
+        raise RuntimeError(f"grouped attention: candidate arena {tuple(t.shape)}, history arena {tuple(h.shape)}, fc1 {tuple(w1.shape)}, groups of "
+                           f"{list(group_b0)} x {list(group_t)} x {list(group_h)} rows (T = {T}, H = {H}) do not agree (feature width must be a "
+                           "multiple of 4)")
+    return _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, True)
+
+
+def _attend_pool_cgrouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
+    _, _, S, Z = _group_layout(group_b0, group_h, T, group_t)
+    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
+    return f(*t.shape), f(S), f(Z * t.shape[1] if save_z else 0)
+
+
+attend_pool_cgrouped_fwd = _op("attend_pool_cgrouped_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
+                               "int[] group_b0, int[] group_h, int[] group_t, int H, int T, bool save_z, int mma) -> (Tensor, Tensor, Tensor)",
+                               _attend_pool_cgrouped_fwd_impl, _attend_pool_cgrouped_fwd_fake)
+
+
+def _attend_pool_cgrouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
+    """Backward of the candidate-grouped node from the pooled gradient g [N, D] (read in place when it is a column block of the head gradient)."""
+    _require_gpu(g, t, h, w1, w2, s, z)
+    groups, _, _, Z = _group_layout(group_b0, group_h, T, group_t)
+    g3, ldg = _pooled_grad_rows(g.unsqueeze(0), 1, t.shape[0], t.shape[1])
+    return _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, pool=(g3[0], ldg, s))
+
+
+def _attend_pool_cgrouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
+    N, D = t.shape
+    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
+    return (f(N, D) if need_dt else f(0)), (f(h.shape[0], D) if need_dh else f(0)), f(D, 4 * D), f(D), f(D + 4)
+
+
+attend_pool_cgrouped_bwd = _op("attend_pool_cgrouped_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
+                               "int[] group_b0, int[] group_h, int[] group_t, int H, int T, int mma, bool need_dt, bool need_dh) -> "
+                               "(Tensor, Tensor, Tensor, Tensor, Tensor)", _attend_pool_cgrouped_bwd_impl, _attend_pool_cgrouped_bwd_fake)
+
+
+_attention_node("attend_pool_cgrouped_fwd", attend_pool_cgrouped_bwd, 7, True, False)
+
+
+def attend_and_pool_cgrouped(target_arena, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
+    """The candidate arena [N, D] of ``plan.cand`` (a ``compact.CandidateGroupPlan`` cut along ``plan``'s groups) x the grouped history arena
+    [R, D] -> pooled [N, D]: row for row what ``attend_and_pool_grouped`` gives the kept cells of the sorted [B, T, D] batch."""
+    args = (target_arena, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
+    _require_gpu(*args)
+    cand = plan.cand
+    if target_arena.dim() != 2 or target_arena.shape[-1] % 4 or target_arena.shape[0] != cand.N or cand.N == 0:
+        raise RuntimeError(f"attend_and_pool_cgrouped: candidate arena {tuple(target_arena.shape)} for a plan of {cand.N} rows (needs [N, D], D a "
+                           "multiple of 4, N > 0)")
+    save_z = torch.is_grad_enabled() and any(a.requires_grad for a in args)
+    return attend_pool_cgrouped_fwd(*args, [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], [int(x) for x in cand.T_g], int(plan.H),
+                                    int(cand.T), save_z, resolve_mma(mma))[0]
+
+
 def _history_gather_groups_impl(x_history, perm, bounds, row_off, H_g, R):
     """x_history [B, H, cols] (float64 or float32, kept) -> the grouped arena [R, cols] (bitwise): row (b - bounds[g]) * H_g[g] + j of group g
     is row j of impression perm[b].  One launch for all groups; the sorted x_history is never formed."""
@@ -1980,6 +2162,62 @@ def softmax_bce_loss(out, delta, label, user_id, alpha):
         return _degenerate((), out, delta) + float("nan")
     _require_gpu(out, delta, label, user_id)
     return softmax_bce_loss_op(out, delta, label, user_id, float(alpha))[0]
+
+
+#   The loss over the candidate arena: group g -- sorted impressions b0[g] .. b0[g + 1] - 1, tg[g] <= T columns each, from
+# arena row sum_{g' < g} B_g' tg[g'] -- is one launch of the last-column-weighted kernel with w_g = T - tg[g] + 1 and the normaliser of the
+# whole batch; the loss and ddelta accumulate over the launches.
+def _loss_grouped_impl(out, delta, label, user_id, group_b0, group_t, T, alpha):
+    """out [N] (the arena logits: dense, or column 0 of the last GEMM's padded [N, 4] output), label [N], user_id [B] in the groups' sorted
+    order -> (loss, dout [N] = column 0 of a zero-padded [N, 4] matrix, ddelta)."""
+    _require_gpu(out, delta, label, user_id)
+    groups, _, _, _ = _group_layout(group_b0, [1] * len(group_t), T, group_t)
+    B = groups[-1][1]
+    N = groups[-1][8] + (groups[-1][1] - groups[-1][0]) * groups[-1][7]
+    if out.dim() != 1 or out.shape[0] != N or label.numel() != N or user_id.numel() != B:
+        raise RuntimeError(f"softmax_bce_loss_grouped: logits {tuple(out.shape)}, labels {tuple(label.shape)}, ids {tuple(user_id.shape)} for groups "
+                           f"{list(group_b0)} x {list(group_t)} ({N} arena rows, {B} impressions)")
+    d = _f32c(delta)
+    so = out.stride(0) if N > 1 else 1
+    if not (out.dtype == torch.float32 and so >= 1):
+        out, so = _f32c(out), 1
+    y = (label if (label.dtype in (torch.float32, torch.float64) and label.is_contiguous()) else _f32c(label)).reshape(-1)
+    uid = user_id.to(torch.int64).contiguous()
+    loss = torch.zeros((), dtype=torch.float32, device=out.device)
+    ddelta = torch.zeros_like(d)
+    dbuf = torch.empty(N, 4, dtype=torch.float32, device=out.device)
+    import numpy as np
+    inv_n = float(np.float32(1.0) / (np.float32(B) * np.float32(T)))          # as the dense kernel forms it
+    err, st = native.ptr(index_error_flag(out.device)), native.stream_ptr()
+    for b_lo, b_hi, _h, _r, _rh, _s, _z, T_g, t_lo in groups:
+        native.call("nrm_loss_fwd_bwd_wlast", native.ptr(out[t_lo:]), so, native.ptr(y[t_lo:]), 1 if y.dtype == torch.float64 else 0,
+                    native.ptr(uid[b_lo:]), native.ptr(d), d.numel(), float(alpha), b_hi - b_lo, T_g, float(T - T_g + 1), inv_n, native.ptr(loss),
+                    native.ptr(dbuf[t_lo:]), 4, native.ptr(ddelta), err, st)
+    return loss, dbuf[:, 0], ddelta
+
+
+softmax_bce_loss_grouped_op = _op("softmax_bce_loss_grouped", "(Tensor out, Tensor delta, Tensor label, Tensor user_id, int[] group_b0, int[] group_t, "
+                                  "int T, float alpha) -> (Tensor, Tensor, Tensor)", _loss_grouped_impl,
+                                  lambda out, delta, label, user_id, group_b0, group_t, T, alpha: (
+                                      out.new_empty((), dtype=torch.float32), out.new_empty((out.shape[0], 4), dtype=torch.float32)[:, 0],
+                                      delta.new_empty(tuple(delta.shape), dtype=torch.float32)))
+
+
+def _loss_grouped_backward(ctx, gl, _a, _b):
+    return _loss_backward(ctx, gl, _a, _b) + (None, None, None)
+
+
+torch.library.register_autograd("nrm::softmax_bce_loss_grouped", _loss_grouped_backward, setup_context=_loss_setup, lib=_LIB)
+
+
+def softmax_bce_loss_grouped(out, delta, label, user_id, plan, alpha):
+    """The loss of the dense [B, T] batch from the arena logits of ``plan`` (a ``compact.CandidateGroupPlan``): ``out`` / ``label`` [N] in
+    arena order, ``user_id`` [B] in the plan's sorted order."""
+    _require_gpu(out, delta, label, user_id)
+    if plan.N == 0:
+        return _degenerate((), out, delta) + float("nan")
+    return softmax_bce_loss_grouped_op(out, delta, label, user_id, [int(x) for x in plan.bounds], [int(x) for x in plan.T_g], int(plan.T),
+                                       float(alpha))[0]
 
 
 # ------------------------------------------------------------------------------------------------ embedding front end
@@ -2334,6 +2572,43 @@ compact_gather = _op("compact_gather", "(Tensor x_target, Tensor x_global, Tenso
                      _compact_gather_impl, _compact_gather_fake)
 
 
+def _candidate_gather_groups_impl(x_target, x_global, label, perm, bounds, row_off, T_g, N):
+    """x_target [B, T, ct], x_global [B, T, cg], label [B, T] (float64 or float32 each, kept) -> (xt [N, ct], xg [N, cg], label [N], row weight
+    [N] fp32): the candidate arenas of the plan's groups in ONE launch, which also compares every dropped cell with the group's last kept
+    column of its impression (``pad_error_flag``)."""
+    _require_gpu(x_target, x_global, label, perm, bounds, row_off, T_g)
+    fix = lambda x: (x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)).contiguous()      # noqa: E731
+    xt, xg, lab = fix(x_target), fix(x_global), fix(label)
+    G = T_g.shape[0]
+    if (xt.dim() != 3 or xg.dim() != 3 or tuple(xg.shape[:2]) != tuple(xt.shape[:2]) or tuple(lab.shape) != tuple(xt.shape[:2])
+            or tuple(perm.shape) != (xt.shape[0],) or tuple(bounds.shape) != (G + 1,) or tuple(row_off.shape) != (G + 1,)):
+        raise RuntimeError(f"candidate_gather_groups: x_target {tuple(xt.shape)}, x_global {tuple(xg.shape)}, label {tuple(lab.shape)}, perm "
+                           f"{tuple(perm.shape)}, bounds {tuple(bounds.shape)}, row_off {tuple(row_off.shape)}, T_g {tuple(T_g.shape)} do not agree")
+    B, T = xt.shape[0], xt.shape[1]
+    N = int(N)
+    out_t = torch.empty(N, xt.shape[2], dtype=xt.dtype, device=xt.device)
+    out_g = torch.empty(N, xg.shape[2], dtype=xg.dtype, device=xt.device)
+    out_l = torch.empty(N, dtype=lab.dtype, device=xt.device)
+    roww = torch.empty(N, dtype=torch.float32, device=xt.device)
+    if B * T and G:
+        native.call("nrm_candidate_gather_groups", native.ptr(xt), xt.shape[2], 1 if xt.dtype == torch.float64 else 0,
+                    native.ptr(xg), xg.shape[2], 1 if xg.dtype == torch.float64 else 0, native.ptr(lab), 1 if lab.dtype == torch.float64 else 0,
+                    native.ptr(_tab(perm)), native.ptr(_tab(bounds)), native.ptr(_tab(row_off)), native.ptr(_tab(T_g)), G, B, T, N,
+                    native.ptr(out_t), native.ptr(out_g), native.ptr(out_l), native.ptr(roww), native.ptr(pad_error_flag(xt.device)),
+                    native.stream_ptr())
+    return out_t, out_g, out_l, roww
+
+
+def _candidate_gather_groups_fake(x_target, x_global, label, perm, bounds, row_off, T_g, N):
+    f = lambda x: x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32      # noqa: E731
+    return (x_target.new_empty((N, x_target.shape[2]), dtype=f(x_target)), x_global.new_empty((N, x_global.shape[2]), dtype=f(x_global)),
+            label.new_empty((N,), dtype=f(label)), label.new_empty((N,), dtype=torch.float32))
+
+
+candidate_gather_groups = _op("candidate_gather_groups", "(Tensor x_target, Tensor x_global, Tensor label, Tensor perm, Tensor bounds, Tensor row_off, "
+                              "Tensor T_g, int N) -> (Tensor, Tensor, Tensor, Tensor)", _candidate_gather_groups_impl, _candidate_gather_groups_fake)
+
+
 def _attend_pool_ragged_fwd_impl(t, h, w1, b1, w2, b2, cand_imp, cand_off, max_count, mma):
     """Ragged attention + pool as one node (inference only, no z): t [N, D] compact candidate rows, h [B, H, D] ->
     (pooled [N, D], s [N, H]) with s[c, :] the pointwise attention scores of candidate c against the history of impression
@@ -2546,4 +2821,6 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
        "history_len", "history_gather", "history_tiles", "attend_pool_hragged_fwd",
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
+       "candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
+       "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
        "adam_step")

@@ -328,6 +328,63 @@ def attach_history_len(batch, after=None):
     return dict(batch, history_len_host=(host, done, xh.data_ptr(), xh._version))
 
 
+def attach_empty_num(batch, host):
+    """-> ``batch`` with ``"empty_num_host"`` = (the HOST copy of ``empty_num`` the batch was staged from, address and version counter of the
+    device tensor): ``train_step(compact_candidates=True)`` plans from it without a synchronise, while ``empty_num`` is still that tensor.
+    The counts are not trusted either way: the gather kernel checks every dropped cell."""
+    dev = batch["empty_num"]
+    return dict(batch, empty_num_host=(host, dev.data_ptr(), dev._version))
+
+
+def _empty_num_host(batch):
+    """``empty_num`` of the batch on the host: the prefetcher's copy where it describes this very tensor, else one ``.cpu()`` (a synchronise)."""
+    e = batch["empty_num"]
+    pre = batch.get("empty_num_host")
+    if pre is not None and hasattr(e, "data_ptr") and (pre[1], pre[2]) == (e.data_ptr(), e._version):
+        return pre[0].numpy() if hasattr(pre[0], "numpy") else pre[0]
+    return e.detach().cpu().numpy() if hasattr(e, "detach") else e
+
+
+def _compact_candidates_forward(model, batch, alpha, max_groups, compact_history):
+    """forward + loss of train_step(compact_candidates=True) -> (loss, out [B, T] in the caller's order), or None where the candidate axis
+    has nothing worth dropping or the model does not take the row-weight head (the caller then tries compact_history alone, then dense)."""
+    from . import compact, ops
+    xh, xt = batch["x_history"], batch["x_target"]
+    empty = _empty_num_host(batch)
+    # first, and before anything that costs host time: can ANY grouping save enough?  (a launch-bound step feels every 10 us spent here)
+    if not compact_history and compact.candidate_saving_bound(empty, xt.shape[1]) < compact.MIN_SAVING:
+        return None
+    if not (hasattr(model, "compact_candidates_applies") and model.compact_candidates_applies()):
+        return None
+    flag = ops.pad_error_flag(xh.device)
+    if int(flag[0]):                                         # raised by an EARLIER step's gather: that step has been applied
+        torch.cuda.synchronize(xh.device)
+        flag.zero_()
+        raise ValueError("train_step(compact_candidates=True): a candidate that empty_num counts as padding differs from the other padded "
+                         "candidates of its impression in x_target, x_global or label, in a batch of an earlier step (which ran on the "
+                         "compacted rows and HAS BEEN APPLIED); train this data with the dense step")
+    hist = None
+    if compact_history:
+        pre = batch.get("history_len_host")
+        if pre is None or (pre[2], pre[3]) != (xh.data_ptr(), xh._version):
+            pre = history_len_host(xh)
+        pre[1].synchronize()
+        hist = compact.plan_history_groups(pre[0].numpy(), xh.shape[1], max_groups=max_groups)
+    cand = compact.plan_candidate_groups(empty, xt.shape[1], max_groups=max_groups, history_plan=hist)
+    if cand.dense or cand.B == 0:
+        return None
+    plan = hist if hist is not None else compact.full_height_history_plan(cand, xh.shape[1])
+    plan.cand = cand
+    tabs, ctabs = plan.upload(xh.device), cand.upload(xh.device)
+    perm = tabs["perm"]
+    arena = ops.history_gather_groups(xh, perm, tabs["bounds"], tabs["row_off"], tabs["H_g"], plan.R)
+    xt_a, xg_a, label_a, roww = ops.candidate_gather_groups(xt, batch["x_global"], batch["label"], perm, tabs["bounds"], ctabs["row_off"],
+                                                            ctabs["T_g"], cand.N)
+    out_arena = model.forward_grouped(arena, xt_a, xg_a, plan, row_weight=roww)
+    loss = model.loss_grouped(batch["user_id"].index_select(0, perm), out_arena, label_a, cand, alpha)
+    return loss, out_arena.detach().index_select(0, ctabs["expand"]).view(cand.B, cand.T)
+
+
 def _compact_forward(model, batch, alpha, max_groups):
     """forward + loss of train_step(compact_history=True) -> (loss, out in the caller's order), or None where the step runs dense: a
     model whose attentions do not take the fused node, or a plan with nothing worth dropping."""
@@ -352,7 +409,7 @@ def _compact_forward(model, batch, alpha, max_groups):
 
 
 def train_step(model, optimizer, batch, reducer: FlatGradReducer | None = None, alpha=0.95, defer_reductions=True,
-               strict_ids=False, compact_history=False, max_groups=None):
+               strict_ids=False, compact_history=False, max_groups=None, compact_candidates=False):
     """One step of train.py:69-75 on device-resident tensors; returns (loss, out) detached.  An out-of-range id of an EARLIER
     step raises IndexError here, before this step's work is enqueued (IndexErrorWatch: asynchronous, the offending step has
     been applied by then).  ``strict_ids=True``: the ids of THIS batch are checked first (validate_batch_ids, one host
@@ -363,16 +420,32 @@ def train_step(model, optimizer, batch, reducer: FlatGradReducer | None = None, 
     caller's order.  The plan needs the lengths on the HOST: what ``BatchPrefetcher(..., history_len=True)`` measured while staging the
     batch (``attach_history_len``; used only while ``x_history`` is the very tensor contents it was measured on) costs nothing here;
     without it the lengths are measured now and this call waits for everything enqueued before it (one synchronise per step).  A plan with nothing worth dropping, and a model whose attentions do not take the fused node, run the dense
-    step unchanged.  Not inside a stream capture."""
+    step unchanged.  Not inside a stream capture.
+    ``compact_candidates=True``: the padded candidates the ETL fills every list with are not computed either -- the
+    batch is sorted by ``T - batch["empty_num"]`` and cut into at most ``max_groups`` groups, each trimmed to its live candidates plus ONE
+    padded one whose weight BatchNorm's batch statistics and the loss take; with ``compact_history`` as well the groups are the history
+    plan's.  ``empty_num`` is read on the host (``BatchPrefetcher(..., empty_num=True)`` keeps its copy: no synchronise; a device-only
+    tensor costs one ``.cpu()``) and CHECKED on the device: a dropped candidate that differs from its impression's padded one raises
+    ValueError at the next compacted step.  ``out`` is the full [B, T] in the caller's order.  A plan with nothing worth dropping and a
+    model with a BatchNorm or gate the row-weight kernels do not take run as without the flag."""
     if compact_history and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("train_step(compact_history=True) plans the length groups on the host and cannot run inside a stream capture "
                            "(GraphedTrainStep captures the dense step)")
+    if compact_candidates:
+        if "empty_num" not in batch:
+            raise KeyError("empty_num: train_step(compact_candidates=True) needs batch['empty_num'], the trailing padded candidates per "
+                           "impression")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("train_step(compact_candidates=True) plans the candidate groups on the host and cannot run inside a stream "
+                               "capture (GraphedTrainStep captures the dense step)")
     watch = _index_watch(batch["x_history"].device) if not torch.cuda.is_current_stream_capturing() else None
     if watch is not None:
         watch.before_step()
     if strict_ids:
         validate_batch_ids(model, batch)
-    compacted = _compact_forward(model, batch, alpha, max_groups) if compact_history else None
+    compacted = _compact_candidates_forward(model, batch, alpha, max_groups, compact_history) if compact_candidates else None
+    if compacted is None:
+        compacted = _compact_forward(model, batch, alpha, max_groups) if compact_history else None
     if compacted is not None:
         loss, out = compacted
     else:
@@ -410,11 +483,14 @@ class GraphedTrainStep:
     (reference default dimensions: 3.1 -> 2.7 ms).  New data is copied INTO the tensors
     of ``batch`` before ``replay()``; ``loss`` / ``out`` are overwritten in place by every replay."""
 
-    def __init__(self, model, optimizer, batch, alpha=0.95, warmup=3, pool=None, compact_history=False):
+    def __init__(self, model, optimizer, batch, alpha=0.95, warmup=3, pool=None, compact_history=False, compact_candidates=False):
         """``pool``: the memory pool of another GraphedTrainStep (``other.graph.pool()``) -- several captured steps, e.g. one per
         resident input batch, then share their intermediates' memory (they must be replayed one at a time, in any order)."""
         if compact_history:
             raise RuntimeError("GraphedTrainStep(compact_history=True): the length groups are planned on the host for every batch; a "
+                               "captured step replays one fixed sequence of launches.  Capture the dense step")
+        if compact_candidates:
+            raise RuntimeError("GraphedTrainStep(compact_candidates=True): the candidate groups are planned on the host for every batch; a "
                                "captured step replays one fixed sequence of launches.  Capture the dense step")
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedTrainStep needs trainer.FlatAdam (its step counter lives on the device)")
@@ -478,11 +554,13 @@ class BatchPrefetcher:
     preallocated device buffer sets on a copy stream while the current step runs; the compute stream waits on the
     copy's event, and a buffer is only overwritten after the step that read it has been enqueued (its event)."""
 
-    def __init__(self, batches, device="cuda", pin=True, history_len=False):
+    def __init__(self, batches, device="cuda", pin=True, history_len=False, empty_num=False):
         """``history_len=True``: the history lengths of every staged batch are measured on a side stream that waits only for the batch's
         own upload, copied to the host and attached as ``batch["history_len_host"]`` (what ``train_step(compact_history=True)`` plans
-        from, without draining the compute stream)."""
+        from, without draining the compute stream).  ``empty_num=True``: the host copy of ``empty_num`` every batch is staged from is
+        kept with it as ``batch["empty_num_host"]`` (what ``train_step(compact_candidates=True)`` plans from)."""
         self.history_len = history_len
+        self.empty_num = empty_num
         self.device = torch.device(device)
         self.batches = iter(batches)
         self.pin = pin
@@ -524,6 +602,8 @@ class BatchPrefetcher:
             self.ready[i].record(self.copy_stream)
         if self.history_len:
             self.bufs[i] = attach_history_len(self.bufs[i], after=self.ready[i])
+        if self.empty_num and "empty_num" in host:
+            self.bufs[i] = attach_empty_num(self.bufs[i], host["empty_num"])
         self._pending = (i, host)                                   # keep the pinned tensors alive until consumed
 
     def __iter__(self):
@@ -547,13 +627,14 @@ class BatchPrefetcher:
 
 
 def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path=None, on_batch=None, compact_history=False,
-                 max_groups=None):
+                 max_groups=None, compact_candidates=False):
     """The epoch loop of reference train.py:52-100 around ``train_step``: every epoch re-reads ``param_groups[0]['lr']``
     (:57), steps through ``make_loader()`` (an iterable of host batches, dict fields as in ``synth.make_batch``), keeps
     the running loss and per-impression AUC averages the reference prints (:77-88, AUC on the device instead of a
     host sklearn loop), and saves the state_dict without ``delta`` (:95-97).  The reference never steps its scheduler
     (:99-100), so none is taken here.  Batches are staged through ``BatchPrefetcher``.  ``compact_history`` / ``max_groups``: as in
-    ``train_step``; the prefetcher then measures the history lengths while it stages a batch.
+    ``train_step``; the prefetcher then measures the history lengths while it stages a batch.  ``compact_candidates``: as in ``train_step``;
+    the prefetcher keeps the host ``empty_num`` of every batch, and a padding error of the epoch's last batches raises at its end.
     Returns one dict per epoch: lr, loss_avg, auc_avg, impressions."""
     from . import evaluation, ops
     history = []
@@ -564,9 +645,12 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
         auc_sum = torch.zeros((), dtype=torch.float64, device=device)
         bad_rows = torch.zeros((), dtype=torch.int64, device=device)
         seen = 0
-        pf = BatchPrefetcher(make_loader(), device, history_len=compact_history)
+        pf = BatchPrefetcher(make_loader(), device, history_len=compact_history, empty_num=compact_candidates)
         for i, (batch, slot) in enumerate(pf):
-            loss, out = train_step(model, optimizer, batch, compact_history=compact_history, max_groups=max_groups)
+            if compact_candidates:
+                loss, out = train_step(model, optimizer, batch, compact_history=compact_history, max_groups=max_groups, compact_candidates=True)
+            else:
+                loss, out = train_step(model, optimizer, batch, compact_history=compact_history, max_groups=max_groups)
             auc, _hit = evaluation.row_auc_top1(out, batch["label"])
             pf.release(slot)
             n = out.shape[0]
@@ -582,6 +666,8 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
         # the kernels clamp and flag, train_step raises at the start of the NEXT step (IndexErrorWatch, no host sync); the last
         # batches of the epoch are covered here, at the epoch's one host sync
         ops.check_index_errors(next(model.parameters()).device)
+        if compact_candidates:
+            ops.check_pad_errors(next(model.parameters()).device)
         rec = {"epoch": epoch, "lr": lr, "impressions": seen,
                "loss_avg": float(loss_sum / max(seen, 1)), "auc_avg": float(auc_sum / max(seen, 1))}
         history.append(rec)
