@@ -139,6 +139,16 @@ int nrm_pwattn_bwd_dp_dtdh(const float* dz, const float* t, const float* h, cons
  * column sums; nrm_gemm_nt_bf16_supported says whether a reduction width K fits the resident-row form (else use NRM_MMA_F32). */
 long nrm_gemm_packed_floats(int nrows, int ncols, int mma);
 int nrm_gemm_nt_bf16_supported(int M, int K, int mma);
+/* Which kernel a launch of nrm_gemm_nt(M, N, K, mma) takes (additive entry point, the ABI version is unchanged): the selection of
+ * the launch itself, without any device call, with the environment knobs applied as the launch applies them (NRM_NT_KC and NRM_RX_BM
+ * at every call; NRM_NT_SMALLM, NRM_NT_NARROW, NRM_NT_13X2 and NRM_RX_MIN_WGS as latched at their first use in the process).
+ *   NRM_MMA_F32:            NT | MT << 8 | WPE << 16 | KC << 24   of gemm_nt_kernel<NT, MT, EPI, WPE, KC>: NT 16-column tiles per
+ *                           N-chunk, MT 16-row tiles per wave (a workgroup holds 64 * MT rows), WPE waves per SIMD the kernel is built
+ *                           for, KC 16-wide K-chunks per LDS stage
+ *   NRM_MMA_BF16 / _BF16X3: RT | G << 8   of gemm_nt_rx_kernel<RT, MMA, EPI, G>: 16 * RT resident rows per workgroup, weight
+ *                           fragments in groups of G reduction chunks; 0 where nrm_gemm_nt_bf16_supported is 0
+ * -1: bad arguments (M, N or K <= 0, unknown mma). */
+int nrm_gemm_nt_form(int M, int N, int K, int mma);
 /* packs the logical [nrows x ncols] matrix src[r*row_stride + c*col_stride]; rows become output columns of
  * nrm_gemm_nt, columns its reduction index.  Linear.forward: (W[N,K], K, 1, N, K); dX = dY W: (W, 1, K, K, N) */
 int nrm_gemm_pack(const float* src, long row_stride, long col_stride, int nrows, int ncols, float* packed,

@@ -317,6 +317,16 @@ long nrm_gemm_packed_floats(int nrows, int ncols, int mma) {
 
 int nrm_gemm_nt_bf16_supported(int M, int K, int mma) { return nrm::gemm_nt_rx_bm(M, K, mma) ? 1 : 0; }
 
+int nrm_gemm_nt_form(int M, int N, int K, int mma) {
+    if (M <= 0 || N <= 0 || K <= 0 || check_mma("nrm_gemm_nt_form", mma)) return -1;
+    if (mma != NRM_MMA_F32) {
+        const nrm::GemmRxForm f = nrm::gemm_nt_rx_select(M, K, mma);
+        return f.RT ? (f.RT | f.G << 8) : 0;
+    }
+    const nrm::GemmNtForm f = nrm::gemm_nt_select(M, (K + 15) / 16, nrm::gemm_nt_plan(N));
+    return f.NT | f.MT << 8 | f.WPE << 16 | f.KC << 24;
+}
+
 int nrm_gemm_pack(const float* src, long row_stride, long col_stride, int nrows, int ncols, float* packed,
                   nrm_stream_t stream) {
     if (!src || !packed || nrows <= 0 || ncols <= 0) return fail(NRM_EINVAL, "nrm_gemm_pack: bad argument");

@@ -310,14 +310,15 @@ static hipError_t launch_nt(const GemmNtParams& p, const GemmNtPlan& pl, int epi
     return hipGetLastError();
 }
 
-hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st) {
-    if (p.M <= 0) return hipSuccess;
+// The one place that decides which gemm_nt_kernel<NT, MT, EPI, WPE, KC> a launch of M rows takes: gemm_nt_launch switches on it and
+// nrm_gemm_nt_form (capi.hip) reports it, environment knobs included.
+GemmNtForm gemm_nt_select(int M, int kchunks, const GemmNtPlan& pl) {
     // The row-tile count MT of a workgroup (64*MT rows) is free at launch time (the packed operand depends on NT only).  A grid
     // of fewer than two workgroups per CU leaves every workgroup alone with its chain of K-chunk rounds (DMA, barrier, a few
     // hundred MFMA cycles): C2's 258-wide layers were 240 workgroups of 128 rows at 57 % of the MFMA peak.  Such launches
     // take one row tile per wave instead.  NRM_NT_SMALLM=0 keeps the planned MT.
     static const bool small_m = [] { const char* e = getenv("NRM_NT_SMALLM"); return !(e && e[0] == '0'); }();
-    const long wgs = (long)((p.M + 64 * pl.MT - 1) / (64 * pl.MT)) * pl.nchunks;
+    const long wgs = (long)((M + 64 * pl.MT - 1) / (64 * pl.MT)) * pl.nchunks;
     // Deeper LDS stages (template parameter KC = 2 | 4 chunks per stage) for launches of few workgroups: built on the theory that
     // such a launch is a chain of DMA-latency-bound rounds, measured (graph replay, same box, whole step): C1 1.795 -> 1.84 ms
     // (gemm_nt 33.2 -> 35.3 us per launch), reference default 12.9 -> 12.2 us per launch -- the latency chain is not what limits
@@ -325,38 +326,32 @@ hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, 
     const char* kc_e = getenv("NRM_NT_KC");                           // (read per launch: tests switch forms inside one process)
     int kc = kc_e ? atoi(kc_e) : 1;
     if (kc != 2 && kc != 4) kc = 1;
-    if (p.kchunks < 2 * kc) kc = p.kchunks >= 4 ? 2 : 1;             // (p.kchunks = ceil(K / 16))
-    if (kc > 1 && (pl.MT == 1 || (small_m && wgs < 512))) {
-        if (kc == 4) {
-            if (pl.NT == 4) return launch_nt<4, 1, 1, 4>(p, pl, epi, st);
-            if (pl.NT == 5) return launch_nt<5, 1, 1, 4>(p, pl, epi, st);
-            if (pl.NT == 8) return launch_nt<8, 1, 1, 4>(p, pl, epi, st);
-            if (pl.NT == 9) return launch_nt<9, 1, 1, 4>(p, pl, epi, st);
-            if (pl.NT == 13) return launch_nt<13, 1, 1, 4>(p, pl, epi, st);
-        } else {
-            if (pl.NT == 4) return launch_nt<4, 1, 2, 2>(p, pl, epi, st);
-            if (pl.NT == 5) return launch_nt<5, 1, 2, 2>(p, pl, epi, st);
-            if (pl.NT == 8) return launch_nt<8, 1, 2, 2>(p, pl, epi, st);
-            if (pl.NT == 9) return launch_nt<9, 1, 2, 2>(p, pl, epi, st);
-            if (pl.NT == 13) return launch_nt<13, 1, 2, 2>(p, pl, epi, st);
-        }
-    }
-    if (small_m && pl.MT > 1 && wgs < 512) {
-        if (pl.NT == 4) return launch_nt<4, 1, 4>(p, pl, epi, st);
-        if (pl.NT == 5) return launch_nt<5, 1, 4>(p, pl, epi, st);
-        if (pl.NT == 8) return launch_nt<8, 1, 4>(p, pl, epi, st);
-        if (pl.NT == 9) return launch_nt<9, 1, 4>(p, pl, epi, st);
-    }
-    if (pl.NT == 4) return launch_nt<4, 4>(p, pl, epi, st);
-    if (pl.NT == 5) return launch_nt<5, 4>(p, pl, epi, st);
-    if (pl.NT == 8) return launch_nt<8, 3>(p, pl, epi, st);
-    if (pl.NT == 9) return launch_nt<9, 2, 3>(p, pl, epi, st);
+    if (kchunks < 2 * kc) kc = kchunks >= 4 ? 2 : 1;                 // (kchunks = ceil(K / 16))
+    if (kc > 1 && (pl.MT == 1 || (small_m && wgs < 512))) return GemmNtForm{pl.NT, 1, kc == 4 ? 1 : 2, kc};
+    if (small_m && pl.MT > 1 && wgs < 512) return GemmNtForm{pl.NT, 1, 4, 1};
+    if (pl.NT == 4) return GemmNtForm{4, 4, 2, 1};
+    if (pl.NT == 5) return GemmNtForm{5, 4, 2, 1};
+    if (pl.NT == 8) return GemmNtForm{8, 3, 2, 1};
+    if (pl.NT == 9) return GemmNtForm{9, 2, 3, 1};
     // 13 column tiles x ONE row tile per wave: 97 VGPRs and 35 KB of LDS, four workgroups per CU.  Measured on the head's
     // layers (M = 30 720, 1608 <-> 402): 0.199 ms per launch against 0.211 ms for 13x2 (129 VGPRs, 43 KB, three per CU),
     // although every W chunk then serves 64 rows instead of 128.  NRM_NT_13X2=1 restores 13x2.
     static const int use13x2 = [] { const char* e = getenv("NRM_NT_13X2"); return e && e[0] == '1' ? 1 : 0; }();
-    if (use13x2) return launch_nt<13, 2>(p, pl, epi, st);
-    return launch_nt<13, 1, 4>(p, pl, epi, st);
+    if (use13x2) return GemmNtForm{13, 2, 2, 1};
+    return GemmNtForm{13, 1, 4, 1};
+}
+
+hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st) {
+    if (p.M <= 0) return hipSuccess;
+    const GemmNtForm f = gemm_nt_select(p.M, p.kchunks, pl);
+#define NRM_NT(NT_, MT_, WPE_, KC_) \
+    if (f.NT == NT_ && f.MT == MT_ && f.WPE == WPE_ && f.KC == KC_) return launch_nt<NT_, MT_, WPE_, KC_>(p, pl, epi, st);
+#define NRM_NT_ROW1(NT_)  NRM_NT(NT_, 1, 1, 4) NRM_NT(NT_, 1, 2, 2) NRM_NT(NT_, 1, 4, 1)
+    NRM_NT_ROW1(4) NRM_NT_ROW1(5) NRM_NT_ROW1(8) NRM_NT_ROW1(9) NRM_NT_ROW1(13)
+    NRM_NT(4, 4, 2, 1) NRM_NT(5, 4, 2, 1) NRM_NT(8, 3, 2, 1) NRM_NT(9, 2, 3, 1) NRM_NT(13, 2, 2, 1)
+#undef NRM_NT_ROW1
+#undef NRM_NT
+    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------

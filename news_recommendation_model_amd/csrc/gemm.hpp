@@ -18,6 +18,8 @@ struct GemmNtParams {
 };
 struct GemmNtPlan { int NT, MT, nchunks, rows; };
 GemmNtPlan gemm_nt_plan(int N);
+struct GemmNtForm { int NT, MT, WPE, KC; };                // gemm_nt_kernel<NT, MT, EPI, WPE, KC>; the workgroup holds 64 * MT rows
+GemmNtForm gemm_nt_select(int M, int kchunks, const GemmNtPlan& pl);      // host only: what gemm_nt_launch runs (knobs applied)
 hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st);
 hipError_t pack_rows_launch(const float* src, long rs, long cs, int nrows, int ncols, int rows, int kchunks,
                             float* packed, hipStream_t st);
@@ -34,6 +36,8 @@ struct GemmRxParams {
 };
 int gemm_bf16_diag_flags();                                // bit 10: NRM_DIAG_RX (timing-only build)
 int gemm_nt_rx_bm(int M, int K, int mma);                  // rows per workgroup; 0: K too wide (the caller keeps the fp32 GEMM)
+struct GemmRxForm { int RT, G; };                          // gemm_nt_rx_kernel<RT, MMA, EPI, G>: 16 * RT rows per workgroup; {0, 0}: none
+GemmRxForm gemm_nt_rx_select(int M, int K, int mma);       // host only: what gemm_nt_rx_launch runs (knobs applied)
 hipError_t gemm_nt_rx_launch(const GemmRxParams& p, int epi, int mma, hipStream_t st);
 
 constexpr int PACK_MAX = 36;

@@ -343,10 +343,19 @@ int gemm_nt_rx_bm(int M, int K, int mma) {
     return bm;
 }
 
+// The one place that decides which gemm_nt_rx_kernel<RT, MMA, EPI, G> a launch takes: gemm_nt_rx_launch switches on it and
+// nrm_gemm_nt_form (capi.hip) reports it, environment knobs included.
+GemmRxForm gemm_nt_rx_select(int M, int K, int mma) {
+    const int bm = gemm_nt_rx_bm(M, K, mma);
+    if (bm != 16 && bm != 32 && bm != 64 && bm != 128) return GemmRxForm{0, 0};
+    const int k32 = (K + 31) / 32;
+    const bool g3 = (k32 + 2) / 3 * 3 < (k32 + 3) / 4 * 4;             // groups of 3 chunks pad less than groups of 4
+    return GemmRxForm{bm / 16, g3 ? 3 : 4};
+}
+
 template <int RT, int MMA>
-static hipError_t launch_rx_e(const GemmRxParams& p, int epi, size_t shm, hipStream_t st) {
+static hipError_t launch_rx_e(const GemmRxParams& p, int epi, bool g3, size_t shm, hipStream_t st) {
     const dim3 grid((p.M + RT * 16 - 1) / (RT * 16)), block(RX_WAVES * 64);
-    const bool g3 = (p.k32 + 2) / 3 * 3 < (p.k32 + 3) / 4 * 4;         // groups of 3 chunks pad less than groups of 4
 #define NRM_RX(E)                                                                                                        \
     {                                                                                                                    \
         auto k = g3 ? gemm_nt_rx_kernel<RT, MMA, E, 3> : gemm_nt_rx_kernel<RT, MMA, E, 4>;                               \
@@ -367,15 +376,15 @@ static hipError_t launch_rx_e(const GemmRxParams& p, int epi, size_t shm, hipStr
 
 hipError_t gemm_nt_rx_launch(const GemmRxParams& p, int epi, int mma, hipStream_t st) {
     if (p.M <= 0) return hipSuccess;
-    const int bm = gemm_nt_rx_bm(p.M, p.K, mma);
-    if (!bm) return hipErrorInvalidValue;
-    const size_t shm = (size_t)p.k32 * (mma == 2 ? 2 : 1) * bm * 64;
-#define NRM_RX_RT(RT_)  return mma == 2 ? launch_rx_e<RT_, 2>(p, epi, shm, st) : launch_rx_e<RT_, 1>(p, epi, shm, st);
-    switch (bm) {
-        case 16:  NRM_RX_RT(1)
-        case 32:  NRM_RX_RT(2)
-        case 64:  NRM_RX_RT(4)
-        case 128: NRM_RX_RT(8)
+    const GemmRxForm f = gemm_nt_rx_select(p.M, p.K, mma);
+    if (!f.RT || p.k32 != (p.K + 31) / 32) return hipErrorInvalidValue;
+    const size_t shm = (size_t)p.k32 * (mma == 2 ? 2 : 1) * f.RT * 16 * 64;
+#define NRM_RX_RT(RT_)  return mma == 2 ? launch_rx_e<RT_, 2>(p, epi, f.G == 3, shm, st) : launch_rx_e<RT_, 1>(p, epi, f.G == 3, shm, st);
+    switch (f.RT) {
+        case 1: NRM_RX_RT(1)
+        case 2: NRM_RX_RT(2)
+        case 4: NRM_RX_RT(4)
+        case 8: NRM_RX_RT(8)
     }
 #undef NRM_RX_RT
     return hipErrorInvalidValue;

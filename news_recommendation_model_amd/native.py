@@ -41,6 +41,7 @@ SIGNATURES = {
     "nrm_pwattn_bwd_dw_pack": (_c_i, [_c_i] * 5),
     "nrm_gemm_packed_floats": (_c_l, [_c_i, _c_i, _c_i]),
     "nrm_gemm_nt_bf16_supported": (_c_i, [_c_i, _c_i, _c_i]),
+    "nrm_gemm_nt_form": (_c_i, [_c_i, _c_i, _c_i, _c_i]),
     "nrm_gemm_pack": (_c_i, [_c_fp, _c_l, _c_l, _c_i, _c_i, _c_fp, _c_fp]),
     "nrm_gemm_nt": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_i, _c_i, _c_fp]),
     "nrm_slab_reduce": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_l, _c_l, _c_fp, _c_l, _c_l, ctypes.c_float,

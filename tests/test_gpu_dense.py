@@ -5,13 +5,13 @@ import numpy as np
 import pytest
 import torch
 
+import dense_forms_util as dfu
 from golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("M,K,N", [(300, 402, 1608), (257, 1608, 402), (64, 3, 8), (1000, 402, 1), (33, 66, 64),
-                                   (5, 272, 68), (192, 400, 400), (700, 402, 400), (700, 400, 402), (3000, 1608, 402), (1300, 402, 1608)])
+@pytest.mark.parametrize("M,K,N", dfu.LINEAR_SHAPES)
 @pytest.mark.parametrize("gelu", [False, True])
 def test_linear_forward_backward(lib, M, K, N, gelu):
     from news_recommendation_model_amd import ops
@@ -35,8 +35,7 @@ def test_linear_forward_backward(lib, M, K, N, gelu):
     assert rel_err(bg.grad.cpu().numpy(), br.grad.numpy()) < 1e-5
 
 
-@pytest.mark.parametrize("M,K,N", [(5120, 1032, 258), (5120, 258, 1032), (3840, 264, 66), (300, 402, 1608), (257, 1608, 402), (33, 66, 64),
-                                   (64, 3, 8), (700, 400, 402), (20000, 402, 400)])
+@pytest.mark.parametrize("M,K,N", dfu.STAGE_DEPTH_SHAPES)
 def test_gemm_nt_stage_depths_are_bit_identical(lib, monkeypatch, M, K, N):
     """gemm_nt_kernel<..., KC>: one, two or four 16-wide K-chunks per LDS stage (round 5: built for launches of few workgroups -- the
     heads of C1 and of the reference's default sizes --, measured no faster there, kept behind NRM_NT_KC).  The chunks are contracted in the same order
@@ -50,11 +49,13 @@ def test_gemm_nt_stage_depths_are_bit_identical(lib, monkeypatch, M, K, N):
     b = (torch.randn(N, generator=g) * 0.1).cuda()
     gy = torch.randn(M, N, generator=g).cuda()
     out = {}
-    for kc in ("1", "2", "4", None):              # None: the default dispatch (KC = 1 since the measurement of round 5)
+    for kc in dfu.STAGE_DEPTHS:                   # None: the default dispatch (KC = 1 since the measurement of round 5)
         if kc is None:
             monkeypatch.delenv("NRM_NT_KC", raising=False)
         else:
             monkeypatch.setenv("NRM_NT_KC", kc)
+        if K == 130:                              # nine chunks: the forward launch really is the stage depth asked for (nrm_gemm_nt_form)
+            assert dfu.nt_form(lib, M, N, K) == {"1": (N // 16, 1, 4, 1), None: (N // 16, 1, 4, 1), "2": (N // 16, 1, 2, 2), "4": (N // 16, 1, 1, 4)}[kc]
         res = []
         for gelu in (False, True):
             xg = x.clone().requires_grad_(True)
@@ -276,12 +277,15 @@ def dense_arithmetic():
 # dX GEMM, split-row weight-gradient GEMM).  bf16x3 (hi/lo split operands) is held to 1e-4 against float64 -- well inside the
 # fp32 gates it has to keep for the whole model; plain bf16 (one rounding per operand, 2^-9) is characterised at 3e-2.
 @pytest.mark.parametrize("mma,tol", [("bf16x3", 1e-4), ("bf16", 3e-2)])
-@pytest.mark.parametrize("M,K,N", [(300, 258, 1032), (257, 1032, 258), (64, 3, 8), (1000, 402, 1), (33, 66, 64), (5, 272, 68),
-                                   (4099, 256, 256), (200, 1608, 402), (17, 40, 36), (51200, 64, 64), (15360, 258, 1032)])     # the last two: 128- and 64-row blocks
+@pytest.mark.parametrize("M,K,N", dfu.BF16_LINEAR_SHAPES)
 @pytest.mark.parametrize("gelu", [False, True])
 def test_linear_forward_backward_on_bf16_matrix_cores(lib, dense_arithmetic, mma, tol, M, K, N, gelu):
     from news_recommendation_model_amd import ops
     dense_arithmetic(mma)
+    if (M, K, N) in dfu.BF16_EXPECTED:                  # the resident-row forms these shapes are here for (nrm_gemm_nt_form)
+        fwd, dx = dfu.BF16_EXPECTED[(M, K, N)][dfu.MMA_BY_NAME[mma]]
+        assert dfu.rx_form(lib, M, N, K, dfu.MMA_BY_NAME[mma]) == fwd
+        assert dfu.rx_form(lib, M, K, N, dfu.MMA_BY_NAME[mma]) == dx
     g = torch.Generator(device="cpu").manual_seed(M * 7 + K + N)
     x = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) / np.sqrt(K)
@@ -336,3 +340,84 @@ def test_mlp_and_gate_block_on_bf16x3_matrix_cores(lib, dense_arithmetic, M, K, 
         names = ("x", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias") + (("mul",) if with_mul else ())
         for a, r, name in zip(dev, ref, names):
             assert rel_err(a.grad.cpu().numpy(), r.grad.numpy()) < 1e-4, (name, with_mul)
+
+
+# ------------------------------------------------------------------------------------------------ every launch form of gemm_nt
+_large_grid_cache = {}
+
+
+def _large_grid_inputs(M, N):
+    """Inputs of one large-grid form and the float64 product, made once and shared by its four epilogues (one form is kept at a time)."""
+    if (M, N) not in _large_grid_cache:
+        _large_grid_cache.clear()
+        K = dfu.LARGE_GRID_K
+        g = torch.Generator(device="cpu").manual_seed(M + N)
+        x = torch.randn(M, K, generator=g)
+        w = torch.randn(N, K, generator=g) / np.sqrt(K)
+        b = torch.randn(N, generator=g) * 0.1
+        side = torch.randn(M, N, generator=g)                   # the saved pre-activation of EPI_DGELU / the gate of EPI_MUL
+        _large_grid_cache[(M, N)] = dict(x=x, w=w, b=b, side=side, acc=x.double() @ w.double().t())
+    return _large_grid_cache[(M, N)]
+
+
+@pytest.mark.parametrize("epilogue", dfu.EPILOGUES)
+@pytest.mark.parametrize("M,N,form", dfu.LARGE_GRID_CASES, ids=["%dx%d" % f[:2] for _, _, f in dfu.LARGE_GRID_CASES])
+def test_gemm_nt_large_grid_forms(lib, monkeypatch, M, N, form, epilogue):
+    """gemm_nt_kernel<4,4>, <5,4>, <8,3> and <9,2,3>: the forms with several interleaved 16-row tiles per wave, which a launch takes
+    only at 512 or more workgroups -- what a production batch runs for the 64- to 258-wide layers.  One launch per epilogue through
+    ops._gemm_nt against float64; x is a view of a buffer whose two padding columns hold NaN (K = 42: the last chunk is cut
+    inside a lane's fragment, and the kernel's contract is that padding may hold anything)."""
+    from news_recommendation_model_amd import ops
+    for k in dfu.KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    K = dfu.LARGE_GRID_K
+    assert dfu.nt_form(lib, M, N, K) == form                    # the launch below is the form under test
+    d = _large_grid_inputs(M, N)
+    buf = torch.full((M, K + 2), float("nan"), device="cuda")
+    buf[:, :K] = d["x"].cuda()
+    x, w, b = buf[:, :K], d["w"].cuda(), d["b"].cuda()
+    side = torch.zeros(M, (N + 3) // 4 * 4, device="cuda")
+    side[:, :N] = d["side"].cuda()
+    z_ref = d["acc"] + d["b"].double()
+    if epilogue == "bias":
+        y, _ = ops._gemm_nt(x, w, K, 1, N, K, b, ops.EPI_BIAS)
+        got, want = [y], [z_ref]
+    elif epilogue == "gelu":
+        y, z = ops._gemm_nt(x, w, K, 1, N, K, b, ops.EPI_GELU)
+        got, want = [y, z], [torch.nn.functional.gelu(z_ref), z_ref]
+    elif epilogue == "dgelu":
+        y, _ = ops._gemm_nt(x, w, K, 1, N, K, None, ops.EPI_DGELU, z=side[:, :N])
+        got, want = [y], [torch.ops.aten.gelu_backward(d["acc"], d["side"].double())]
+    else:
+        y, z = ops._gemm_nt(x, w, K, 1, N, K, b, ops.EPI_MUL, m=side[:, :N])
+        got, want = [y, z], [z_ref * d["side"].double(), z_ref]
+    torch.cuda.synchronize()
+    for a, r in zip(got, want):
+        assert tuple(a.shape) == (M, N)
+        err = rel_err(a.cpu().numpy(), r.numpy())
+        print(f"gemm_nt {form} {epilogue}: rel_err {err:.3g}")
+        assert err < 1e-5
+
+
+# The knobs that are latched once per process (function-local statics of csrc/gemm.hip): each set runs in a child process of its
+# own (tests/dense_knob_worker.py), one after the other; the child prints one JSON line of rel_err values, the gates are here.
+@pytest.mark.parametrize("which", ["13x2", "planned_mt"])
+def test_latched_gemm_knobs_in_a_child_process(lib, which):
+    """A: NRM_NT_13X2=1 (gemm_nt_kernel<13,2>) with NRM_TN_SHAPES=0 (gemm_tn on the plain 4x4 / 5x5 wave tiles).
+    B: NRM_NT_SMALLM=0 and NRM_NT_NARROW=0: the planned MT > 1 forms (<4,4>, <8,3>) on small grids."""
+    import json
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = {k: v for k, v in os.environ.items() if k not in dfu.KNOBS and k != "NRM_TN_SHAPES"}
+    env.update({"13x2": {"NRM_NT_13X2": "1", "NRM_TN_SHAPES": "0"}, "planned_mt": {"NRM_NT_SMALLM": "0", "NRM_NT_NARROW": "0"}}[which])
+    pr = subprocess.run([sys.executable, os.path.join(here, "dense_knob_worker.py"), which], env=env, stdout=subprocess.PIPE,
+                        stderr=subprocess.PIPE, timeout=300)
+    assert pr.returncode == 0, (pr.returncode, pr.stderr.decode(errors="replace")[-3000:])
+    res = json.loads(pr.stdout.decode().strip().splitlines()[-1])
+    assert res["which"] == which and res["forms_ok"] is True, res
+    assert len(res["rel_err"]) == res["expected"] > 0
+    print(res)
+    bad = {k: v for k, v in res["rel_err"].items() if not v < 1e-5}
+    assert not bad, bad

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import dense_forms_util as dfu
 from attention_budget import FORMS, form_skip_reason
 from golden_util import masked_rel_err
 from oracle import user_model_oracle as orc
@@ -237,6 +238,53 @@ def test_linear_keeps_rows_apart(lib, mma, gelu, M, K, N):
                     tag = (where, r, value)
                     _check(tag + ("y",), y.detach().cpu().numpy(), y_ref.detach().numpy(), tol, value, gelu=gelu)
                     _check(tag + ("dx",), xg.grad.cpu().numpy(), xr.grad.numpy(), tol, value, gelu=gelu)
+    finally:
+        ops.set_dense_arithmetic(None)
+
+
+@pytest.mark.parametrize("mma,M,K,N", dfu.CONTAINMENT_CASES, ids=["-".join(map(str, c)) for c in dfu.CONTAINMENT_CASES])
+def test_linear_keeps_rows_apart_in_the_multi_tile_forms(lib, monkeypatch, mma, M, K, N):
+    """The forms in which a wave owns several interleaved 16-row tiles (fp32 gemm_nt_kernel<NT, MT > 1>: 64 * MT rows per workgroup,
+    taken only by grids of 512 or more workgroups) or a workgroup holds 64 / 128 resident rows (gemm_nt_rx_kernel<RT = 4 | 8>): NaN
+    rows planted all at once around the tile and block boundaries -- 0, 15, 16, BM - 1, BM, M - 1, BM the block height of the form the
+    launch takes (nrm_gemm_nt_form) -- first in x, checked on y, then in dy, checked on dx; GELU on.  The non-finite output rows must
+    be exactly the planted ones and every other row must hold the float64 value."""
+    from news_recommendation_model_amd import ops
+    for k in dfu.KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    code = dfu.MMA_BY_NAME[mma]
+    fwd, bwd = dfu.dense_form(lib, M, N, K, code), dfu.dense_form(lib, M, K, N, code)      # y = x W^T; dx = dy' W
+    # several row tiles in the forward launch (the 42-wide dX of the fp32 cases is a narrower grid: whatever form it takes, its block
+    # height places the rows), in the arithmetic asked for
+    assert fwd[2] > 1 and all((form[0] == "nt") == (mma == "f32") for form in (fwd, bwd)), (fwd, bwd)
+    g = torch.Generator(device="cpu").manual_seed(M + K + N)
+    x0 = torch.randn(M, K, generator=g)
+    w = torch.randn(N, K, generator=g) / np.sqrt(K)
+    b = torch.randn(N, generator=g) * 0.1
+    gy0 = torch.randn(M, N, generator=g)
+    tol = DENSE_TOL[mma]
+    ops.set_dense_arithmetic(mma)
+    try:
+        for where, form in (("x", fwd), ("dy", bwd)):
+            BM = dfu.block_rows(form)
+            rows = sorted({0, 15, 16, BM - 1, BM, M - 1})
+            x, gy = x0.clone().numpy(), gy0.clone().numpy()
+            for r in rows:
+                _plant_row(x if where == "x" else gy, (r,), "nan")
+            xr = torch.from_numpy(x).double().requires_grad_(where == "dy")
+            y_ref = torch.nn.functional.gelu(torch.nn.functional.linear(xr, w.double(), b.double()))
+            xg = torch.from_numpy(x).cuda().requires_grad_(where == "dy")
+            if where == "x":
+                with torch.no_grad():
+                    got, ref = ops.linear(xg, w.cuda(), b.cuda(), gelu=True).cpu().numpy(), y_ref.detach().numpy()
+            else:
+                y_ref.backward(torch.from_numpy(gy).double())
+                ops.linear(xg, w.cuda(), b.cuda(), gelu=True).backward(torch.from_numpy(gy).cuda())
+                got, ref = xg.grad.cpu().numpy(), xr.grad.numpy()
+            bad_rows = np.flatnonzero(~np.isfinite(got).all(axis=1)).tolist()
+            assert bad_rows == rows, (where, form, bad_rows)
+            assert not np.isfinite(got[rows]).any(), (where, form)
+            _check((where, form), got, ref, tol, "nan", gelu=True)
     finally:
         ops.set_dense_arithmetic(None)
 
