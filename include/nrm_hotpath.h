@@ -427,6 +427,39 @@ int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const
 int nrm_pool_bmm_hragged(const float* s, const float* h, float* out, const int* cand_off, const int* hist_off, const int* hist_mult,
                          const int* tile_pre, int B, int N, int max_count, int R, int Mt, int k_max, int D, nrm_stream_t stream);
 
+/* Which kernel a launch of nrm_pwattn_fwd / _fwd_ragged / _fwd_hragged takes (additive entry point, the ABI version is unchanged): the
+ * answer of the selector the launches themselves switch on, without a kernel launch or an allocation, with the environment knobs applied
+ * as the launches apply them (NRM_FWD_CT, NRM_FWD_WALK_F32 and NRM_FWD_TSPLIT at every call; NRM_FWD_RW, NRM_FWD_13X1 and NRM_FWD_WALK
+ * as latched at their first use in the process).
+ *   ragged = 0: nrm_pwattn_fwd(B, T, H, D, mma) with (save_z = 1) or without a z buffer; N, max_count and k_max are not read.
+ *   ragged = 1: nrm_pwattn_fwd_ragged(B, N, max_count, H, D, mma); T is not read.
+ *   ragged = 2: nrm_pwattn_fwd_hragged(B, N, max_count, Mt = T, k_max, D, mma): T carries Mt, the number of 16-row score tiles; H is
+ *               not read.
+ *   cus: compute units of the device the launch would go to; 0: those of the current device, or 256 where there is none.
+ * out[NRM_PWATTN_FWD_FORM_LEN]:
+ *   [0] valid     0: the selection has no kernel and the launch is refused (a ragged form asked for with bf16 arithmetic or a z store, a
+ *                 ragged width of more than one resident slice under NRM_FWD_RW=2, a width the bf16 forward cannot hold)
+ *   [1] family    NRM_FWD_STREAM (pwattn_fwd_kernel), NRM_FWD_RW_TILE (pwattn_fwd_rw_kernel), NRM_FWD_WALK_BF16 (pwattn_fwd_walk_kernel),
+ *                 NRM_FWD_WALK_F32 (pwattn_fwd_walk_f32_kernel)
+ *   [2..6]        NT, MT, WPE, CT, NW of pwattn_fwd_kernel<NT, MT, SAVE_Z, WPE, CT, NW, ..> (NRM_FWD_STREAM; 0 otherwise)
+ *   [7], [8]      NTS of the resident forms, KCH of the walks (fp32 walk: KCH = NTS) (0 for NRM_FWD_STREAM)
+ *   [9..11]       mma, save_z, ragged as asked
+ *   [12] nsplit   column slices of the resident forms whose partial scores are added (1: one slice, no atomics)
+ *   [13] tsplit   parts the candidate walk of a task is cut into (walks; 1 otherwise)
+ *   [14]          workgroups of the launch
+ *   [15] tasks    16-row tiles (NRM_FWD_RW_TILE), walk tasks (impression x 16 history rows x part), workgroups (NRM_FWD_STREAM);
+ *                 0: the entry returns without a launch
+ *   [16] rounds   ceil(tasks / (workgroups per slice x waves per workgroup)), 16 waves in NRM_FWD_RW_TILE and 8 in the walks: how often
+ *                 the busiest wave goes round its persistent loop; 1 for NRM_FWD_STREAM
+ *   [17] nchunks  N-chunks the width is streamed in (NRM_FWD_STREAM; 0 otherwise)
+ * Returns 0, or -1 with nrm_last_error() set ("nrm_pwattn_fwd_form: ...") for arguments the launch entries refuse by value. */
+#define NRM_PWATTN_FWD_FORM_LEN 18
+#define NRM_FWD_STREAM 0
+#define NRM_FWD_RW_TILE 1
+#define NRM_FWD_WALK_BF16 2
+#define NRM_FWD_WALK_F32 3
+int nrm_pwattn_fwd_form(int B, int T, int H, int D, int mma, int save_z, int ragged, int N, int max_count, int k_max, int cus, int* out);
+
 /* ---- training on compacted histories: length groups through the dense kernels
  * The padded history rows are scored and pooled unmasked in training too (reference models/user_invariant_interest_model.py:77-78,
  * 83-87).  The batch is sorted by history length and cut into G contiguous groups; group g (impressions b0_g .. b0_{g+1} - 1 of the

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/nrm_hotpath.h"
+#include "common.hpp"
 #include "pwattn.hpp"
 #include "gemm.hpp"
 #include "head.hpp"
@@ -151,7 +152,7 @@ int nrm_pwattn_fwd(const float* t, const float* h, const float* u, const float* 
     if (mma != NRM_MMA_F32 && !nrm::pwattn_fwd_uses_rw(D, mma))
         return fail(NRM_EINVAL, "nrm_pwattn_fwd: D=%d is too wide for the bf16 forward (one 16-column slice of W_p must fit the LDS)", D);
     const nrm::FwdParams p = fwd_params(t, h, u, v, packed_wp, w2, b2, z, s, (long)B * T, T, B, H, D, pl);
-    return check_hip(nrm::pwattn_fwd_launch(p, pl, mma, (hipStream_t)stream), "pwattn_fwd");
+    return check_hip(nrm::pwattn_fwd_launch(p, mma, (hipStream_t)stream), "pwattn_fwd");
 }
 
 int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
@@ -173,7 +174,7 @@ int nrm_pwattn_fwd_ragged(const float* t, const float* h, const float* u, const 
     const nrm::FwdParams p = fwd_params(t, h, u, v, packed_wp, w2, b2, nullptr, s, N, 1, B, H, D, pl);
     nrm::RaggedTabs rg;
     rg.cand_imp = cand_imp; rg.cand_off = cand_off; rg.B = B; rg.N = N; rg.max_count = max_count;
-    return check_hip(nrm::pwattn_fwd_ragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_ragged");
+    return check_hip(nrm::pwattn_fwd_ragged_launch(p, rg, (hipStream_t)stream), "pwattn_fwd_ragged");
 }
 
 int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const float* v, const float* packed_wp,
@@ -202,7 +203,40 @@ int nrm_pwattn_fwd_hragged(const float* t, const float* h, const float* u, const
     nrm::RaggedTabs rg;
     rg.cand_imp = cand_imp; rg.cand_off = cand_off; rg.B = B; rg.N = N; rg.max_count = max_count;
     rg.hist_off = hist_off; rg.tile_pre = tile_pre; rg.tile_tab = (const int4*)tile_tab; rg.R = R; rg.Mt = Mt; rg.k_max = k_max;
-    return check_hip(nrm::pwattn_fwd_hragged_launch(p, pl, rg, (hipStream_t)stream), "pwattn_fwd_hragged");
+    return check_hip(nrm::pwattn_fwd_hragged_launch(p, rg, (hipStream_t)stream), "pwattn_fwd_hragged");
+}
+
+int nrm_pwattn_fwd_form(int B, int T, int H, int D, int mma, int save_z, int ragged, int N, int max_count, int k_max, int cus, int* out) {
+    const char* fn = "nrm_pwattn_fwd_form";
+    if (!out) { fail(NRM_EINVAL, "%s: null pointer", fn); return -1; }
+    if (check_mma(fn, mma)) return -1;
+    if (ragged < 0 || ragged > 2 || (save_z != 0 && save_z != 1) || cus < 0) {
+        fail(NRM_EINVAL, "%s: save_z=%d ragged=%d cus=%d (save_z 0 or 1, ragged 0, 1 or 2, cus >= 0)", fn, save_z, ragged, cus);
+        return -1;
+    }
+    long M;
+    if (ragged == 0) {
+        if (check_dims(fn, B, T, H, D)) return -1;
+        M = (long)B * T * H;
+    } else {
+        // the checks of nrm_pwattn_fwd_ragged / _hragged that need no pointer; ragged == 2: T is Mt, the number of 16-row score tiles
+        const int Mt = ragged == 2 ? T : 0;
+        if (ragged == 2) H = 1;
+        if (B < 0 || N < 0 || max_count < 0 || max_count > N || H <= 0 || D <= 0 || D % 4 || D > 1024 || Mt < 0 || k_max < 0 ||
+            (ragged == 1 ? (long)N * H : 16L * Mt) >= (1L << 31) || (long)N * D >= (1L << 29)) {
+            fail(NRM_EINVAL, "%s: B=%d N=%d max_count=%d H=%d D=%d Mt=%d k_max=%d (B, N, Mt, k_max >= 0, 0 <= max_count <= N, H > 0, D a positive "
+                             "multiple of 4 up to 1024, fewer than 2^31 rows)", fn, B, N, max_count, H, D, Mt, k_max);
+            return -1;
+        }
+        M = ragged == 1 ? (long)N * H : 16L * Mt;
+        if (N == 0 || B == 0) M = 0;                                     // the entries return before any launch
+        T = 1;
+    }
+    const nrm::FwdForm f = nrm::pwattn_fwd_select(M, B, T, H, D, mma, save_z != 0, ragged, N, max_count, k_max, cus ? cus : nrm::device_cus());
+    const int v[NRM_PWATTN_FWD_FORM_LEN] = {f.valid, f.family, f.NT, f.MT, f.WPE, f.CT, f.NW, f.NTS, f.KCH, f.mma, f.save_z, f.ragged,
+                                            f.nsplit, f.tsplit, f.wgs * (f.nsplit > 0 ? f.nsplit : 1), (int)f.tasks, f.rounds, f.nchunks};
+    for (int i = 0; i < NRM_PWATTN_FWD_FORM_LEN; ++i) out[i] = v[i];
+    return 0;
 }
 
 int nrm_pwattn_bwd_dz(float* z_inout, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,

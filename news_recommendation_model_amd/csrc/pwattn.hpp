@@ -41,20 +41,43 @@ struct RaggedTabs {
 };
 struct FwdPlan { int NT, MT, nchunks, rows, kchunks; };
 FwdPlan pwattn_fwd_plan(int D);
-hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st);
+// Every environment knob of the forward, read in ONE place (fwd_knobs, pwattn_fwd.hip).  rw_mode (NRM_FWD_RW), use13 (NRM_FWD_13X1) and
+// walk (NRM_FWD_WALK) are latched at the first call in the process -- the packed W_p image depends on the first two; ct (NRM_FWD_CT),
+// walk_f32 (NRM_FWD_WALK_F32) and tsplit (NRM_FWD_TSPLIT) are read at every call.  ct / walk_f32: -1 unset, 0, 1.
+struct FwdKnobs { int rw_mode, use13, walk, ct, walk_f32, tsplit; bool tsplit_set; };      // tsplit counts only where tsplit_set
+FwdKnobs fwd_knobs();
+// What one forward launch runs: chosen by pwattn_fwd_select (host arithmetic only, no HIP call); the launches switch on it and on nothing else.
+enum FwdFamily { FWD_STREAM = 0, FWD_RW_TILE = 1, FWD_WALK_BF16 = 2, FWD_WALK_F32 = 3 };
+struct FwdForm {
+    int valid;                    // 0: the selection has no instantiation (the launch returns hipErrorInvalidValue)
+    int family;                   // FwdFamily
+    int NT, MT, WPE, CT, NW;      // FWD_STREAM: pwattn_fwd_kernel<NT, MT, SAVE_Z, WPE, CT, NW, RAGGED, HRAG>
+    int NTS, KCH;                 // FWD_RW_TILE: pwattn_fwd_rw_kernel<NTS, ..>; the walks: <NTS, .., KCH> (fp32 walk: KCH = NTS)
+    int mma, save_z, ragged;      // arithmetic; z stored; 0 dense, 1 candidates, 2 candidates and history
+    int nsplit, tsplit;           // column slices of the resident forms (1 otherwise); parts of the candidate walk (1 otherwise)
+    int wgs;                      // workgroups per slice (the grid is wgs * nsplit)
+    long tasks;                   // row tiles (FWD_RW_TILE), walk tasks, or workgroups (FWD_STREAM); 0: nothing is launched
+    int rounds;                   // ceil(tasks / (wgs * waves per workgroup)): trips of the busiest wave's persistent loop; FWD_STREAM: 1
+    int nchunks;                  // FWD_STREAM: N-chunks the width is streamed in
+};
+// M: flattened rows (B T H dense, N H ragged, 16 Mt history-ragged); B: impressions; T, H as in FwdParams (ragged: T = 1; history-ragged:
+// H = 1); N, max_count, k_max as in RaggedTabs (ragged forms only); cus: compute units of the device the launch goes to
+FwdForm pwattn_fwd_select(long M, int B, int T, int H, int D, int mma, bool save_z, int ragged, int N, int max_count, int k_max, int cus);
+FwdForm pwattn_fwd_rw_select(long M, int B, int T, int H, int D, int mma, bool save_z, int ragged, int N, int max_count, int k_max, int cus,
+                             const FwdKnobs& kn);
+hipError_t pwattn_fwd_launch(const FwdParams& p, int mma, hipStream_t st);
 // fp32 arithmetic, no z store; p.M = N * H, p.T is not read
-hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st);
+hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);
 // ragged in the history too: p.M = 16 * rg.Mt, p.h_bytes covers the R kept rows, p.T and p.H are not read
-hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st);
+hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);
 hipError_t pack_wp_launch(const float* w, int ldw, int D, const FwdPlan& pl, int mma, float* packed, hipStream_t st);
 // resident-W forward (pwattn_fwd_rw.hip): mma = 0 (fp32 MFMA), 1 (bf16 operands) or 2 (bf16x3: hi + lo split).  The output
 // columns are cut into nsplit slices of nts 16-column tiles whose whole image stays resident in LDS (persistent workgroups).
 struct RwPlan { int nts, nsplit, rows, k32, wimg; };      // rows = padded rows of the packed image = nsplit * nts * 16; k32 = chunks
 RwPlan pwattn_rw_plan(int D, int mma);
 bool pwattn_fwd_uses_rw(int D, int mma);                  // which forward (and which packed layout) a call takes
-hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st);
-hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);     // fp32, D <= 128 (one resident slice)
-hipError_t pwattn_fwd_rw_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st);    // the same widths, history-ragged
+// launches a FWD_RW_TILE / FWD_WALK_* form (ragged: fp32, D <= 128 -- one resident slice); called by the launches of pwattn_fwd.hip
+hipError_t pwattn_fwd_rw_launch_form(const FwdParams& p, const RaggedTabs& rg, const struct FwdForm& f, hipStream_t st);
 hipError_t pack_wp_bf16_launch(const float* w, int ldw, int D, int mma, float* packed, hipStream_t st);
 
 // ---- backward (pwattn_bwd.hip)

@@ -322,6 +322,22 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
 static const int kNT[10] = {4, 6, 8, 10, 12, 13, 14, 16, 20, 25};
 static const int kMT[10] = {4, 4, 3, 1, 1, 1, 2, 1, 1, 1};     // 10..13 tiles: one row tile per wave, 3 waves/SIMD (3 row tiles spilled)
 
+// Every environment knob of the forward (pwattn.hpp).  The three latched ones are read at the first call in the process.
+FwdKnobs fwd_knobs() {
+    static const int rw_mode = [] { const char* e = getenv("NRM_FWD_RW"); return e ? atoi(e) : 1; }();
+    static const int use13 = [] { const char* e = getenv("NRM_FWD_13X1"); return e && e[0] == '0' ? 0 : 1; }();
+    static const int walk = [] { const char* e = getenv("NRM_FWD_WALK"); return e && e[0] == '0' ? 0 : 1; }();
+    FwdKnobs kn;
+    kn.rw_mode = rw_mode; kn.use13 = use13; kn.walk = walk;
+    const char* e = getenv("NRM_FWD_CT");                             // (read per launch: tests switch forms inside one process)
+    kn.ct = e ? (e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1) : -1;
+    e = getenv("NRM_FWD_WALK_F32");
+    kn.walk_f32 = e ? (e[0] == '1' ? 1 : 0) : -1;
+    e = getenv("NRM_FWD_TSPLIT");
+    kn.tsplit_set = e != nullptr; kn.tsplit = e ? atoi(e) : 0;
+    return kn;
+}
+
 FwdPlan pwattn_fwd_plan(int D) {
     const int n16 = (D + 15) / 16;
     int nch = n16 <= 25 ? 1 : (n16 + 15) / 16;          // wider than 25 tiles: chunks of at most 16 tiles
@@ -330,8 +346,7 @@ FwdPlan pwattn_fwd_plan(int D) {
     // D = 400: 4.14 ms against 4.29 ms for the single 25-tile chunk, although the rows are streamed twice and the last
     // chunk carries one all-padding tile (its MFMAs are skipped); three chunks of 10 tiles at four workgroups per CU:
     // 4.27 ms.  NRM_FWD_13X1=0 restores the one-chunk plan.
-    static const int use13 = [] { const char* e = getenv("NRM_FWD_13X1"); return e && e[0] == '0' ? 0 : 1; }();
-    if (use13 && n16 >= 21 && n16 <= 26) nch = 2;
+    if (fwd_knobs().use13 && n16 >= 21 && n16 <= 26) nch = 2;
     const int need = (n16 + nch - 1) / nch;
     int sel = 9;
     for (int i = 0; i < 10; ++i) if (kNT[i] >= need) { sel = i; break; }
@@ -341,78 +356,13 @@ FwdPlan pwattn_fwd_plan(int D) {
     return pl;
 }
 
-// RAGGED: fp32 arithmetic, no z store (the only ragged instantiations there are)
-template <int RAGGED, int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>      // RAGGED: 0 dense, 1 candidates, 2 candidates and history
-static hipError_t launch_fwd_t(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
-    constexpr int BM = NW * MT * 16;
-    const long nblk = (p.M + BM - 1) / BM;
-    if (nblk <= 0) return hipSuccess;
-    if (nblk > 0x7fffffffL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)nblk), block(NW * 64);
-    if constexpr (RAGGED == 2) {
-        if constexpr (NW * MT <= 16) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true, true>), grid, block, 0, st, p, rg);
-        else return hipErrorInvalidValue;
-    }
-    else if constexpr (RAGGED == 1) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true>), grid, block, 0, st, p, rg);
-    else if (p.z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), grid, block, 0, st, p, rg);
-    else          hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), grid, block, 0, st, p, rg);
-    return hipGetLastError();
-}
-
 // compact candidate image (template parameter CT): histories of at least 16 rows (a workgroup's 64 rows then span <= 5 candidates and a
 // 16-lane read group <= 2); NRM_FWD_CT=0 keeps the per-row image (round 3), =1 forces the compact one for any H >= 5
-static bool fwd_compact_t(int H, int block_rows = 64) {
-    const char* e = getenv("NRM_FWD_CT");                         // (read per launch: tests switch forms inside one process)
-    if (e && e[0] == '0') return false;
+static bool fwd_compact_t(const FwdKnobs& kn, int H, int block_rows = 64) {
+    if (kn.ct == 0) return false;
     if ((block_rows - 1) / H + 2 > 16) return false;             // the image holds 16 candidate rows
-    if (e && e[0] == '1') return true;
+    if (kn.ct == 1) return true;
     return H >= 16;
-}
-
-// the chunk-streaming kernel for the plan's tiles, dense or ragged
-template <int RAGGED>
-static hipError_t fwd_dispatch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
-#define NRM_FWD(...) launch_fwd_t<RAGGED, __VA_ARGS__>(p, rg, st)
-    // history-ragged: tiles never straddle candidates, so the compact image holds for any history of at least one whole tile
-    auto fwd_compact_t = [&](int H, int block_rows = 64) { return RAGGED == 2 ? nrm::fwd_compact_t(rg.k_max >= 16 ? 64 : 1, block_rows) : nrm::fwd_compact_t(H, block_rows); };
-    switch (pl.NT) {
-        case 4:  return NRM_FWD(4, 4);
-        case 6:  return NRM_FWD(6, 4);
-        case 8:  return NRM_FWD(8, 3);
-        case 10: return fwd_compact_t(p.H) ? NRM_FWD(10, 1, 4, true) : NRM_FWD(10, 1, 3);
-        case 12: return fwd_compact_t(p.H) ? NRM_FWD(12, 1, 4, true) : NRM_FWD(12, 1, 3);
-        case 13:
-            if (!fwd_compact_t(p.H, NRM_FWD_NW8 && !RAGGED ? 128 : 64)) return NRM_FWD(13, 1, 3);
-#if NRM_FWD_NW8
-            if constexpr (!RAGGED) return NRM_FWD(13, 1, 4, true, 8);   // tuning: 128-row workgroups of 8 waves, two per CU (dense only)
-            else
-#endif
-            return NRM_FWD(13, 1, 4, true);
-        case 14: return NRM_FWD(14, 2);
-        case 16: return NRM_FWD(16, 1);        // (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms)
-        case 20: return NRM_FWD(20, 1);
-        case 25: return NRM_FWD(25, 1);
-    }
-#undef NRM_FWD
-    return hipErrorInvalidValue;
-}
-
-hipError_t pwattn_fwd_launch(const FwdParams& p, const FwdPlan& pl, int mma, hipStream_t st) {
-    if (pwattn_fwd_uses_rw(p.D, mma)) return pwattn_fwd_rw_launch(p, mma, st);
-    return fwd_dispatch<0>(p, pl, RaggedTabs{}, st);
-}
-
-// Ragged candidate lists: the plan of the dense forward for the same D and H (same tiles, same image choice); widths whose whole
-// W_p is one resident slice (D <= 128) take the resident-W forms, as the dense forward does -- the packed image is the same.
-hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
-    if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_ragged_launch(p, rg, st);
-    return fwd_dispatch<1>(p, pl, rg, st);
-}
-
-// Ragged in the history too (section 5d): the same plan and the same choice between the resident-W and the streaming forms.
-hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const FwdPlan& pl, const RaggedTabs& rg, hipStream_t st) {
-    if (pwattn_fwd_uses_rw(p.D, 0)) return pwattn_fwd_rw_hragged_launch(p, rg, st);
-    return fwd_dispatch<2>(p, pl, rg, st);
 }
 
 // bf16 forms: always the resident-W forward (pwattn_fwd_rw.hip).  fp32: only where the WHOLE W_p fits one LDS slice
@@ -420,11 +370,107 @@ hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const FwdPlan& pl, cons
 // (measured at C3, D = 400, 5 slices: 4.32 vs 4.13 ms; C5, D = 768: 20.5 vs 19.4 ms) and keeps the scores free of float
 // atomics.  NRM_FWD_RW=0 / =2 force the streaming / the resident form for fp32.
 bool pwattn_fwd_uses_rw(int D, int mma) {
-    static const int mode = [] { const char* e = getenv("NRM_FWD_RW"); return e ? atoi(e) : 1; }();
+    const int mode = fwd_knobs().rw_mode;
     const RwPlan pl = pwattn_rw_plan(D, mma);
     if (pl.nts == 0) return false;
     if (mma != 0) return true;
     return mode == 2 || (mode == 1 && pl.nsplit == 1);
+}
+
+// THE selector of the forward: which kernel a dense, ragged or history-ragged launch runs, with which template parameters and grid.
+// Ragged candidate lists take the plan of the dense forward for the same D and H (same tiles, same image choice); widths whose whole W_p
+// is one resident slice (D <= 128) take the resident-W forms, as the dense forward does -- the packed image is the same.  The ragged
+// instantiations have fp32 arithmetic and no z store (the only ones there are).
+FwdForm pwattn_fwd_select(long M, int B, int T, int H, int D, int mma, bool save_z, int ragged, int N, int max_count, int k_max, int cus) {
+    const FwdKnobs kn = fwd_knobs();
+    if (pwattn_fwd_uses_rw(D, ragged ? 0 : mma)) return pwattn_fwd_rw_select(M, B, T, H, D, mma, save_z, ragged, N, max_count, k_max, cus, kn);
+    FwdForm f = {};
+    f.family = FWD_STREAM; f.mma = mma; f.save_z = save_z; f.ragged = ragged;
+    f.nsplit = 1; f.tsplit = 1; f.WPE = 2; f.NW = 4;
+    const FwdPlan pl = pwattn_fwd_plan(D);
+    f.NT = pl.NT; f.MT = pl.MT; f.nchunks = pl.nchunks;
+    // history-ragged: tiles never straddle candidates, so the compact image holds for any history of at least one whole tile
+    auto compact = [&](int block_rows) { return fwd_compact_t(kn, ragged == 2 ? (k_max >= 16 ? 64 : 1) : H, block_rows); };
+    switch (pl.NT) {
+        case 10: case 12:
+            if (compact(64)) { f.WPE = 4; f.CT = 1; } else f.WPE = 3;
+            break;
+        case 13:
+            if (!compact(NRM_FWD_NW8 && !ragged ? 128 : 64)) { f.WPE = 3; break; }
+            f.WPE = 4; f.CT = 1;
+#if NRM_FWD_NW8
+            if (!ragged) f.NW = 8;                 // tuning: 128-row workgroups of 8 waves, two per CU (dense only)
+#endif
+            break;
+        default: break;                            // 4x4, 6x4, 8x3, 14x2, 16x1 (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms), 20x1, 25x1
+    }
+    const int BM = f.NW * f.MT * 16;
+    f.tasks = M > 0 ? (M + BM - 1) / BM : 0;
+    f.wgs = (int)(f.tasks > 0x7fffffffL ? 0x7fffffffL : f.tasks);
+    f.rounds = f.tasks > 0 ? 1 : 0;
+    // fp32 arithmetic only; the ragged forms store no z; a history-ragged workgroup holds at most 16 tiles (its compact image has 16 rows)
+    f.valid = mma == 0 && !(ragged && save_z) && !(ragged == 2 && f.NW * f.MT > 16) && f.tasks <= 0x7fffffffL;
+    return f;
+}
+
+template <int RAGGED, int NT, int MT, int WPE = 2, bool CT = false, int NW = 4>      // RAGGED: 0 dense, 1 candidates, 2 candidates and history
+static hipError_t launch_fwd_t(const FwdParams& p, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+    const dim3 grid((unsigned)f.wgs), block(NW * 64);
+    if constexpr (RAGGED == 2) {
+        if constexpr (NW * MT <= 16) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true, true>), grid, block, 0, st, p, rg);
+        else return hipErrorInvalidValue;
+    }
+    else if constexpr (RAGGED == 1) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW, true>), grid, block, 0, st, p, rg);
+    else if (f.save_z) hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, true, WPE, CT, NW>), grid, block, 0, st, p, rg);
+    else               hipLaunchKernelGGL((pwattn_fwd_kernel<NT, MT, false, WPE, CT, NW>), grid, block, 0, st, p, rg);
+    return hipGetLastError();
+}
+
+// the chunk-streaming kernel of a FWD_STREAM form, dense or ragged
+template <int RAGGED>
+static hipError_t fwd_dispatch(const FwdParams& p, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+#define NRM_FWD(...) launch_fwd_t<RAGGED, __VA_ARGS__>(p, rg, f, st)
+    switch (f.NT) {
+        case 4:  return NRM_FWD(4, 4);
+        case 6:  return NRM_FWD(6, 4);
+        case 8:  return NRM_FWD(8, 3);
+        case 10: return f.CT ? NRM_FWD(10, 1, 4, true) : NRM_FWD(10, 1, 3);
+        case 12: return f.CT ? NRM_FWD(12, 1, 4, true) : NRM_FWD(12, 1, 3);
+        case 13:
+            if (!f.CT) return NRM_FWD(13, 1, 3);
+#if NRM_FWD_NW8
+            if constexpr (!RAGGED) { if (f.NW == 8) return NRM_FWD(13, 1, 4, true, 8); }
+#endif
+            return NRM_FWD(13, 1, 4, true);
+        case 14: return NRM_FWD(14, 2);
+        case 16: return NRM_FWD(16, 1);
+        case 20: return NRM_FWD(20, 1);
+        case 25: return NRM_FWD(25, 1);
+    }
+#undef NRM_FWD
+    return hipErrorInvalidValue;
+}
+
+// one launch path for the three entries: the selector's answer, and nothing else, decides what runs
+static hipError_t fwd_launch_form(const FwdParams& p, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+    if (!f.valid) return hipErrorInvalidValue;
+    if (f.tasks <= 0) return hipSuccess;
+    if (f.family != FWD_STREAM) return pwattn_fwd_rw_launch_form(p, rg, f, st);
+    return f.ragged == 2 ? fwd_dispatch<2>(p, rg, f, st) : f.ragged == 1 ? fwd_dispatch<1>(p, rg, f, st) : fwd_dispatch<0>(p, rg, f, st);
+}
+
+hipError_t pwattn_fwd_launch(const FwdParams& p, int mma, hipStream_t st) {
+    const long rows = (long)p.T * p.H;
+    return fwd_launch_form(p, RaggedTabs{}, pwattn_fwd_select(p.M, (int)(p.M / rows), p.T, p.H, p.D, mma, p.z != nullptr, 0, 0, 0, 0, device_cus()), st);
+}
+
+hipError_t pwattn_fwd_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
+    return fwd_launch_form(p, rg, pwattn_fwd_select(p.M, rg.B, p.T, p.H, p.D, 0, false, 1, rg.N, rg.max_count, 0, device_cus()), st);
+}
+
+// Ragged in the history too (section 5d): the same plan and the same choice between the resident-W and the streaming forms.
+hipError_t pwattn_fwd_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) {
+    return fwd_launch_form(p, rg, pwattn_fwd_select(p.M, rg.B, p.T, p.H, p.D, 0, false, 2, rg.N, rg.max_count, rg.k_max, device_cus()), st);
 }
 
 int pwattn_fwd_diag_flags() { return (NRM_DIAG_FWD ? 1 : 0) | (XCD_REMAP != 1 ? 2 : 0); }

@@ -559,34 +559,30 @@ __global__ __launch_bounds__(512, 2) void pwattn_fwd_walk_f32_kernel(const FwdPa
 #endif
 }
 
-// The launchers take the dense and the ragged (compact scoring) form alike: rg != nullptr selects the RAGGED instantiation, which exists
-// for fp32 arithmetic without a z store only.
+// The launchers take the dense and the ragged (compact scoring) form alike: f.ragged selects the RAGGED instantiation, which exists
+// for fp32 arithmetic without a z store only.  Grid, slices and walk parts are the selector's (pwattn_fwd_rw_select).
 template <int NTS>
-static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, int mma, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
-    const int ntile = (int)((p.M + 15) / 16);
-    if (ntile <= 0) return hipSuccess;
-    int wgs = device_cus() / pl.nsplit;                                     // one persistent workgroup per CU, CUs shared evenly by the slices
-    if (wgs < 1) wgs = 1;
-    if ((long)wgs * FB_WAVES > ntile) wgs = (ntile + FB_WAVES - 1) / FB_WAVES;
+static hipError_t launch_rw(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+    const int wgs = f.wgs;
     const size_t shm = (size_t)pl.k32 * pl.wimg * NTS * 1024;
-    if (pl.nsplit > 1) {                                                // the slices ADD their partial scores
+    if (f.nsplit > 1) {                                                 // the slices ADD their partial scores
         hipError_t e = hipMemsetAsync(p.s, 0, (size_t)p.M * sizeof(float), st);
         if (e != hipSuccess) return e;
     }
-    const dim3 grid((unsigned)(wgs * pl.nsplit)), block(FB_WAVES * 64);
+    const dim3 grid((unsigned)(wgs * f.nsplit)), block(FB_WAVES * 64);
 #define NRM_RW(SZ, M_, RG, ...)                                                                                          \
     {                                                                                                                    \
         auto k = pwattn_fwd_rw_kernel<NTS, SZ, M_, RG, ##__VA_ARGS__>;                                                               \
         /* per launch: the attribute is per device, and a process may launch on more than one */                        \
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_BUDGET);  \
         if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, RG ? *rg : RaggedTabs{});                                \
+        hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, rg);                                                     \
     }
-    if (rg && hrag)    NRM_RW(false, 0, true, true)
-    else if (rg)       NRM_RW(false, 0, true)
-    else if (mma == 2) { if (p.z) NRM_RW(true, 2, false) else NRM_RW(false, 2, false) }
-    else if (mma == 1) { if (p.z) NRM_RW(true, 1, false) else NRM_RW(false, 1, false) }
-    else               { if (p.z) NRM_RW(true, 0, false) else NRM_RW(false, 0, false) }
+    if (f.ragged == 2)    NRM_RW(false, 0, true, true)
+    else if (f.ragged)    NRM_RW(false, 0, true)
+    else if (f.mma == 2) { if (f.save_z) NRM_RW(true, 2, false) else NRM_RW(false, 2, false) }
+    else if (f.mma == 1) { if (f.save_z) NRM_RW(true, 1, false) else NRM_RW(false, 1, false) }
+    else                 { if (f.save_z) NRM_RW(true, 0, false) else NRM_RW(false, 0, false) }
 #undef NRM_RW
     return hipGetLastError();
 }
@@ -596,32 +592,28 @@ int pwattn_fwd_rw_diag_flags() { return NRM_DIAG_RW ? 4 : 0; }
 // Grid rule of the walks.  `base` tasks (impression x 16 history rows) are cut along the candidates into `tsplit` parts until two rounds
 // of 8-wave workgroups are filled, while a part of a list of `len` candidates keeps at least `min_part` of them; NRM_FWD_TSPLIT overrides
 // the cut (read per launch), `clamp` bounds it.  In: wgs = the workgroups the chip takes; out: tsplit, and wgs shrunk to the tasks there are.
-static hipError_t walk_grid(long base, int len, int min_part, int clamp, int& wgs, int& tsplit) {
+// false: more tasks than the kernels count in an int.
+static bool walk_grid(const FwdKnobs& kn, long base, int len, int min_part, int clamp, int& wgs, int& tsplit) {
     tsplit = 1;
-    if (const char* e = getenv("NRM_FWD_TSPLIT")) tsplit = atoi(e);
+    if (kn.tsplit_set) tsplit = kn.tsplit;
     else while (base * tsplit < 2L * wgs * 8 && len / (tsplit + 1) >= min_part) ++tsplit;
     if (tsplit < 1) tsplit = 1;
     if (tsplit > clamp) tsplit = clamp > 0 ? clamp : 1;
     const long ntask = base * tsplit;
-    if (ntask > 0x7fffffffL) return hipErrorInvalidValue;             // the kernels count tasks in an int
+    if (ntask > 0x7fffffffL) return false;
     if ((long)wgs * 8 > ntask) wgs = (int)((ntask + 7) / 8);
-    return hipSuccess;
+    return true;
 }
 
 template <int NTS, int KCH>
-static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hipStream_t st) {
-    const int B = (int)(p.M / ((long)p.T * p.H)), nht = (p.H + 15) / 16;
-    const long base = (long)B * nht;
-    if (base <= 0) return hipSuccess;
-    int wgs = device_cus() / pl.nsplit, tsplit;
-    if (wgs < 1) wgs = 1;
-    if (hipError_t e = walk_grid(base, p.T, 8, p.T, wgs, tsplit)) return e;
+static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, const FwdForm& f, hipStream_t st) {
+    const int wgs = f.wgs, tsplit = f.tsplit;
     const size_t shm = (size_t)pl.k32 * pl.wimg * NTS * 1024;
-    if (pl.nsplit > 1) {
+    if (f.nsplit > 1) {
         hipError_t e = hipMemsetAsync(p.s, 0, (size_t)p.M * sizeof(float), st);
         if (e != hipSuccess) return e;
     }
-    const dim3 grid((unsigned)(wgs * pl.nsplit)), block(512);
+    const dim3 grid((unsigned)(wgs * f.nsplit)), block(512);
 #define NRM_WALK(SZ, M_)                                                                                                 \
     {                                                                                                                    \
         auto k = pwattn_fwd_walk_kernel<NTS, SZ, M_, KCH>;                                                               \
@@ -629,76 +621,110 @@ static hipError_t launch_walk(const FwdParams& p, const RwPlan& pl, int mma, hip
         if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs, tsplit);                                                 \
     }
-    if (mma == 2) { if (p.z) NRM_WALK(true, 2) else NRM_WALK(false, 2) }
-    else          { if (p.z) NRM_WALK(true, 1) else NRM_WALK(false, 1) }
+    if (f.mma == 2) { if (f.save_z) NRM_WALK(true, 2) else NRM_WALK(false, 2) }
+    else            { if (f.save_z) NRM_WALK(true, 1) else NRM_WALK(false, 1) }
 #undef NRM_WALK
     return hipGetLastError();
 }
 
-// ragged: the same grid rule with the MEAN list length in T's place (the cut itself is per impression, in the kernel)
 template <int NTS>
-static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
-    const int B = rg ? rg->B : (int)(p.M / ((long)p.T * p.H)), nht = ((hrag ? rg->k_max : p.H) + 15) / 16;
-    const long base = (long)B * nht;
-    if (base <= 0 || (rg && rg->N <= 0)) return hipSuccess;
-    int wgs = 2 * device_cus(), tsplit;                                     // two workgroups of 8 waves per CU
-    if (hipError_t e = walk_grid(base, rg ? (rg->N + rg->B - 1) / rg->B : p.T, 4, rg ? rg->max_count : p.T, wgs, tsplit)) return e;
+static hipError_t launch_walk_f32(const FwdParams& p, const RwPlan& pl, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+    const int wgs = f.wgs, tsplit = f.tsplit;
     const size_t shm = (size_t)pl.k32 * NTS * 1024;
     const dim3 grid((unsigned)wgs), block(512);
-    if (rg && hrag) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
-    else if (rg)  hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), grid, block, shm, st, p, pl, wgs, tsplit, *rg);
-    else if (p.z) hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
-    else          hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, RaggedTabs{});
+    if (f.ragged == 2)  hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true, true>), grid, block, shm, st, p, pl, wgs, tsplit, rg);
+    else if (f.ragged)  hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS, true>), grid, block, shm, st, p, pl, wgs, tsplit, rg);
+    else if (f.save_z)  hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, true, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, rg);
+    else                hipLaunchKernelGGL((pwattn_fwd_walk_f32_kernel<NTS, false, NTS>), grid, block, shm, st, p, pl, wgs, tsplit, rg);
     return hipGetLastError();
 }
 
 // Which fp32 walk, if any, a width takes (NRM_FWD_WALK_F32=0|1 forces, read per launch): its NTS, or 0 for the tile-by-tile form
-static int walk_f32_nts(int D) {
-    const char* e = getenv("NRM_FWD_WALK_F32");
-    if ((e ? e[0] == '1' : true) && D == 64) return 4;
+static int walk_f32_nts(const FwdKnobs& kn, int D) {
+    if (kn.walk_f32 != 0 && D == 64) return 4;
     // D = 128: h + u + accumulators + v take 196 VGPRs (two waves per SIMD): not the default, NRM_FWD_WALK_F32=1 selects it
-    if (e && e[0] == '1' && D == 128) return 8;
+    if (kn.walk_f32 == 1 && D == 128) return 8;
     return 0;
 }
 
-// the bf16 walks: NRM_FWD_WALK=0 keeps the tile-by-tile form (read once, at the first dense launch)
-static bool fwd_walk_enabled() {
-    static const bool on = [] { const char* e = getenv("NRM_FWD_WALK"); return !(e && e[0] == '0'); }();
-    return on;
+// The resident-W side of pwattn_fwd_select (host arithmetic only).  Ragged candidate lists: fp32 only, widths that are one resident slice;
+// T = 1 and M = N H there, so the walk where the dense forward walks, the tile-by-tile form otherwise.  The bf16 walks: NRM_FWD_WALK=0
+// keeps the tile-by-tile form.  The grids: one persistent 16-wave workgroup per CU for the tile form and the bf16 walks, the CUs shared
+// evenly by the slices; two 8-wave workgroups per CU for the fp32 walk (ragged: the grid rule with the MEAN list length in T's place, the
+// cut itself is per impression, in the kernel); every grid shrunk to the work there is.
+FwdForm pwattn_fwd_rw_select(long M, int B, int T, int H, int D, int mma, bool save_z, int ragged, int N, int max_count, int k_max, int cus,
+                             const FwdKnobs& kn) {
+    FwdForm f = {};
+    f.family = FWD_RW_TILE; f.mma = mma; f.save_z = save_z; f.ragged = ragged; f.tsplit = 1;
+    const bool hrag = ragged == 2;
+    const RwPlan pl = pwattn_rw_plan(D, mma);
+    f.NTS = pl.nts; f.nsplit = pl.nsplit;
+    if (pl.nts == 0 || (ragged && (mma != 0 || save_z || pl.nsplit != 1))) return f;          // valid = 0
+    const bool walkable = hrag || (M % ((long)T * H) == 0 && (long)T * H * D * 4 < (1L << 31));
+    int walk_nts = 0, kch = 0;
+    // fp32: the walk for the widths that are one resident slice of whole 16-column tiles
+    if (mma == 0 && pl.nsplit == 1 && D == pl.nts * 16 && walkable) walk_nts = kch = walk_f32_nts(kn, D);
+    if (walk_nts) f.family = FWD_WALK_F32;
+    else if (!ragged && kn.walk && mma != 0 && walkable) {
+        if (D == 256 && pl.nts == 8) { walk_nts = 8; kch = 8; }
+        else if (D == 128 && pl.nts == 8) { walk_nts = 8; kch = 4; }
+        else if (D == 64 && pl.nts == 4) { walk_nts = 4; kch = 2; }
+        if (walk_nts) f.family = FWD_WALK_BF16;
+    }
+    if (f.family == FWD_RW_TILE) {
+        const long ntile = (M + 15) / 16;
+        int wgs = cus / pl.nsplit;                                      // one persistent workgroup per CU, CUs shared evenly by the slices
+        if (wgs < 1) wgs = 1;
+        if ((long)wgs * FB_WAVES > ntile) wgs = (int)((ntile + FB_WAVES - 1) / FB_WAVES);
+        f.wgs = wgs; f.tasks = ntile > 0 ? ntile : 0;
+        f.rounds = ntile > 0 ? (int)((ntile + (long)wgs * FB_WAVES - 1) / ((long)wgs * FB_WAVES)) : 0;
+        f.valid = ntile <= 0x7fffffffL;
+        return f;
+    }
+    f.KCH = kch;
+    const int nb = ragged ? B : (int)(M / ((long)T * H)), nht = ((hrag ? k_max : H) + 15) / 16;
+    const long base = (long)nb * nht;
+    f.valid = 1;
+    if (base <= 0 || (ragged && N <= 0)) return f;                      // nothing to launch: tasks = 0
+    int wgs, tsplit;
+    bool ok;
+    if (f.family == FWD_WALK_BF16) {
+        wgs = cus / pl.nsplit;
+        if (wgs < 1) wgs = 1;
+        ok = walk_grid(kn, base, T, 8, T, wgs, tsplit);
+    } else {
+        wgs = 2 * cus;                                                  // two workgroups of 8 waves per CU
+        ok = walk_grid(kn, base, ragged ? (N + B - 1) / B : T, 4, ragged ? max_count : T, wgs, tsplit);
+    }
+    if (!ok) { f.valid = 0; return f; }
+    f.wgs = wgs; f.tsplit = tsplit; f.tasks = base * tsplit;
+    f.rounds = (int)((f.tasks + (long)wgs * 8 - 1) / ((long)wgs * 8));
+    return f;
 }
 
-// rg != nullptr: ragged candidate lists -- fp32 only, widths that are one resident slice (pwattn_fwd_uses_rw(D, 0)); p.T = 1 and
-// p.M = N H, so the walk where the dense forward walks, the tile-by-tile form otherwise
-static hipError_t rw_dispatch(const FwdParams& p, int mma, const RaggedTabs* rg, hipStream_t st, bool hrag = false) {
-    const RwPlan pl = pwattn_rw_plan(p.D, mma);
-    if (rg && pl.nsplit != 1) return hipErrorInvalidValue;
-    const bool walk = !rg && fwd_walk_enabled();
-    const bool walkable = hrag || (p.M % ((long)p.T * p.H) == 0 && (long)p.T * p.H * p.D * 4 < (1L << 31));
-    // fp32: the walk for the widths that are one resident slice of whole 16-column tiles
-    if (mma == 0 && pl.nsplit == 1 && p.D == pl.nts * 16 && walkable) {
-        const int nts = walk_f32_nts(p.D);
-        if (nts == 4) return launch_walk_f32<4>(p, pl, rg, st, hrag);
-        if (nts == 8) return launch_walk_f32<8>(p, pl, rg, st, hrag);
-    }
-    if (walk && mma != 0 && walkable) {
-        if (p.D == 256 && pl.nts == 8) return launch_walk<8, 8>(p, pl, mma, st);
-        if (p.D == 128 && pl.nts == 8) return launch_walk<8, 4>(p, pl, mma, st);
-        if (p.D == 64 && pl.nts == 4) return launch_walk<4, 2>(p, pl, mma, st);
-    }
-    switch (pl.nts) {
-        case 1:  return launch_rw<1>(p, pl, mma, rg, st, hrag);
-        case 2:  return launch_rw<2>(p, pl, mma, rg, st, hrag);
-        case 3:  return launch_rw<3>(p, pl, mma, rg, st, hrag);
-        case 4:  return launch_rw<4>(p, pl, mma, rg, st, hrag);
-        case 5:  return launch_rw<5>(p, pl, mma, rg, st, hrag);
-        case 6:  return launch_rw<6>(p, pl, mma, rg, st, hrag);
-        case 8:  return launch_rw<8>(p, pl, mma, rg, st, hrag);
+hipError_t pwattn_fwd_rw_launch_form(const FwdParams& p, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
+    if (!f.valid) return hipErrorInvalidValue;
+    if (f.tasks <= 0) return hipSuccess;
+    const RwPlan pl = pwattn_rw_plan(p.D, f.mma);
+    if (f.family == FWD_WALK_F32) {
+        if (f.NTS == 4) return launch_walk_f32<4>(p, pl, rg, f, st);
+        if (f.NTS == 8) return launch_walk_f32<8>(p, pl, rg, f, st);
+    } else if (f.family == FWD_WALK_BF16) {
+        if (f.NTS == 8 && f.KCH == 8) return launch_walk<8, 8>(p, pl, f, st);
+        if (f.NTS == 8 && f.KCH == 4) return launch_walk<8, 4>(p, pl, f, st);
+        if (f.NTS == 4 && f.KCH == 2) return launch_walk<4, 2>(p, pl, f, st);
+    } else if (f.family == FWD_RW_TILE) {
+        switch (f.NTS) {
+            case 1:  return launch_rw<1>(p, pl, rg, f, st);
+            case 2:  return launch_rw<2>(p, pl, rg, f, st);
+            case 3:  return launch_rw<3>(p, pl, rg, f, st);
+            case 4:  return launch_rw<4>(p, pl, rg, f, st);
+            case 5:  return launch_rw<5>(p, pl, rg, f, st);
+            case 6:  return launch_rw<6>(p, pl, rg, f, st);
+            case 8:  return launch_rw<8>(p, pl, rg, f, st);
+        }
     }
     return hipErrorInvalidValue;
 }
-
-hipError_t pwattn_fwd_rw_launch(const FwdParams& p, int mma, hipStream_t st) { return rw_dispatch(p, mma, nullptr, st); }
-hipError_t pwattn_fwd_rw_ragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) { return rw_dispatch(p, 0, &rg, st); }
-hipError_t pwattn_fwd_rw_hragged_launch(const FwdParams& p, const RaggedTabs& rg, hipStream_t st) { return rw_dispatch(p, 0, &rg, st, true); }
 
 }  // namespace nrm

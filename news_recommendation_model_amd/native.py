@@ -76,6 +76,7 @@ SIGNATURES = {
     "nrm_history_gather": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp]),
     "nrm_history_tiles": (_c_i, [_c_fp] * 4 + [_c_i] * 4 + [_c_fp, _c_fp]),
     "nrm_pwattn_fwd_hragged": (_c_i, [_c_fp] * 13 + [_c_i] * 8 + [_c_fp]),
+    "nrm_pwattn_fwd_form": (_c_i, [_c_i] * 11 + [ctypes.POINTER(ctypes.c_int)]),
     "nrm_pool_bmm_hragged": (_c_i, [_c_fp] * 7 + [_c_i] * 7 + [_c_fp]),
     "nrm_history_gather_groups": (_c_i, [_c_fp, _c_i, _c_i] + [_c_fp] * 4 + [_c_i] * 4 + [_c_fp, _c_fp]),
     "nrm_pool_bmm_wlast": (_c_i, [_c_fp, _c_l, _c_l, _c_l, _c_fp, _c_i, _c_fp] + [_c_i] * 5 + [ctypes.c_float, _c_i, _c_fp]),
