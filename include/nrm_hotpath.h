@@ -103,6 +103,38 @@ int nrm_pwattn_bwd_form(int T, int H, int D, int pass, int mma, int dz_format);
  * keeps every group on its own).  1: per group, its last step padded -- H % 4 == 0, splits shorter than a super-group, every launch that
  * is not the one-accumulator kernel; 2 for H = 2 mod 4, 4 for odd H.  Depends on B through the groups per split.  -1: bad arguments. */
 int nrm_pwattn_bwd_dw_pack(int B, int T, int H, int D, int mma);
+/* What one launch of the attention backward runs (additive entry point, the ABI version is unchanged): the answer of the host function
+ * the launch itself switches on (bwd_dz_select, bwd_e_plan + bwd_e_select, pwattn_bwd_dp_select, pwattn_bwd_rw_select), without a device
+ * call, a launch or an allocation, with the environment knobs applied as the launches apply them -- NRM_DZ_ROWS, NRM_BH_PIPE,
+ * NRM_DW_DIRECT, NRM_DW_R32, NRM_DW_PACK, NRM_BT_WAVES, NRM_BH_WAVES, NRM_BT_INTERLEAVE, NRM_BT_ORDER, NRM_DP_GRID, NRM_BRW_WAVES and
+ * NRM_BRW_TSPLIT at every call; NRM_BWD_RW and NRM_DZ_NARROW as latched at their first use in the process.
+ *   launch: NRM_BWD_LAUNCH_DZ (nrm_pwattn_bwd_dz; pass and mma are not read), NRM_BWD_LAUNCH_CONTRACT (one launch of
+ *           nrm_pwattn_bwd_contract: pass 1, 2 or 4), NRM_BWD_LAUNCH_DP (nrm_pwattn_bwd_dp_dtdh; pass, mma, dz_format not read),
+ *           NRM_BWD_LAUNCH_RW (nrm_pwattn_bwd_rw_dtdh; pass and dz_format not read).
+ *   cus: compute units of the device the launch would go to; 0: those of the current device, or 256 where there is none.
+ * out[NRM_PWATTN_BWD_PLAN_LEN]; out[0] = valid (0: the launch entry answers with an error for this selection -- the dz slab needs more
+ * than 160 KB of LDS, the dP walk or the resident-W backward does not take the shape) and the fields behind the last one named are 0:
+ *   NRM_BWD_LAUNCH_DZ        [1] family 0 slab (bwd_dz_kernel), 1 full-row (bwd_dz_rows_kernel)   [2] threads per workgroup
+ *                            [3] rows-per-thread class of the full-row form: 1 (up to 3 rows), 2 (4 to 6); 0 slab
+ *                            [4] slab_cols  [5] slabs  [6] hchunk  [7] nhc (history chunks)   (slab form; 0 otherwise)
+ *                            [8] dynamic LDS above 64 KB   [9] the narrowing loop ran   [10] dz_format as asked
+ *   NRM_BWD_LAUNCH_CONTRACT  [1] kernel family as bits 0-1 of nrm_pwattn_bwd_form   [2] wave tile 4 | 5   [3] EXACT   [4] mma
+ *                            [5] dW_p slabs written   [6] a row gradient formed   [7] NRM_DZ_HL4 read   [8] pack (nrm_pwattn_bwd_dw_pack)
+ *                            [9] interleaved walk, [10] block order, as the kernel honours them (the pipelined, the packed and the 32-row
+ *                            kernel walk blocked, the pipelined and the 32-row kernel take order 0)
+ *                            [11] nkw  [12] ndcol  [13] nsplit  [14] gps (groups per split)  [15] groups of the last split
+ *                            [16] live splits (waves) of the last workgroup  [17] G (groups)
+ *   NRM_BWD_LAUNCH_DP        [1] NT  [2] nchunks  [3] kchunks  [4] steps  [5] workgroups  [6] most steps one workgroup walks
+ *                            [7] most (row block, N-chunk) items one workgroup walks
+ *   NRM_BWD_LAUNCH_RW        [1] NG  [2] mma  [3] EXACT  [4] nks (reduction slices)  [5] workgroups  [6] waves per workgroup  [7] tsplit
+ *                            [8] tasks (of one slice)  [9] rounds: trips of the busiest wave's task loop  [10] plain_dh (no dh atomics)
+ * Returns 0, or -1 with nrm_last_error() set ("nrm_pwattn_bwd_plan: ...") for arguments the launch entries refuse by value. */
+#define NRM_PWATTN_BWD_PLAN_LEN 18
+#define NRM_BWD_LAUNCH_DZ 0
+#define NRM_BWD_LAUNCH_CONTRACT 1
+#define NRM_BWD_LAUNCH_DP 2
+#define NRM_BWD_LAUNCH_RW 3
+int nrm_pwattn_bwd_plan(int launch, int B, int T, int H, int D, int pass, int mma, int dz_format, int cus, int* out);
 /* backward, step 2 in the "resident W_p" form (bf16 arithmetics, D <= 256): the same dt / dh as above from ONE contraction
  * dP = dz W_p whose W_p image stays in LDS and whose dz operand (NRM_DZ_HL4) is read exactly once; autograd of
  * models/attention_model.py:81-92 w.r.t. target and history.  nrm_pwattn_bwd_rw_supported: 1 if (D, mma) has this form;

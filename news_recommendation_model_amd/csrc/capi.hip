@@ -338,6 +338,51 @@ int nrm_pwattn_bwd_dw_pack(int B, int T, int H, int D, int mma) {
     return f.family == nrm::BWD_DW_DIRECT ? f.pack : 1;
 }
 
+int nrm_pwattn_bwd_plan(int launch, int B, int T, int H, int D, int pass, int mma, int dz_format, int cus, int* out) {
+    const char* fn = "nrm_pwattn_bwd_plan";
+    if (!out) { fail(NRM_EINVAL, "%s: null pointer", fn); return -1; }
+    if (launch < NRM_BWD_LAUNCH_DZ || launch > NRM_BWD_LAUNCH_RW || cus < 0) { fail(NRM_EINVAL, "%s: launch=%d cus=%d", fn, launch, cus); return -1; }
+    if (check_dims(fn, B, T, H, D)) return -1;
+    if (!cus && (launch == NRM_BWD_LAUNCH_DP || launch == NRM_BWD_LAUNCH_RW)) cus = nrm::device_cus();
+    int v[NRM_PWATTN_BWD_PLAN_LEN] = {};
+    if (launch == NRM_BWD_LAUNCH_DZ) {                                   // the value checks of nrm_pwattn_bwd_dz
+        if (B > 65535 || (dz_format != NRM_DZ_F32 && dz_format != NRM_DZ_HL4)) { fail(NRM_EINVAL, "%s: B=%d dz_format=%d (B <= 65535, NRM_DZ_F32 or NRM_DZ_HL4)", fn, B, dz_format); return -1; }
+        const nrm::BwdDzForm f = nrm::bwd_dz_select(B, T, H, D);
+        const int w[] = {f.valid, f.family, f.threads, f.rows_class, f.slab_cols, f.nslab, f.hchunk, f.nhc, f.big_lds, f.narrowed, dz_format};
+        if (f.valid) for (size_t i = 0; i < sizeof(w) / sizeof(w[0]); ++i) v[i] = w[i];
+    } else if (launch == NRM_BWD_LAUNCH_CONTRACT) {                      // ... of nrm_pwattn_bwd_contract, for one of its launches
+        if (check_mma(fn, mma)) return -1;
+        if ((pass != 1 && pass != 2 && pass != 4) || !bwd_dz_format_ok(pass, mma, dz_format)) { fail(NRM_EINVAL, "%s: pass=%d mma=%d dz_format=%d", fn, pass, mma, dz_format); return -1; }
+        const BwdPass a = bwd_pass(pass, nullptr, nullptr, nullptr, nullptr, D, nullptr, nullptr, nullptr, B, T, H, D, mma, dz_format);
+        const nrm::BwdEForm f = nrm::bwd_e_select(a.p, a.pl, a.with_dw, mma, nrm::bwd_e_knobs());
+        if (f.family != nrm::BWD_E_REFUSED && a.p.G > 0) {
+            const nrm::BwdEWalk wk = nrm::bwd_e_walk(a.p, a.pl, f);
+            const int w[] = {1, f.family, a.pl.DT, f.exact, f.mma, f.with_dw, f.with_dt, f.xhl4, f.family == nrm::BWD_DW_DIRECT ? f.pack : 1,
+                             wk.interleave, wk.order, a.pl.nkw, a.pl.ndcol, a.pl.nsplit, a.pl.gps, wk.last_groups, wk.last_live, a.p.G};
+            for (size_t i = 0; i < sizeof(w) / sizeof(w[0]); ++i) v[i] = w[i];
+        }
+    } else if (launch == NRM_BWD_LAUNCH_DP) {                            // ... of nrm_pwattn_bwd_dp_dtdh
+        if ((long)(63 / H + 2) * T * H * D * 4 >= (1L << 31)) { fail(NRM_EINVAL, "%s: the dz blocks of one row block exceed 2^31 bytes", fn); return -1; }
+        const nrm::BwdDpForm f = nrm::pwattn_bwd_dp_select(B, T, H, D, cus);
+        if (f.valid) {
+            int max_steps, max_items;
+            nrm::pwattn_bwd_dp_extent(f, T, max_steps, max_items);
+            const int w[] = {1, f.pl.NT, f.pl.nchunks, f.pl.kchunks, (int)f.steps, (int)f.grid, max_steps, max_items};
+            for (size_t i = 0; i < sizeof(w) / sizeof(w[0]); ++i) v[i] = w[i];
+        }
+    } else {                                                             // ... of nrm_pwattn_bwd_rw_dtdh
+        if (check_mma(fn, mma)) return -1;
+        if ((long)T * H * D * 4 >= (1L << 31)) { fail(NRM_EINVAL, "%s: one impression's dz block exceeds 2^31 bytes", fn); return -1; }
+        const nrm::BwdRwForm f = nrm::pwattn_bwd_rw_select(B, T, H, D, mma, cus);
+        if (f.valid) {
+            const int w[] = {1, f.NG, f.mma, f.exact, f.nks, f.wgs * f.nks, f.nw, f.tsplit, (int)f.tasks, f.rounds, f.plain_dh};
+            for (size_t i = 0; i < sizeof(w) / sizeof(w[0]); ++i) v[i] = w[i];
+        }
+    }
+    for (int i = 0; i < NRM_PWATTN_BWD_PLAN_LEN; ++i) out[i] = v[i];
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------- dense layers
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 

@@ -111,6 +111,20 @@ struct BwdEForm {
 };
 BwdEForm bwd_e_select(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, const BwdEKnobs& knobs);
 hipError_t bwd_e_launch(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int mma, hipStream_t st);
+// The walk of a selected launch as its kernel honours it: p.interleave and p.order count in the serial and the one-accumulator kernel only
+// (the packed one walks blocked, the pipelined and the 32-row kernel walk blocked in order 0: e_tile / e_groups in pwattn_bwd.hip)
+struct BwdEWalk { int interleave, order, last_groups, last_live; };   // groups of the last split; live splits (waves) of the last workgroup
+BwdEWalk bwd_e_walk(const BwdEParams& p, const BwdEPlan& pl, const BwdEForm& f);
+// What one dz-pass launch runs: chosen by bwd_dz_select (host arithmetic only, no HIP call; NRM_DZ_ROWS read at every call, NRM_DZ_NARROW
+// latched at the first); bwd_dz_launch switches on it and on nothing else
+enum BwdDzFamily { BWD_DZ_SLAB = 0, BWD_DZ_ROWS = 1 };
+struct BwdDzForm {
+    int valid;                                            // 0: the slab needs more LDS than a workgroup has (the launch returns hipErrorInvalidValue)
+    int family, threads, rows_class;                      // BWD_DZ_ROWS: bwd_dz_rows_kernel<threads, rows_class, 3> (rows_class 1: up to 3 rows per thread, 2: 4..6)
+    int slab_cols, nslab, hchunk, nhc;                    // BWD_DZ_SLAB: bwd_dz_kernel's column slabs and history chunks
+    size_t shm; bool big_lds, narrowed;                   // its dynamic LDS; above 64 KB; the narrowing loop ran
+};
+BwdDzForm bwd_dz_select(int B, int T, int H, int D);
 // dz_format: 0 = fp32 dz in place, 1 = NRM_DZ_HL4 (every aligned group of 4 values as 4 bf16 hi + 4 bf16 lo, in place)
 hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,
                          int B, int T, int H, int D, int dz_format, hipStream_t st);
@@ -132,6 +146,15 @@ BwdRwPlan pwattn_bwd_rw_plan(int D, int mma);
 long pwattn_bwd_rw_packed_floats(int D, int mma);
 hipError_t pwattn_bwd_rw_pack_launch(const float* wp, int ldw, int D, int mma, float* packed, hipStream_t st);
 hipError_t pwattn_bwd_rw_launch(const BwdRwParams& p, int mma, hipStream_t st);
+// What one resident-W backward launch runs: chosen by pwattn_bwd_rw_select (host arithmetic only, no HIP call; NRM_BRW_WAVES and
+// NRM_BRW_TSPLIT read at every call); the launch switches on it and on nothing else.  cus: compute units of the device
+struct BwdRwForm {
+    int valid;                                            // 0: this (D, mma) keeps the E-form
+    int NG, mma; bool exact;                              // bwd_dp_rw_kernel<NG, MMA, EXACT>
+    int nks, wgs, nw, tsplit;                             // reduction slices; workgroups per slice (the grid is wgs * nks); waves per workgroup; parts of the candidate walk
+    long tasks; int rounds; bool plain_dh;                // tasks of one slice; trips of the busiest wave's task loop; one task owns its dh rows (no atomics)
+};
+BwdRwForm pwattn_bwd_rw_select(int B, int T, int H, int D, int mma, int cus);
 
 // ---- backward of the bilinear term in fp32, dP walk form (pwattn_bwd_dp.hip): dt and dh from ONE contraction dP = dz W_p with the
 // forward's K-chunk-streaming skeleton; dW_p then comes from the (b,t) pass without its dt epilogue
@@ -152,6 +175,15 @@ BwdDpPlan pwattn_bwd_dp_plan(int D, int H);
 long pwattn_bwd_dp_packed_floats(int D, int H);
 hipError_t pwattn_bwd_dp_pack_launch(const float* wp, int ldw, int D, int H, float* packed, hipStream_t st);
 hipError_t pwattn_bwd_dp_launch(BwdDpParams p, hipStream_t st);
+// What one dP-walk launch runs: chosen by pwattn_bwd_dp_select (host arithmetic only, no HIP call; NRM_DP_GRID read at every call); the
+// launch switches on it and on nothing else.  cus: compute units of the device
+struct BwdDpForm {
+    int valid;                                            // 0: this (D, H) keeps the E-form, or more than 2^31 - 1 steps
+    BwdDpPlan pl; long steps; long grid;                  // bwd_dp_walk_kernel<pl.NT>; (row blocks of 64) x N-chunks x T; workgroups (0: nothing to launch)
+};
+BwdDpForm pwattn_bwd_dp_select(int B, int T, int H, int D, int cus);
+// most steps / most (row block, N-chunk) items one workgroup of the launch walks (the plan query asks; the launch does not)
+void pwattn_bwd_dp_extent(const BwdDpForm& f, int T, int& max_steps, int& max_items);
 
 // Non-zero when the translation unit was compiled with a timing-diagnostic override (scripts/_diag): such a library computes
 // WRONG results by construction; capi.hip ORs these into nrm_build_flags() and native.load refuses a non-zero value.

@@ -354,16 +354,16 @@ static int dz_rows_threads(int B, int T, int H, int D, int& rows) {
     return 0;
 }
 
-hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,
-                         int B, int T, int H, int D, int dz_format, hipStream_t st) {
-    if (B <= 0) return hipSuccess;
+// Which dz kernel a launch takes and its geometry: host arithmetic only (every getenv of the dz pass sits here and in dz_rows_threads)
+BwdDzForm bwd_dz_select(int B, int T, int H, int D) {
+    BwdDzForm f = {};
+    f.valid = 1;
     int rows = 0;
     if (const int threads = dz_rows_threads(B, T, H, D, rows)) {
-        auto kern = threads == 512 ? (rows <= 3 ? bwd_dz_rows_kernel<512, 1, 3> : bwd_dz_rows_kernel<512, 2, 3>)
-                                   : (rows <= 3 ? bwd_dz_rows_kernel<1024, 1, 3> : bwd_dz_rows_kernel<1024, 2, 3>);
-        hipLaunchKernelGGL(kern, dim3(B), dim3(threads), 0, st, z, ds, w2, dw2, db2, du, dv, T, H, D, dz_format);
-        return hipGetLastError();
+        f.family = BWD_DZ_ROWS; f.threads = threads; f.rows_class = rows <= 3 ? 1 : 2;
+        return f;
     }
+    f.family = BWD_DZ_SLAB; f.threads = 256;
     int nslab = (D + 127) / 128;
     int slab_cols = ((D + nslab - 1) / nslab + 3) / 4 * 4;           // equal slabs (D = 400: 4 x 100 columns)
     // Long histories: a candidate's rows fit ONE sweep of the workgroup (the path that requests the next candidate's rows before
@@ -375,21 +375,39 @@ hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2,
         nslab *= 2;
         slab_cols = ((D + nslab - 1) / nslab + 3) / 4 * 4;
         if (slab_cols < 16) slab_cols = 16;
+        f.narrowed = true;
     }
-    const int hchunk = H <= 256 ? H : 256;                           // history rows whose du slab shares the LDS
-    const int nhc = (H + hchunk - 1) / hchunk;
-    const size_t shm = ((size_t)hchunk * (slab_cols / 4) + 2 * 256) * sizeof(f32x4);
-    if (shm > 160 * 1024 || nhc > 65535) return hipErrorInvalidValue;
-    if (shm > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)bwd_dz_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    f.slab_cols = slab_cols;
+    f.nslab = (D + slab_cols - 1) / slab_cols;
+    f.hchunk = H <= 256 ? H : 256;                                   // history rows whose du slab shares the LDS
+    f.nhc = (H + f.hchunk - 1) / f.hchunk;
+    f.shm = ((size_t)f.hchunk * (slab_cols / 4) + 2 * 256) * sizeof(f32x4);
+    f.big_lds = f.shm > 64 * 1024;
+    if (f.shm > 160 * 1024 || f.nhc > 65535) f.valid = 0;
+    return f;
+}
+
+hipError_t bwd_dz_launch(float* z, const float* ds, const float* w2, float* dw2, float* db2, float* du, float* dv,
+                         int B, int T, int H, int D, int dz_format, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    const BwdDzForm f = bwd_dz_select(B, T, H, D);
+    if (!f.valid) return hipErrorInvalidValue;
+    if (f.family == BWD_DZ_ROWS) {
+        auto kern = f.threads == 512 ? (f.rows_class == 1 ? bwd_dz_rows_kernel<512, 1, 3> : bwd_dz_rows_kernel<512, 2, 3>)
+                                     : (f.rows_class == 1 ? bwd_dz_rows_kernel<1024, 1, 3> : bwd_dz_rows_kernel<1024, 2, 3>);
+        hipLaunchKernelGGL(kern, dim3(B), dim3(f.threads), 0, st, z, ds, w2, dw2, db2, du, dv, T, H, D, dz_format);
+        return hipGetLastError();
+    }
+    if (f.big_lds) {
+        hipError_t e = hipFuncSetAttribute((const void*)bwd_dz_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.shm);
         if (e != hipSuccess) return e;
     }
-    if (nhc > 1) {                                                    // dv is summed over the history chunks
+    if (f.nhc > 1) {                                                  // dv is summed over the history chunks
         hipError_t e = hipMemsetAsync(dv, 0, (size_t)B * T * D * sizeof(float), st);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(bwd_dz_kernel, dim3((D + slab_cols - 1) / slab_cols, B, nhc), dim3(256), shm, st, z, ds, w2, dw2, db2, du, dv,
-                       T, H, D, slab_cols, hchunk, dz_format);
+    hipLaunchKernelGGL(bwd_dz_kernel, dim3(f.nslab, B, f.nhc), dim3(256), f.shm, st, z, ds, w2, dw2, db2, du, dv,
+                       T, H, D, f.slab_cols, f.hchunk, dz_format);
     return hipGetLastError();
 }
 
@@ -1429,6 +1447,17 @@ BwdEForm bwd_e_select(const BwdEParams& p, const BwdEPlan& pl, bool with_dw, int
         f.family = BWD_E_PIPE;
     }
     return f;
+}
+
+// The walk as the selected kernel honours it (e_tile<.., HONOUR> / e_groups<HONOUR> of each kernel, above)
+BwdEWalk bwd_e_walk(const BwdEParams& p, const BwdEPlan& pl, const BwdEForm& f) {
+    const bool honours = f.family == BWD_E_SERIAL || f.family == BWD_DW_DIRECT;
+    BwdEWalk w;
+    w.interleave = honours && f.pack == 1 && p.interleave != 0;
+    w.order = honours && p.order == 1;
+    w.last_groups = p.G - (pl.nsplit - 1) * pl.gps;
+    w.last_live = pl.nsplit - (pl.nsplit - 1) / 4 * 4;
+    return w;
 }
 
 // f(tile, EXACT, MMA as integral constants) for the run-time triple: 5x5 tiles exist in fp32 only (bwd_e_plan, bwd_e_select)

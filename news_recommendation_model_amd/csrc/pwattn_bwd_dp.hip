@@ -23,6 +23,7 @@
 //   * work = (row block, N-chunk, candidate) steps in that order, cut into EQUAL contiguous ranges over a grid of four rounds of
 //     workgroups (3 per CU): the tail is a sixteenth of a range, and the LDS ring runs on across steps (the first chunk of
 //     step s + 1 is requested under the last chunk of step s).
+#include <algorithm>
 #include <cstdlib>
 // timing diagnostics only (results are WRONG with any bit set; reported by nrm_build_flags): bit 0 no dz DMA after a step's first
 // chunk, bit 1 no epilogue, bit 2 no W DMA after a step's first chunk
@@ -356,32 +357,55 @@ __global__ __launch_bounds__(256, DP_WPE) void bwd_dp_walk_kernel(const BwdDpPar
 
 int pwattn_bwd_dp_diag_flags() { return NRM_DIAG_DP ? 1024 : 0; }
 
-template <int NT>
-static hipError_t launch_dp(BwdDpParams p, hipStream_t st) {
+// The plan, the steps and the grid of one launch: host arithmetic only (the one getenv of this file)
+BwdDpForm pwattn_bwd_dp_select(int B, int T, int H, int D, int cus) {
+    BwdDpForm f = {};
+    f.pl = pwattn_bwd_dp_plan(D, H);
+    if (!f.pl.NT) return f;
+    const long nrb = ((long)B * H + 63) / 64;
+    f.steps = nrb * f.pl.nchunks * T;
+    if (f.steps > 0x7fffffffL) return f;
+    f.valid = 1;
+    if (f.steps <= 0) return f;                                          // grid == 0: nothing to launch
     // four rounds of workgroups at three per CU (measured at C3, 768 / 1536 / 3072 workgroups: 3.97 / 3.95 / 3.92 ms -- the CUs do not
     // finish equal ranges at the same time); never fewer than 4 steps per workgroup (a range pays one ring start and one dh flush)
-    long grid = 12L * device_cus();
+    long grid = 12L * cus;
     if (const char* e = getenv("NRM_DP_GRID")) { const long v = atol(e); if (v > 0) grid = v; }
-    if (grid > p.steps / 4) grid = p.steps / 4;
+    if (grid > f.steps / 4) grid = f.steps / 4;
     if (grid < 1) grid = 1;
+    f.grid = grid;
+    return f;
+}
+
+// The kernel's own ranges, s_lo = S g / G and s_hi = S (g + 1) / G: the most steps and the most (row block, N-chunk) items -- runs of T
+// steps -- one workgroup walks (for the plan query: the launch does not need them)
+void pwattn_bwd_dp_extent(const BwdDpForm& f, int T, int& max_steps, int& max_items) {
+    max_steps = max_items = 0;
+    for (long g = 0; g < f.grid; ++g) {
+        const long s_lo = f.steps * g / f.grid, s_hi = f.steps * (g + 1) / f.grid;
+        if (s_lo >= s_hi) continue;
+        max_steps = std::max(max_steps, (int)(s_hi - s_lo));
+        max_items = std::max(max_items, (int)((s_hi - 1) / T - s_lo / T + 1));
+    }
+}
+
+template <int NT>
+static hipError_t launch_dp(const BwdDpParams& p, long grid, hipStream_t st) {
     hipLaunchKernelGGL((bwd_dp_walk_kernel<NT>), dim3((unsigned)grid), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 
 hipError_t pwattn_bwd_dp_launch(BwdDpParams p, hipStream_t st) {
-    const BwdDpPlan pl = pwattn_bwd_dp_plan(p.D, p.H);
-    if (!pl.NT) return hipErrorInvalidValue;
-    const long R = (long)p.B * p.H;
-    const long nrb = (R + 63) / 64;
-    p.rows = pl.rows; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
-    p.steps = nrb * pl.nchunks * p.T;
-    if (p.steps <= 0) return hipSuccess;
-    if (p.steps > 0x7fffffffL) return hipErrorInvalidValue;
-    switch (pl.NT) {
-        case 4:  return launch_dp<4>(p, st);
-        case 8:  return launch_dp<8>(p, st);
-        case 12: return launch_dp<12>(p, st);
-        case 13: return launch_dp<13>(p, st);
+    const BwdDpForm f = pwattn_bwd_dp_select(p.B, p.T, p.H, p.D, device_cus());
+    if (!f.valid) return hipErrorInvalidValue;
+    if (f.grid <= 0) return hipSuccess;
+    p.rows = f.pl.rows; p.kchunks = f.pl.kchunks; p.nchunks = f.pl.nchunks;
+    p.steps = f.steps;
+    switch (f.pl.NT) {
+        case 4:  return launch_dp<4>(p, f.grid, st);
+        case 8:  return launch_dp<8>(p, f.grid, st);
+        case 12: return launch_dp<12>(p, f.grid, st);
+        case 13: return launch_dp<13>(p, f.grid, st);
     }
     return hipErrorInvalidValue;
 }

@@ -324,12 +324,21 @@ __global__ __launch_bounds__(BRW_WAVES * 64, BRW_WAVES / 4) void bwd_dp_rw_kerne
 
 int pwattn_bwd_rw_diag_flags() { return NRM_DIAG_BRW ? 512 : 0; }
 
-template <int NG>
-static hipError_t launch_brw(BwdRwParams p, const BwdRwPlan& pl, int mma, hipStream_t st) {
-    const int nht = (p.H + 15) / 16, ngs = pl.rows / (64 * NG);
-    const long base = (long)p.B * nht * ngs;
-    if (base <= 0) return hipSuccess;
-    int wgs = device_cus() / pl.nks;
+// The instantiation, the grid and the cut of the candidate walk of one launch: host arithmetic only (NRM_BRW_WAVES and NRM_BRW_TSPLIT
+// are read here and nowhere else; NRM_BWD_RW is latched in pwattn_bwd_rw_plan)
+BwdRwForm pwattn_bwd_rw_select(int B, int T, int H, int D, int mma, int cus) {
+    BwdRwForm f = {};
+    const BwdRwPlan pl = pwattn_bwd_rw_plan(D, mma);
+    if (!pl.ng) return f;
+    f.valid = 1;
+    f.NG = pl.ng == 1 ? 1 : 2;                                          // two 64-column groups of d per wave task from D = 68 up
+    f.mma = mma == 2 ? 2 : 1;
+    f.exact = D % (32 * BRW_KC) == 0;
+    f.nks = pl.nks;
+    const int nht = (H + 15) / 16, ngs = pl.rows / (64 * f.NG);
+    const long base = (long)B * nht * ngs;
+    if (base <= 0) return f;                                             // tasks == 0: nothing to launch
+    int wgs = cus / pl.nks;
     if (wgs < 1) wgs = 1;
     // the candidate walk is cut into tsplit parts when the tasks would not fill the chip's wave slots twice over (every part adds
     // its dh with float atomics: C2, 2 rounds of tasks: 0.191 ms unsplit, 0.201 ms in two parts), as long as a part keeps >= 8 steps
@@ -338,17 +347,26 @@ static hipError_t launch_brw(BwdRwParams p, const BwdRwPlan& pl, int mma, hipStr
     const long slots = (long)wgs * nw;
     int tsplit = 1;
     if (const char* e = getenv("NRM_BRW_TSPLIT")) tsplit = atoi(e);
-    else while (base * tsplit < 2 * slots && p.T / (tsplit + 1) >= 8) ++tsplit;
+    else while (base * tsplit < 2 * slots && T / (tsplit + 1) >= 8) ++tsplit;
     if (tsplit < 1) tsplit = 1;
-    if (tsplit > p.T) tsplit = p.T;
-    p.tsplit = tsplit;
+    if (tsplit > T) tsplit = T;
     const long ntask = base * tsplit;
     if ((long)wgs * nw > ntask) wgs = (int)((ntask + nw - 1) / nw);
+    f.wgs = wgs; f.nw = nw; f.tsplit = tsplit; f.tasks = ntask;
+    f.rounds = (int)((ntask + (long)wgs * nw - 1) / ((long)wgs * nw));
+    f.plain_dh = pl.nks == 1 && tsplit == 1;                            // (as the kernel decides it)
+    return f;
+}
+
+template <int NG>
+static hipError_t launch_brw(BwdRwParams p, const BwdRwPlan& pl, const BwdRwForm& f, hipStream_t st) {
+    const int mma = f.mma, wgs = f.wgs, nw = f.nw;
+    p.tsplit = f.tsplit;
     const size_t shm = (size_t)pl.kc * pl.wimg * pl.rows * 64 + (size_t)BRW_WAVES * 1024;     // image + per-wave bounce
     const dim3 grid((unsigned)(wgs * pl.nks)), block(nw * 64);
 #define NRM_BRW(M_)                                                                                                          \
     {                                                                                                                        \
-        auto k = (p.D % (32 * BRW_KC) == 0) ? bwd_dp_rw_kernel<NG, M_, true> : bwd_dp_rw_kernel<NG, M_, false>;                         \
+        auto k = f.exact ? bwd_dp_rw_kernel<NG, M_, true> : bwd_dp_rw_kernel<NG, M_, false>;                                    \
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BRW_LDS_BUDGET); \
         if (e != hipSuccess) return e;                                                                                       \
         hipLaunchKernelGGL(k, grid, block, shm, st, p, pl, wgs);                                                             \
@@ -359,10 +377,12 @@ static hipError_t launch_brw(BwdRwParams p, const BwdRwPlan& pl, int mma, hipStr
 }
 
 hipError_t pwattn_bwd_rw_launch(const BwdRwParams& p, int mma, hipStream_t st) {
-    const BwdRwPlan pl = pwattn_bwd_rw_plan(p.D, mma);
-    if (!pl.ng) return hipErrorInvalidValue;
-    if (pl.ng == 1) return launch_brw<1>(p, pl, mma, st);
-    return launch_brw<2>(p, pl, mma, st);                               // two 64-column groups of d per wave task
+    const BwdRwForm f = pwattn_bwd_rw_select(p.B, p.T, p.H, p.D, mma, device_cus());
+    if (!f.valid) return hipErrorInvalidValue;
+    if (f.tasks <= 0) return hipSuccess;
+    const BwdRwPlan pl = pwattn_bwd_rw_plan(p.D, mma);                  // the image's geometry (kernel argument)
+    if (f.NG == 1) return launch_brw<1>(p, pl, f, st);
+    return launch_brw<2>(p, pl, f, st);                                 // two 64-column groups of d per wave task
 }
 
 }  // namespace nrm

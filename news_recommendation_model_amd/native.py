@@ -39,6 +39,7 @@ SIGNATURES = {
     "nrm_pwattn_bwd_contract": (_c_i, [_c_fp] * 4 + [_c_i] + [_c_fp] * 3 + [_c_i] * 7 + [_c_fp]),
     "nrm_pwattn_bwd_form": (_c_i, [_c_i] * 6),
     "nrm_pwattn_bwd_dw_pack": (_c_i, [_c_i] * 5),
+    "nrm_pwattn_bwd_plan": (_c_i, [_c_i] * 9 + [ctypes.POINTER(ctypes.c_int)]),
     "nrm_gemm_packed_floats": (_c_l, [_c_i, _c_i, _c_i]),
     "nrm_gemm_nt_bf16_supported": (_c_i, [_c_i, _c_i, _c_i]),
     "nrm_gemm_nt_form": (_c_i, [_c_i, _c_i, _c_i, _c_i]),

@@ -586,32 +586,58 @@ def test_random_shapes_match_oracle(lib, B, T, H, D):
 # The dt/dW pass has two group walks (csrc/capi.hip): blocked (every wave its own run of groups) and interleaved (the four
 # waves of a workgroup share one run round-robin; default for groups above 256 KB, i.e. C5).  Both must give the same
 # gradients for any number of groups / splits, including a last workgroup with fewer than four active waves.
+# Under the default plan a launch of few groups gets one group per wave, where the two walks are the same walk: every shape with
+# enough groups therefore runs a second time under a plan forced with NRM_BT_WAVES to at least three groups per split and a split
+# count that is no multiple of 4 (attention_bwd_forms_util.interleave_waves asks nrm_pwattn_bwd_plan), asserted through the query.
+# The last four shapes are there for that plan: 9 groups in 3 splits; 21 in 7 on 5x5 tiles; H = 33 (the bf16 arithmetics on the
+# serial hl4 kernel, which honours the walk; at H <= 32 their 32-row kernel always walks blocked); D = 320 (their dt pass).
+INTERLEAVED_SHAPES = [(2, 30, 50, 400), (3, 7, 19, 72), (5, 1, 3, 64), (1, 4, 9, 420), (7, 5, 37, 100), (1, 1, 1, 64), (2, 3, 130, 768),
+                      (3, 3, 5, 64), (3, 7, 5, 80), (3, 7, 33, 100), (3, 7, 5, 320)]
+INTERLEAVED_FORCED = INTERLEAVED_SHAPES[:3] + INTERLEAVED_SHAPES[4:5] + INTERLEAVED_SHAPES[7:]      # the others have fewer than 5 groups
+
+
 @pytest.mark.parametrize("mma", ["f32", "bf16x3"])
-@pytest.mark.parametrize("B,T,H,D", [(2, 30, 50, 400), (3, 7, 19, 72), (5, 1, 3, 64), (1, 4, 9, 420), (7, 5, 37, 100),
-                                     (1, 1, 1, 64), (2, 3, 130, 768)])
+@pytest.mark.parametrize("B,T,H,D", INTERLEAVED_SHAPES)
 def test_interleaved_group_walk_matches_oracle(lib, monkeypatch, mma, B, T, H, D):
+    import attention_bwd_forms_util as abu
     rng = np.random.default_rng(B * 1000 + T * 100 + H * 10 + D + 1)
     w = _weights(rng, D)
     tgt = rng.standard_normal((B, T, D)).astype(np.float32)
     his = rng.standard_normal((B, H, D)).astype(np.float32)
     gs = rng.standard_normal((B, T, H)).astype(np.float32)
-    out = {}
-    for walk in ("0", "1"):
-        monkeypatch.setenv("NRM_BT_INTERLEAVE", walk)
-        s, got, s_ref, ref = _run_both(w, tgt, his, gs, mma=mma)
-        assert rel_err(s, s_ref) < FWD_TOL
-        for k in ref:
-            assert rel_err(got[k], ref[k]) < GRAD_TOL, (walk, k, rel_err(got[k], ref[k]))
-        out[walk] = got
-    # the two walks differ only in the order in which float atomics and slab sums meet
-    for k in out["0"]:
-        assert rel_err(out["1"][k], out["0"][k]) < 1e-4, k
-    # ... and so does the k-range-major block order of the pass (NRM_BT_ORDER=1: a measured no-go for C5's over-fetch, kept as a
-    # tuning knob -- which workgroup owns which tile must not matter)
-    monkeypatch.setenv("NRM_BT_ORDER", "1")
-    _, got, _, _ = _run_both(w, tgt, his, gs, mma=mma)
-    for k in out["0"]:
-        assert rel_err(got[k], out["1"][k]) < 1e-4, k
+    for k in abu.PER_LAUNCH:
+        monkeypatch.delenv(k, raising=False)
+    plans = [None]
+    if (B, T, H, D) in INTERLEAVED_FORCED:
+        waves = abu.interleave_waves(lib, (B, T, H, D), abu.MMA_BY_NAME[mma])
+        assert waves is not None, "no NRM_BT_WAVES gives this shape several groups per split"
+        plans.append(waves)
+    for waves in plans:
+        if waves is not None:
+            monkeypatch.setenv("NRM_BT_WAVES", waves)
+            monkeypatch.setenv("NRM_BWD_DP", "0")
+        out = {}
+        for walk in ("0", "1"):
+            monkeypatch.setenv("NRM_BT_INTERLEAVE", walk)
+            if waves is not None:                                        # the launch below walks several groups per wave, in this walk
+                f = [f for f in abu.launches(lib, (B, T, H, D), abu.MMA_BY_NAME[mma]) if f["launch"] == abu.CONTRACT and f["pass"] != 2][0]
+                assert f["gps"] > 1 and (f["gps"] >= 3 and f["nsplit"] % 4 != 0 or B * T < 9), f
+                assert f["interleave"] == int(walk) or f["family"] == "dw_r32", f
+            s, got, s_ref, ref = _run_both(w, tgt, his, gs, mma=mma)
+            assert rel_err(s, s_ref) < FWD_TOL
+            for k in ref:
+                assert rel_err(got[k], ref[k]) < GRAD_TOL, (waves, walk, k, rel_err(got[k], ref[k]))
+            out[walk] = got
+        # the two walks differ only in the order in which float atomics and slab sums meet
+        for k in out["0"]:
+            assert rel_err(out["1"][k], out["0"][k]) < 1e-4, (waves, k)
+        # ... and so does the k-range-major block order of the pass (NRM_BT_ORDER=1: a measured no-go for C5's over-fetch, kept as a
+        # tuning knob -- which workgroup owns which tile must not matter)
+        monkeypatch.setenv("NRM_BT_ORDER", "1")
+        _, got, _, _ = _run_both(w, tgt, his, gs, mma=mma)
+        for k in out["0"]:
+            assert rel_err(got[k], out["1"][k]) < 1e-4, (waves, k)
+        monkeypatch.delenv("NRM_BT_ORDER")
 
 
 def test_full_size_c5_properties(lib):
