@@ -6,6 +6,7 @@ launch), host float64 batches staged one ahead, per-impression AUC on the device
     python examples/train_synthetic.py --workload C1-demo --batches 20 --epochs 2
     python examples/train_synthetic.py --workload ref-default --compact-history --history-lengths uniform      
     python examples/train_synthetic.py --workload ref-default --compact-candidates --candidate-counts percentile    (section 5f)
+    python examples/train_synthetic.py --workload ref-default --from-tables --compact-history --compact-candidates    (section 5g)
 """
 import argparse
 import os
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from news_recommendation_model_amd import data_io, evaluation, synth, trainer  # noqa: E402
+from news_recommendation_model_amd import data_io, evaluation, synth, tables, trainer  # noqa: E402
 from news_recommendation_model_amd.config import Dims, WORKLOADS               # noqa: E402
 sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from compact_util import pad_batch, percentile_counts                          # noqa: E402  (the count distribution the tests use)
@@ -39,12 +40,17 @@ def main():
     ap.add_argument("--candidate-counts", default="full", choices=["full", "percentile"],
                     help="pad the synthetic candidate lists the way the ETL does: all-zero rows past a list's own candidates, label 0 (percentile: "
                          "list lengths drawn from the percentiles the reference records, 70 %% of the lists at most 12 candidates)")
+    ap.add_argument("--from-tables", action="store_true",
+                    help="keep the data set on the device as index-based tables (raw synthetic records through tables.ImpressionTables) and write "
+                         "every batch there with the assemble kernel (trainer.train_epochs_tables) instead of uploading processed records")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
     wl = WORKLOADS[args.workload]
     B = args.batch or wl["B"]
     dims = Dims.for_emb(wl["emb"])
+    if args.from_tables:
+        return main_from_tables(args, wl, B, dims)
     user_num = 10 * B
     torch.manual_seed(args.seed)                                           # train.py:42-43
     model = trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=args.seed + 1, user_num=user_num))
@@ -86,6 +92,34 @@ def main():
     # the batch statistics and the eval-mode AUC can fall back to chance although the train-mode AUC keeps rising -- the
     # reference model behaves the same way (oracle/user_model_oracle.py reproduces it on the CPU)
     print(f"validation (eval mode) on 4 training batches: auc={auc:.4f} top1={hit:.4f}  checkpoints in {ckpt_dir}")
+
+
+def main_from_tables(args, wl, B, dims):
+    """The same driver with the data resident on the device: raw records -> tables (once) -> one assemble launch per step."""
+    rng = np.random.default_rng(args.seed)
+    n = args.batches * B
+    n_users = max(n // 4, 8)
+    recs = synth.make_records(dims, 4096, n_users, n, seed=args.seed, history_lens=rng.integers(0, wl["H"] + 20, n_users),
+                              list_lens=np.clip(rng.geometric(1.0 / (0.7 * wl["T"]), n), 2, 3 * wl["T"]))
+    host = tables.ImpressionTables.from_records(*recs, dims, history_max=wl["H"])
+    dev = host.to("cuda")
+    user_num = host.max_user_id + 1
+    torch.manual_seed(args.seed)
+    model = trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=args.seed + 1, user_num=user_num))
+    opt = trainer.FlatAdam(model, lr=args.lr)
+    ckpt_dir = args.ckpt_dir or tempfile.mkdtemp(prefix="nrm_ckpt_")
+    print(f"{host.n_impressions} impressions, {host.nbytes / 1e6:.1f} MB of tables on the device; a step uploads {8 * B} bytes of indices "
+          f"instead of {B * (wl['H'] * dims.history_cols + wl['T'] * (dims.target_cols + 4)) * 8 / 1e6:.1f} MB of float64 rows")
+    hist = trainer.train_epochs_tables(model, opt, dev, args.epochs, B, wl["H"], wl["T"], seed=args.seed, drop_last=True,
+                                       ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"),
+                                       compact_history=args.compact_history, compact_candidates=args.compact_candidates)
+    for rec in hist:
+        print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec))
+    fresh = trainer.build_model(dims, user_num)
+    evaluation.load_checkpoint(fresh, os.path.join(ckpt_dir, f"ckpt_synthetic_epoch_{args.epochs - 1}.pth"))
+    batches = (b for i, b in enumerate(tables.TableLoader(dev, B, wl["H"], wl["T"], shuffle=False, drop_last=True)) if i < 4)
+    auc, hit = evaluation.validate([fresh], batches)
+    print(f"validation (eval mode) on 4 assembled batches: auc={auc:.4f} top1={hit:.4f}  checkpoints in {ckpt_dir}")
 
 
 if __name__ == "__main__":

@@ -548,6 +548,45 @@ int nrm_loss_fwd_bwd_wlast(const float* out, int out_stride, const void* label, 
                            long n_delta, float alpha, int B, int T, float wlast, float inv_n, float* loss_sum, float* dout, int dout_stride,
                            float* ddelta, int* err, nrm_stream_t stream);
 
+/* ---- batch assembly from device-resident tables (additive entry point, the ABI version is unchanged)
+ * Writes the processed record of reference tool/process_data.py:190-252 (process_dataset's loop body, batch_type 0 and 2) for the B
+ * impressions sel[0 .. B) straight from index-based tables, instead of reading it from the host:
+ *   x_history [B, H, hc]  row j < min(events of the user, H): [year, month, day, hour of (impression time - event time) | the article's
+ *                         static row | read time, scroll]; the rows behind are +0.0          hc = 4 + static_cols + 2
+ *   x_target  [B, T, tc]  slot s: [buckets of (impression time - publish time) | static row]   tc = 4 + static_cols
+ *   x_global  [B, T, 3]   the article's three normalised counters
+ *   label [B, T] float64 (1 where the slot holds the target), label_id [B, T] int64 (the article's id, -1 on an empty slot),
+ *   empty_num [B] = empty slots, user_id [B], impression_id [B], history_len [B] int32 = min(events of the user, H)
+ * Slots: 0 .. T-2 are the first T-1 in-view entries.  With NRM_ASSEMBLE_KEEP_TARGET_SLOT (batch_type 0) slot T-1 is in-view entry T-1 if
+ * one of the first T-1 is the target, else the first entry at position >= T-1 that is the target, else empty; without the flag
+ * (batch_type 2) it is entry T-1.  Empty slots are +0.0 rows with label 0.
+ * Time buckets (tool/normalization.py sec_norm): sec = max(0, delta_us / 1e6) in float64, then for (365 d, 3000), (30 d, 12), (1 d, 30),
+ * (1 h, 23): k = min(int(sec / standard), cap), sec -= standard * k -- float64 arithmetic, once per row.
+ * Tables (device): art_static [A, S] rows of S = static_cols rounded up to a multiple of 4 elements, tail zero, 16-byte aligned and below
+ * 2^32 bytes; art_global [A, 3]; the floating tables (art_static, art_global, ev_read, ev_scroll) are all float64 (is_f64 != 0) or all
+ * float32 and the three x outputs have their type.  user_off [U + 1], imp_off [N + 1] are prefix sums; events of a user lie most recent
+ * first.  ev_art, imp_inview, imp_target (-1 = none) index art_*; imp_user indexes user_*.
+ * Every table entry is clamped to its array; an entry of sel outside [0, N) is clamped and sets err[0] = 1 (the index flag of
+ * nrm_frontend_fwd).  One wave writes 16 rows of one impression in 16-byte units where hc % 4 == 0 (candidate rows, which start 8 bytes
+ * off in float32, in 8-byte units) and element by element otherwise; no atomics, the output is the same bit for bit from run to run.
+ * B = 0 launches nothing.  H * hc and T * tc elements of one impression stay below 2^31 bytes. */
+typedef struct nrm_assemble_tables {
+    const void* art_static; const void* art_global; const long* art_pub_us; const long* art_id;
+    const long* user_off; const int* ev_art; const long* ev_time_us; const void* ev_read; const void* ev_scroll; const long* user_id;
+    const int* imp_user; const long* imp_time_us; const long* imp_off; const int* imp_inview; const int* imp_target; const long* imp_id;
+    long A, U, E, N, L;              /* articles, users, events, impressions, in-view entries */
+    int S, static_cols, is_f64;
+    /* outputs */
+    void* x_history; void* x_target; void* x_global; double* label; long* label_id; long* empty_num; long* user_id_out;
+    long* impression_id; int* history_len;
+    int* err;
+} nrm_assemble_tables;
+#define NRM_ASSEMBLE_KEEP_TARGET_SLOT 1
+int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B, int H, int T, int flags, nrm_stream_t stream);
+/* the form nrm_assemble_batch writes rows in (the answer of the host function the launch switches on, no device call):
+ * 4 = 16-byte units (8-byte units for float32 candidate rows), 1 = element by element; -1: bad arguments */
+int nrm_assemble_form(int static_cols, int S);
+
 #ifdef __cplusplus
 }
 #endif

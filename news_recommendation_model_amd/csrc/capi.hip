@@ -14,6 +14,7 @@
 #include "frontend.hpp"
 #include "scoring.hpp"
 #include "compact.hpp"
+#include "assemble.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -1003,6 +1004,35 @@ int nrm_frontend_cat_grad(const void* x0, int nrows0, int xcols0, const float* d
     if (((long)nrows0 + nrows1) * (n_sub + 1) >= (1L << 31)) return fail(NRM_EINVAL, "nrm_frontend_cat_grad: more than 2^31 table references");
     return check_hip(nrm::cat_grad_launch(x0, nrows0, xcols0, dlab0, lddl0, x1, nrows1, xcols1, dlab1, lddl1, x_is_f64, P, n_sub, n_cat, e0,
                                           d_cat_tab, ws, (hipStream_t)stream), "frontend_cat_grad");
+}
+
+int nrm_assemble_form(int static_cols, int S) { return nrm::assemble_form(static_cols, S); }
+
+int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B, int H, int T, int flags, nrm_stream_t stream) {
+    if (!tables) return fail(NRM_EINVAL, "nrm_assemble_batch: null table struct");
+    const nrm_assemble_tables& t = *tables;
+    if (B < 0 || H <= 0 || T <= 0 || (flags & ~NRM_ASSEMBLE_KEEP_TARGET_SLOT))
+        return fail(NRM_EINVAL, "nrm_assemble_batch: B=%d H=%d T=%d flags=%d (B >= 0, H, T > 0, flags 0 or NRM_ASSEMBLE_KEEP_TARGET_SLOT)", B, H, T, flags);
+    if (B == 0) return NRM_OK;
+    const long sz = t.is_f64 ? 8 : 4;
+    if (t.A < 1 || t.A >= (1L << 31) || t.U < 1 || t.U >= (1L << 31) || t.N < 1 || t.E < 0 || t.L < 0)
+        return fail(NRM_EINVAL, "nrm_assemble_batch: A=%ld U=%ld E=%ld N=%ld L=%ld (1 <= A, U < 2^31, N >= 1, E, L >= 0)", t.A, t.U, t.E, t.N, t.L);
+    if (t.static_cols < 1 || t.S != (t.static_cols + 3) / 4 * 4 || t.A * t.S * sz >= (1L << 32))
+        return fail(NRM_EINVAL, "nrm_assemble_batch: static_cols=%d S=%d A=%ld (S = static_cols rounded up to a multiple of 4; art_static below 2^32 bytes)",
+                    t.static_cols, t.S, t.A);
+    const long hc = 4 + t.static_cols + 2, tc = 4 + t.static_cols;
+    if ((long)H * hc * sz >= (1L << 31) || (long)T * tc * sz >= (1L << 31) || (long)B * T >= (1L << 31))
+        return fail(NRM_EINVAL, "nrm_assemble_batch: H=%d T=%d B=%d: the rows of one impression exceed 2^31 bytes (or B*T >= 2^31)", H, T, B);
+    if (!sel || !t.art_static || !t.art_global || !t.art_pub_us || !t.art_id || !t.user_off || !t.user_id || !t.imp_user || !t.imp_time_us ||
+        !t.imp_off || !t.imp_target || !t.imp_id || (t.E > 0 && (!t.ev_art || !t.ev_time_us || !t.ev_read || !t.ev_scroll)) || (t.L > 0 && !t.imp_inview) ||
+        !t.x_history || !t.x_target || !t.x_global || !t.label || !t.label_id || !t.empty_num || !t.user_id_out || !t.impression_id ||
+        !t.history_len || !t.err)
+        return fail(NRM_EINVAL, "nrm_assemble_batch: null pointer");
+    if (((uintptr_t)t.art_static | (uintptr_t)t.x_history | (uintptr_t)t.x_target) & 15)
+        return fail(NRM_EINVAL, "nrm_assemble_batch: art_static, x_history and x_target must be 16-byte aligned");
+    nrm::AssembleParams p;
+    p.t = t; p.sel = sel; p.B = B; p.H = H; p.T = T; p.keep_target_slot = (flags & NRM_ASSEMBLE_KEEP_TARGET_SLOT) ? 1 : 0;
+    return check_hip(nrm::assemble_launch(p, (hipStream_t)stream), "assemble_batch");
 }
 
 }  // extern "C"

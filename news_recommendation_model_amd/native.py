@@ -88,6 +88,8 @@ SIGNATURES = {
     "nrm_loss_fwd_bwd_wlast": (_c_i, [_c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp, _c_l, ctypes.c_float, _c_i, _c_i, ctypes.c_float, ctypes.c_float,
                                       _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp]),
     "nrm_ensemble_rank_ragged": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i] + [_c_fp] * 5),     # the first two: HOST arrays
+    "nrm_assemble_batch": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),       # the first: a HOST struct (AssembleTables), by pointer
+    "nrm_assemble_form": (_c_i, [_c_i, _c_i]),
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,
                                  _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp]),
@@ -115,6 +117,16 @@ class SlabDesc(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("out_istride", ctypes.c_long), ("out_jstride", ctypes.c_long),
                 ("out2", ctypes.c_void_p), ("out2_istride", ctypes.c_long), ("out2_jstride", ctypes.c_long), ("sign2", ctypes.c_float),
                 ("vec", ctypes.c_void_p), ("vec_out", ctypes.c_void_p)]
+
+
+class AssembleTables(ctypes.Structure):
+    """nrm_assemble_tables of include/nrm_hotpath.h"""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("art_static", "art_global", "art_pub_us", "art_id", "user_off", "ev_art", "ev_time_us", "ev_read",
+                                                "ev_scroll", "user_id", "imp_user", "imp_time_us", "imp_off", "imp_inview", "imp_target", "imp_id")]
+                + [(n, ctypes.c_long) for n in ("A", "U", "E", "N", "L")]
+                + [(n, ctypes.c_int) for n in ("S", "static_cols", "is_f64")]
+                + [(n, ctypes.c_void_p) for n in ("x_history", "x_target", "x_global", "label", "label_id", "empty_num", "user_id_out",
+                                                  "impression_id", "history_len", "err")])
 
 
 _lib = None

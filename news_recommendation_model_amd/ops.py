@@ -2675,6 +2675,73 @@ history_len = _op("history_len", "(Tensor x_history) -> Tensor", _history_len_im
                   lambda x: x.new_empty((x.shape[0],), dtype=torch.int32))
 
 
+# ---- batch assembly from device-resident tables (tables.ImpressionTables, tables.TABLE_FIELDS gives the order)
+_ASSEMBLE_DTYPES = (None, None, torch.int64, torch.int64, torch.int64, torch.int32, torch.int64, None, None, torch.int64,
+                    torch.int32, torch.int64, torch.int64, torch.int32, torch.int32, torch.int64)       # None: the tables' floating type
+
+
+def _assemble_shapes(tables, sel, H, T, static_cols):
+    if len(tables) != len(_ASSEMBLE_DTYPES):
+        raise RuntimeError(f"assemble_batch: {len(tables)} tables, expected {len(_ASSEMBLE_DTYPES)} (tables.TABLE_FIELDS)")
+    ft = tables[0].dtype
+    if ft not in (torch.float32, torch.float64):
+        raise RuntimeError(f"assemble_batch: art_static is {ft}; the floating tables are float32 or float64")
+    for i, (t, want) in enumerate(zip(tables, _ASSEMBLE_DTYPES)):
+        if t.dtype != (want or ft) or not t.is_contiguous():
+            raise RuntimeError(f"assemble_batch: table {i} is {t.dtype}{'' if t.is_contiguous() else ' (not contiguous)'}, expected a contiguous "
+                               f"{want or ft} tensor (tables.TABLE_FIELDS)")
+    if sel.dim() != 1 or sel.dtype != torch.int64 or H < 1 or T < 1 or static_cols < 1:
+        raise RuntimeError(f"assemble_batch: sel {tuple(sel.shape)} {sel.dtype}, H={H}, T={T}, static_cols={static_cols} (sel is a 1-D int64 "
+                           "tensor; H, T, static_cols >= 1)")
+    return ft, sel.shape[0], 4 + static_cols + 2, 4 + static_cols
+
+
+def _assemble_outputs(like, ft, B, H, T, hc, tc):
+    new = lambda shape, dt: like.new_empty(shape, dtype=dt)      # noqa: E731
+    return (new((B, H, hc), ft), new((B, T, tc), ft), new((B, T, 3), ft), new((B, T), torch.float64), new((B, T), torch.int64),
+            new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int32))
+
+
+def _assemble_batch_impl(tables, sel, H, T, keep_target_slot, static_cols):
+    """The processed records of the impressions ``sel`` written from device-resident tables by ONE kernel -> (x_history [B, H, hc],
+    x_target [B, T, tc], x_global [B, T, 3] in the tables' floating type, label [B, T] float64, label_id [B, T], empty_num [B], user_id [B],
+    impression_id [B] int64, history_len [B] int32): reference tool/process_data.py:190-252 (batch_type 0 with ``keep_target_slot``, else 2)."""
+    _require_gpu(*tables, sel)
+    ft, B, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
+    outs = _assemble_outputs(sel, ft, B, H, T, hc, tc)
+    if B == 0:
+        return outs
+    (art_static, art_global, art_pub, art_id, user_off, ev_art, ev_time, ev_read, ev_scroll, user_id, imp_user, imp_time, imp_off, imp_inview,
+     imp_target, imp_id) = tables
+    A, U, E, N, L = art_static.shape[0], user_id.shape[0], ev_art.shape[0], imp_user.shape[0], imp_inview.shape[0]
+    if (art_static.dim() != 2 or tuple(art_global.shape) != (A, 3) or tuple(art_pub.shape) != (A,) or tuple(art_id.shape) != (A,)
+            or tuple(user_off.shape) != (U + 1,) or any(tuple(t.shape) != (E,) for t in (ev_time, ev_read, ev_scroll))
+            or any(tuple(t.shape) != (N,) for t in (imp_time, imp_target, imp_id)) or tuple(imp_off.shape) != (N + 1,)):
+        raise RuntimeError("assemble_batch: the tables do not agree in their sizes (tables.ImpressionTables.validate)")
+    d = native.AssembleTables()
+    for name, t in zip(("art_static", "art_global", "art_pub_us", "art_id", "user_off", "ev_art", "ev_time_us", "ev_read", "ev_scroll", "user_id",
+                        "imp_user", "imp_time_us", "imp_off", "imp_inview", "imp_target", "imp_id"), tables):
+        setattr(d, name, t.data_ptr())
+    d.A, d.U, d.E, d.N, d.L = A, U, E, N, L
+    d.S, d.static_cols, d.is_f64 = art_static.shape[1], static_cols, 1 if ft == torch.float64 else 0
+    for name, t in zip(("x_history", "x_target", "x_global", "label", "label_id", "empty_num", "user_id_out", "impression_id", "history_len"), outs):
+        setattr(d, name, t.data_ptr())
+    d.err = index_error_flag(sel.device).data_ptr()
+    import ctypes
+    native.call("nrm_assemble_batch", ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), native.ptr(sel.contiguous()), B, int(H), int(T),
+                1 if keep_target_slot else 0, native.stream_ptr())
+    return outs
+
+
+def _assemble_batch_fake(tables, sel, H, T, keep_target_slot, static_cols):
+    ft, B, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
+    return _assemble_outputs(sel, ft, B, H, T, hc, tc)
+
+
+assemble_batch = _op("assemble_batch", "(Tensor[] tables, Tensor sel, int H, int T, bool keep_target_slot, int static_cols) -> "
+                     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _assemble_batch_impl, _assemble_batch_fake)
+
+
 def _history_gather_impl(x_history, hist_off, R, k_max):
     """x_history [B, H, cols] -> [R, cols] (bitwise, dtype kept): row j < K_b of impression b goes to row hist_off[b] + j.  One launch."""
     _require_gpu(x_history, hist_off)
@@ -2823,4 +2890,4 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
        "candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
        "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
-       "adam_step")
+       "assemble_batch", "adam_step")

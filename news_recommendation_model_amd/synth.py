@@ -72,6 +72,77 @@ def make_batch(dims: Dims, B: int, H: int, T: int, seed: int = 0, user_num: int 
     }
 
 
+def make_records(dims: Dims, n_articles: int, n_users: int, n_impressions: int, seed: int = 0, history_lens=None, list_lens=None,
+                 labelled: bool = True, absent_target_frac: float = 0.0, multi_click_frac: float = 0.0, nan_frac: float = 0.05,
+                 max_history: int = 250, max_list: int = 40):
+    """Seeded RAW records -- what ``tables.ImpressionTables.from_records`` takes: (articles, histories, behaviors), dicts of per-record
+    columns shaped like the EBNeRD parquet columns the reference ETL reads (tool/process_data.py:294-447), with the text+image vector of an
+    article given as ``text_img`` [A, P].  ``make_batch`` is untouched by this function.
+
+    ``history_lens`` / ``list_lens``: the events per user [n_users] and the in-view entries per impression [n_impressions] (arrays; None:
+    drawn from 0 .. ``max_history`` with every tenth user empty, and from 1 .. ``max_list``) -- users with no event and lists longer
+    than any T are part of the default.  Histories are stored oldest first, as the data set has them.  With ``labelled`` every impression
+    has ``article_ids_clicked``: one entry of its list, or (``absent_target_frac``) an article that is not in the list, or
+    (``multi_click_frac``) two clicks -- such impressions are dropped by the builder.  ``nan_frac`` of the counters, read times and scroll
+    values are NaN.  Categories are >= 1, so a written row always holds a non-zero bit."""
+    from .config import model_config
+    rng = np.random.default_rng(seed)
+    base = 1_684_000_000_000_000                                        # microseconds since the epoch
+    day = 86_400_000_000
+    A, P = n_articles, dims.pca_vector
+
+    def with_nan(x):
+        x = np.asarray(x, dtype=np.float64)
+        x[rng.random(x.shape) < nan_frac] = np.nan
+        return x
+    sent_keys, type_keys = list(model_config["sentiment_label_dict"]), list(model_config["article_type_dict"])
+    articles = {
+        "article_id": (9_000_000 + rng.permutation(4 * A)[:A]).astype(np.int64),
+        "text_img": rng.standard_normal((A, P)),
+        "category": rng.integers(1, dims.category_label_num, A),
+        "subcategory": [rng.integers(1, dims.category_label_num, int(k)).tolist() for k in rng.integers(0, dims.n_subcat + 3, A)],
+        "sentiment_score": rng.random(A),
+        "sentiment_label": [sent_keys[int(k)] for k in rng.integers(0, len(sent_keys), A)],
+        "article_type": [type_keys[int(k)] for k in rng.integers(0, len(type_keys), A)],
+        "published_time_us": (base - rng.integers(-2 * day, 1200 * day, A)).astype(np.int64),
+        "total_inviews": with_nan(rng.integers(0, 2_000_000, A)),
+        "total_pageviews": with_nan(rng.integers(0, 500_000, A)),
+        "total_read_time": with_nan(rng.integers(0, 50_000_000, A)),
+    }
+    if history_lens is None:
+        history_lens = rng.integers(1, max_history + 1, n_users)
+        history_lens[::10] = 0
+    history_lens = np.asarray(history_lens, dtype=np.int64)
+    histories = {"user_id": (1 + rng.permutation(3 * n_users)[:n_users]).astype(np.int64), "article_id": [], "impression_time_us": [],
+                 "read_time": [], "scroll_percentage": []}
+    for k in history_lens.tolist():
+        histories["article_id"].append(articles["article_id"][rng.integers(0, A, k)])
+        histories["impression_time_us"].append(np.sort(base - rng.integers(0, 90 * day, k)).astype(np.int64))
+        histories["read_time"].append(with_nan(rng.integers(0, 600, k)))
+        histories["scroll_percentage"].append(with_nan(rng.integers(0, 101, k)))
+    if list_lens is None:
+        list_lens = rng.integers(1, max_list + 1, n_impressions)
+    list_lens = np.asarray(list_lens, dtype=np.int64)
+    behaviors = {"impression_id": (1 + rng.permutation(5 * n_impressions)[:n_impressions]).astype(np.int64),
+                 "user_id": histories["user_id"][rng.integers(0, n_users, n_impressions)],
+                 "impression_time_us": (base + rng.integers(0, 7 * day, n_impressions)).astype(np.int64), "article_ids_inview": []}
+    clicked = []
+    for k in list_lens.tolist():
+        inview = articles["article_id"][rng.permutation(A)[:k]] if k <= A else articles["article_id"][rng.integers(0, A, k)]
+        behaviors["article_ids_inview"].append(inview)
+        r = rng.random()
+        if r < multi_click_frac or k == 0:
+            clicked.append(articles["article_id"][rng.integers(0, A, 0 if (k == 0 and r >= multi_click_frac) else 2)])
+        elif r < multi_click_frac + absent_target_frac and k < A:
+            outside = np.setdiff1d(articles["article_id"], inview)
+            clicked.append(outside[rng.integers(0, outside.shape[0], 1)])
+        else:
+            clicked.append(inview[rng.integers(0, k, 1)])
+    if labelled:
+        behaviors["article_ids_clicked"] = clicked
+    return articles, histories, behaviors
+
+
 def state_dict_shapes(dims: Dims, user_num: int | None = None):
     """Ordered (key, shape, kind) list: the 37 state_dict entries of the reference UserModel
      plus ``delta`` when ``user_num`` is given."""

@@ -10,6 +10,7 @@ backward and the Adam step.  BatchNorm statistics stay per replica.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -334,6 +335,24 @@ def attach_empty_num(batch, host):
     The counts are not trusted either way: the gather kernel checks every dropped cell."""
     dev = batch["empty_num"]
     return dict(batch, empty_num_host=(host, dev.data_ptr(), dev._version))
+
+
+def attach_known_history_len(batch, lengths):
+    """-> ``batch`` with ``"history_len_host"`` filled from HOST lengths the batch's own producer knows (``tables.TableLoader``: the number of
+    events it wrote rows for) instead of a measuring kernel and a copy; the entry has the form ``attach_history_len`` gives it and is dropped
+    the same way once ``x_history`` is another tensor or has been written to.  A known length can only be >= the measured one (a row the
+    producer wrote may be all-zero; a row behind its length never holds a bit), so the rows a plan drops are all-zero and compaction stays
+    exact."""
+    xh = batch["x_history"]
+    host = torch.as_tensor(np.ascontiguousarray(lengths, dtype=np.int32))
+    if tuple(host.shape) != (xh.shape[0],) or (host.numel() and (int(host.min()) < 0 or int(host.max()) > xh.shape[1])):
+        raise ValueError(f"attach_known_history_len: lengths {tuple(host.shape)} for x_history {tuple(xh.shape)} (one per impression, 0 .. H)")
+    return dict(batch, history_len_host=(host, torch.cuda.Event(), xh.data_ptr(), xh._version))     # (an event never recorded: complete)
+
+
+def attach_known_lengths(batch, history_len, empty_num):
+    """``attach_known_history_len`` and ``attach_empty_num`` from the producer's host arrays in one call."""
+    return attach_empty_num(attach_known_history_len(batch, history_len), np.ascontiguousarray(empty_num, dtype=np.int64))
 
 
 def _empty_num_host(batch):
@@ -671,6 +690,47 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
         rec = {"epoch": epoch, "lr": lr, "impressions": seen,
                "loss_avg": float(loss_sum / max(seen, 1)), "auc_avg": float(auc_sum / max(seen, 1))}
         history.append(rec)
+        if ckpt_path is not None:
+            evaluation.save_checkpoint(model, ckpt_path.format(epoch=epoch))
+    return history
+
+
+def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuffle=True, seed=0, keep_target_slot=True, device="cuda",
+                        ckpt_path=None, on_batch=None, compact_history=False, max_groups=None, compact_candidates=False, drop_last=False):
+    """``train_epochs`` over a data set that lives on the device as ``tables.ImpressionTables``: every batch is
+    written by the assemble kernel from a few KB of impression indices instead of being uploaded, on the current stream, and carries its
+    producer's history lengths and ``empty_num`` on the host, so ``compact_history`` / ``compact_candidates`` plan without a measuring
+    kernel or a synchronise.  The per-epoch record, the checkpoints and the index and padding checks are ``train_epochs``'s.  ``tables``:
+    host tables (uploaded once) or device tables."""
+    from . import evaluation, ops
+    from .tables import TableLoader
+    loader = TableLoader(tables, batch_size, H, T, shuffle=shuffle, seed=seed, keep_target_slot=keep_target_slot, device=device, drop_last=drop_last)
+    history = []
+    for epoch in range(epochs):
+        model.train()
+        lr = optimizer.param_groups[0]["lr"]
+        loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+        auc_sum = torch.zeros((), dtype=torch.float64, device=device)
+        bad_rows = torch.zeros((), dtype=torch.int64, device=device)
+        seen = 0
+        for i, batch in enumerate(loader):
+            loss, out = train_step(model, optimizer, batch, compact_history=compact_history, max_groups=max_groups,
+                                   compact_candidates=compact_candidates)
+            auc, _hit = evaluation.row_auc_top1(out, batch["label"])
+            n = out.shape[0]
+            loss_sum += loss.double() * n
+            auc_sum += auc.double().sum()
+            bad_rows += (auc < 0).sum()
+            seen += n
+            if on_batch is not None:
+                on_batch(epoch, i, loss, auc)
+        if int(bad_rows):
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        ops.check_index_errors(next(model.parameters()).device)
+        if compact_candidates:
+            ops.check_pad_errors(next(model.parameters()).device)
+        history.append({"epoch": epoch, "lr": lr, "impressions": seen,
+                        "loss_avg": float(loss_sum / max(seen, 1)), "auc_avg": float(auc_sum / max(seen, 1))})
         if ckpt_path is not None:
             evaluation.save_checkpoint(model, ckpt_path.format(epoch=epoch))
     return history
