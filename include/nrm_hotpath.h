@@ -172,11 +172,11 @@ int nrm_pwattn_bwd_dp_dtdh(const float* dz, const float* t, const float* h, cons
 long nrm_gemm_packed_floats(int nrows, int ncols, int mma);
 int nrm_gemm_nt_bf16_supported(int M, int K, int mma);
 /* Which kernel a launch of nrm_gemm_nt(M, N, K, mma) takes (additive entry point, the ABI version is unchanged): the selection of
- * the launch itself, without any device call, with the environment knobs applied as the launch applies them (NRM_NT_KC and NRM_RX_BM
- * at every call; NRM_NT_SMALLM, NRM_NT_NARROW, NRM_NT_13X2 and NRM_RX_MIN_WGS as latched at their first use in the process).
- *   NRM_MMA_F32:            NT | MT << 8 | WPE << 16 | KC << 24   of gemm_nt_kernel<NT, MT, EPI, WPE, KC>: NT 16-column tiles per
+ * the launch itself, without any device call, with the environment knobs applied as the launch applies them (NRM_RX_BM at every
+ * call; NRM_NT_SMALLM, NRM_NT_NARROW and NRM_RX_MIN_WGS as latched at their first use in the process).
+ *   NRM_MMA_F32:            NT | MT << 8 | WPE << 16 | KC << 24   of gemm_nt_kernel<NT, MT, EPI, WPE>: NT 16-column tiles per
  *                           N-chunk, MT 16-row tiles per wave (a workgroup holds 64 * MT rows), WPE waves per SIMD the kernel is built
- *                           for, KC 16-wide K-chunks per LDS stage
+ *                           for, KC 16-wide K-chunks per LDS stage (always 1: the deeper stages are gone, the byte keeps its place)
  *   NRM_MMA_BF16 / _BF16X3: RT | G << 8   of gemm_nt_rx_kernel<RT, MMA, EPI, G>: 16 * RT resident rows per workgroup, weight
  *                           fragments in groups of G reduction chunks; 0 where nrm_gemm_nt_bf16_supported is 0
  * -1: bad arguments (M, N or K <= 0, unknown mma). */
@@ -461,16 +461,16 @@ int nrm_pool_bmm_hragged(const float* s, const float* h, float* out, const int* 
 
 /* Which kernel a launch of nrm_pwattn_fwd / _fwd_ragged / _fwd_hragged takes (additive entry point, the ABI version is unchanged): the
  * answer of the selector the launches themselves switch on, without a kernel launch or an allocation, with the environment knobs applied
- * as the launches apply them (NRM_FWD_CT, NRM_FWD_WALK_F32 and NRM_FWD_TSPLIT at every call; NRM_FWD_RW, NRM_FWD_13X1 and NRM_FWD_WALK
- * as latched at their first use in the process).
+ * as the launches apply them (NRM_FWD_CT, NRM_FWD_WALK_F32 and NRM_FWD_TSPLIT at every call; NRM_FWD_WALK as latched at its first use
+ * in the process).
  *   ragged = 0: nrm_pwattn_fwd(B, T, H, D, mma) with (save_z = 1) or without a z buffer; N, max_count and k_max are not read.
  *   ragged = 1: nrm_pwattn_fwd_ragged(B, N, max_count, H, D, mma); T is not read.
  *   ragged = 2: nrm_pwattn_fwd_hragged(B, N, max_count, Mt = T, k_max, D, mma): T carries Mt, the number of 16-row score tiles; H is
  *               not read.
  *   cus: compute units of the device the launch would go to; 0: those of the current device, or 256 where there is none.
  * out[NRM_PWATTN_FWD_FORM_LEN]:
- *   [0] valid     0: the selection has no kernel and the launch is refused (a ragged form asked for with bf16 arithmetic or a z store, a
- *                 ragged width of more than one resident slice under NRM_FWD_RW=2, a width the bf16 forward cannot hold)
+ *   [0] valid     0: the selection has no kernel and the launch is refused (a ragged form asked for with bf16 arithmetic or a z store,
+ *                 a width the bf16 forward cannot hold)
  *   [1] family    NRM_FWD_STREAM (pwattn_fwd_kernel), NRM_FWD_RW_TILE (pwattn_fwd_rw_kernel), NRM_FWD_WALK_BF16 (pwattn_fwd_walk_kernel),
  *                 NRM_FWD_WALK_F32 (pwattn_fwd_walk_f32_kernel)
  *   [2..6]        NT, MT, WPE, CT, NW of pwattn_fwd_kernel<NT, MT, SAVE_Z, WPE, CT, NW, ..> (NRM_FWD_STREAM; 0 otherwise)

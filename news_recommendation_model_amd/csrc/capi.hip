@@ -104,10 +104,11 @@ const char* nrm_last_error(void) { return g_err; }
 long nrm_pwattn_packed_floats(int D) {
     if (D <= 0) return 0;
     const nrm::FwdPlan pl = nrm::pwattn_fwd_plan(D);
-    // fp32: kchunks 16-column chunks of rows x 64 B.  bf16 / bf16x3 (pwattn_fwd_bf16.hip): k32 chunks x (1 | 2) images x plan
-    // rows x 64 B, where the resident-W plan may pad the rows up to one more slice -- size for the largest of the three
-    const nrm::RwPlan r0 = nrm::pwattn_rw_plan(D, NRM_MMA_F32);
-    const long f32 = (long)pl.kchunks * (pl.rows > r0.rows ? pl.rows : r0.rows) * 16;
+    // fp32: kchunks 16-column chunks of rows x 64 B, the rows of the form the width takes (pack_wp_launch).  bf16 / bf16x3
+    // (pwattn_fwd_rw.hip): k32 chunks x (1 | 2) images x plan rows x 64 B, where the resident-W plan may pad the rows up to one more
+    // slice -- size for the largest of the three
+    const int rows0 = nrm::pwattn_fwd_uses_rw(D, NRM_MMA_F32) ? nrm::pwattn_rw_plan(D, NRM_MMA_F32).rows : pl.rows;
+    const long f32 = (long)pl.kchunks * rows0 * 16;
     const nrm::RwPlan r3 = nrm::pwattn_rw_plan(D, NRM_MMA_BF16X3), r1 = nrm::pwattn_rw_plan(D, NRM_MMA_BF16);
     const long b3 = (long)r3.k32 * 2 * r3.rows * 16, b1 = (long)r1.k32 * r1.rows * 16;
     const long need = f32 > b3 ? (f32 > b1 ? f32 : b1) : (b3 > b1 ? b3 : b1);
@@ -403,7 +404,7 @@ int nrm_gemm_nt_form(int M, int N, int K, int mma) {
         const nrm::GemmRxForm f = nrm::gemm_nt_rx_select(M, K, mma);
         return f.RT ? (f.RT | f.G << 8) : 0;
     }
-    const nrm::GemmNtForm f = nrm::gemm_nt_select(M, (K + 15) / 16, nrm::gemm_nt_plan(N));
+    const nrm::GemmNtForm f = nrm::gemm_nt_select(M, nrm::gemm_nt_plan(N));
     return f.NT | f.MT << 8 | f.WPE << 16 | f.KC << 24;
 }
 

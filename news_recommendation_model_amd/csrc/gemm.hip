@@ -108,18 +108,14 @@ hipError_t pack_rows_launch(const float* src, long rs, long cs, int nrows, int n
 }
 
 // ---------------------------------------------------------------------------------------------
-// KC (round 5): 16-wide K-chunks per LDS stage.  A launch of few workgroups (the head of C1: 5120 rows = 80 row blocks) has one
-// or two workgroups per CU, nothing co-resident to hide a stage's DMA latency behind, and with one chunk per stage a chain of
-// K/16 rounds of (DMA ~1.5 us  ||  52 MFMAs = 0.7 us) + barrier: latency-bound at a third of the MFMA rate.  KC = 2 / 4 puts two /
-// four consecutive chunks into one stage (the packed operand and the X rows are already laid out chunk after chunk): a quarter
-// of the rounds and barriers, 70 / 139 KB of LDS -- which such a launch has to spare.  Big grids keep KC = 1 (four workgroups per CU).
-template <int NT, int MT, int EPI, int WPE = 2, int KC = 1>
+// One 16-wide K-chunk per LDS stage, two stages.  (Deeper stages of 2 / 4 chunks were built for launches of few workgroups and
+// measured slower: DESIGN.md, "Deeper LDS stages ... no-go".)
+template <int NT, int MT, int EPI, int WPE = 2>
 __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 4 * MT * 16;
     constexpr int WROWS = NT * 16;
-    constexpr int SUB = (WROWS + BM) * 16;                           // one 16-wide chunk: [W chunk | X rows], 16 floats per row
-    constexpr int BUF = KC * SUB;
+    constexpr int BUF = (WROWS + BM) * 16;                           // one 16-wide chunk: [W chunk | X rows], 16 floats per row
     __shared__ __attribute__((aligned(16))) float smem[2 * BUF];
 
     const int tid = threadIdx.x;
@@ -168,12 +164,6 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(buf + (WROWS + (wave * MT + j) * 16) * 16),
                                                      16, voff_x[j], c * 64, 0, 0);
     };
-    // stage s = chunks KC*s .. KC*s + KC - 1 (those that exist)
-    auto dma_stage = [&](int s, float* buf) {
-#pragma unroll
-        for (int k = 0; k < KC; ++k)
-            if (KC == 1 || s * KC + k < p.kchunks) dma_chunk(s * KC + k, buf + k * SUB);
-    };
     // FULL = false: column tiles >= ntv -- the zero padding of the last N-chunk (3 of 13 tiles at N = 1608, 1 of 13 at N = 400) --
     // issue no MFMA: 3-4 % of the launch at those widths.  (The zero padding of the last K-chunk cannot be skipped the same way:
     // K-step j of a chunk covers k = 4 q + j over the four lane groups q -- the 16-byte fragment layout -- so at K = 402 every
@@ -210,20 +200,20 @@ __global__ __launch_bounds__(256, WPE) void gemm_nt_kernel(const GemmNtParams p)
     };
 
     const int nt_valid = min(NT, (p.N - n0 + 15) >> 4);              // (workgroup-uniform)
-    const int nstages = (p.kchunks + KC - 1) / KC;
-    dma_stage(0, smem);
+    dma_chunk(0, smem);
     __syncthreads();
     if (NRM_PRIO) __builtin_amdgcn_s_setprio(NRM_PRIO);
-    for (int c = 0; c < nstages; ++c) {
+    for (int c = 0; c < p.kchunks; ++c) {
         float* cur = smem + (c & 1) * BUF;
         float* nxt = smem + ((c & 1) ^ 1) * BUF;
-        if (c + 1 < nstages && !(NRM_DIAG_GEMM & 4)) dma_stage(c + 1, nxt);
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            if (KC > 1 && c * KC + k >= p.kchunks) break;
-            const int kleft = p.K - 16 * (c * KC + k);
-            if (nt_valid == NT) compute(cur + k * SUB, std::true_type{}, NT, kleft);
-            else compute(cur + k * SUB, std::false_type{}, nt_valid, kleft);
+        if (c + 1 < p.kchunks && !(NRM_DIAG_GEMM & 4)) dma_chunk(c + 1, nxt);
+        // A one-trip loop, what is left of the loop over a stage's chunks: hipcc's code for the whole kernel depends on it (without it the
+        // address arithmetic comes out differently, two more VGPRs and 7 to 17 more instructions per instantiation).  It stays so that
+        // every instantiation is instruction for instruction the measured one (scripts/asm_diff_instantiations.py).
+        for (int k = 0; k < 1; ++k) {
+            const int kleft = p.K - 16 * c;
+            if (nt_valid == NT) compute(cur, std::true_type{}, NT, kleft);
+            else compute(cur, std::false_type{}, nt_valid, kleft);
         }
         if (!(NRM_DIAG_GEMM & 1)) __syncthreads();
     }
@@ -292,42 +282,29 @@ GemmNtPlan gemm_nt_plan(int N) {
     return pl;
 }
 
-template <int NT, int MT, int WPE = 2, int KC = 1>
+template <int NT, int MT, int WPE = 2>
 static hipError_t launch_nt(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st) {
     constexpr int BM = 4 * MT * 16;
     const dim3 grid((p.M + BM - 1) / BM, pl.nchunks), block(256);
-    if (KC > 1) {                                                    // more than 64 KB of static LDS: opt in once per kernel and device
-        constexpr int lds = 2 * KC * (NT * 16 + BM) * 16 * 4;
-        static_assert(lds <= 160 * 1024, "two stages must fit the CU's LDS");
-    }
     switch (epi) {
-        case EPI_BIAS:  hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_BIAS, WPE, KC>), grid, block, 0, st, p); break;
-        case EPI_GELU:  hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_GELU, WPE, KC>), grid, block, 0, st, p); break;
-        case EPI_DGELU: hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_DGELU, WPE, KC>), grid, block, 0, st, p); break;
-        case EPI_MUL:   hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_MUL, WPE, KC>), grid, block, 0, st, p); break;
+        case EPI_BIAS:  hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_BIAS, WPE>), grid, block, 0, st, p); break;
+        case EPI_GELU:  hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_GELU, WPE>), grid, block, 0, st, p); break;
+        case EPI_DGELU: hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_DGELU, WPE>), grid, block, 0, st, p); break;
+        case EPI_MUL:   hipLaunchKernelGGL((gemm_nt_kernel<NT, MT, EPI_MUL, WPE>), grid, block, 0, st, p); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-// The one place that decides which gemm_nt_kernel<NT, MT, EPI, WPE, KC> a launch of M rows takes: gemm_nt_launch switches on it and
+// The one place that decides which gemm_nt_kernel<NT, MT, EPI, WPE> a launch of M rows takes: gemm_nt_launch switches on it and
 // nrm_gemm_nt_form (capi.hip) reports it, environment knobs included.
-GemmNtForm gemm_nt_select(int M, int kchunks, const GemmNtPlan& pl) {
+GemmNtForm gemm_nt_select(int M, const GemmNtPlan& pl) {
     // The row-tile count MT of a workgroup (64*MT rows) is free at launch time (the packed operand depends on NT only).  A grid
     // of fewer than two workgroups per CU leaves every workgroup alone with its chain of K-chunk rounds (DMA, barrier, a few
     // hundred MFMA cycles): C2's 258-wide layers were 240 workgroups of 128 rows at 57 % of the MFMA peak.  Such launches
     // take one row tile per wave instead.  NRM_NT_SMALLM=0 keeps the planned MT.
     static const bool small_m = [] { const char* e = getenv("NRM_NT_SMALLM"); return !(e && e[0] == '0'); }();
     const long wgs = (long)((M + 64 * pl.MT - 1) / (64 * pl.MT)) * pl.nchunks;
-    // Deeper LDS stages (template parameter KC = 2 | 4 chunks per stage) for launches of few workgroups: built on the theory that
-    // such a launch is a chain of DMA-latency-bound rounds, measured (graph replay, same box, whole step): C1 1.795 -> 1.84 ms
-    // (gemm_nt 33.2 -> 35.3 us per launch), reference default 12.9 -> 12.2 us per launch -- the latency chain is not what limits
-    // these launches.  Not a default: NRM_NT_KC=2|4 selects it (tests hold every depth bit-identical to KC = 1).
-    const char* kc_e = getenv("NRM_NT_KC");                           // (read per launch: tests switch forms inside one process)
-    int kc = kc_e ? atoi(kc_e) : 1;
-    if (kc != 2 && kc != 4) kc = 1;
-    if (kchunks < 2 * kc) kc = kchunks >= 4 ? 2 : 1;                 // (kchunks = ceil(K / 16))
-    if (kc > 1 && (pl.MT == 1 || (small_m && wgs < 512))) return GemmNtForm{pl.NT, 1, kc == 4 ? 1 : 2, kc};
     if (small_m && pl.MT > 1 && wgs < 512) return GemmNtForm{pl.NT, 1, 4, 1};
     if (pl.NT == 4) return GemmNtForm{4, 4, 2, 1};
     if (pl.NT == 5) return GemmNtForm{5, 4, 2, 1};
@@ -335,21 +312,17 @@ GemmNtForm gemm_nt_select(int M, int kchunks, const GemmNtPlan& pl) {
     if (pl.NT == 9) return GemmNtForm{9, 2, 3, 1};
     // 13 column tiles x ONE row tile per wave: 97 VGPRs and 35 KB of LDS, four workgroups per CU.  Measured on the head's
     // layers (M = 30 720, 1608 <-> 402): 0.199 ms per launch against 0.211 ms for 13x2 (129 VGPRs, 43 KB, three per CU),
-    // although every W chunk then serves 64 rows instead of 128.  NRM_NT_13X2=1 restores 13x2.
-    static const int use13x2 = [] { const char* e = getenv("NRM_NT_13X2"); return e && e[0] == '1' ? 1 : 0; }();
-    if (use13x2) return GemmNtForm{13, 2, 2, 1};
+    // although every W chunk then serves 64 rows instead of 128.
     return GemmNtForm{13, 1, 4, 1};
 }
 
 hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st) {
     if (p.M <= 0) return hipSuccess;
-    const GemmNtForm f = gemm_nt_select(p.M, p.kchunks, pl);
-#define NRM_NT(NT_, MT_, WPE_, KC_) \
-    if (f.NT == NT_ && f.MT == MT_ && f.WPE == WPE_ && f.KC == KC_) return launch_nt<NT_, MT_, WPE_, KC_>(p, pl, epi, st);
-#define NRM_NT_ROW1(NT_)  NRM_NT(NT_, 1, 1, 4) NRM_NT(NT_, 1, 2, 2) NRM_NT(NT_, 1, 4, 1)
-    NRM_NT_ROW1(4) NRM_NT_ROW1(5) NRM_NT_ROW1(8) NRM_NT_ROW1(9) NRM_NT_ROW1(13)
-    NRM_NT(4, 4, 2, 1) NRM_NT(5, 4, 2, 1) NRM_NT(8, 3, 2, 1) NRM_NT(9, 2, 3, 1) NRM_NT(13, 2, 2, 1)
-#undef NRM_NT_ROW1
+    const GemmNtForm f = gemm_nt_select(p.M, pl);
+#define NRM_NT(NT_, MT_, WPE_) \
+    if (f.NT == NT_ && f.MT == MT_ && f.WPE == WPE_) return launch_nt<NT_, MT_, WPE_>(p, pl, epi, st);
+    NRM_NT(4, 1, 4) NRM_NT(5, 1, 4) NRM_NT(8, 1, 4) NRM_NT(9, 1, 4) NRM_NT(13, 1, 4)
+    NRM_NT(4, 4, 2) NRM_NT(5, 4, 2) NRM_NT(8, 3, 2) NRM_NT(9, 2, 3)
 #undef NRM_NT
     return hipErrorInvalidValue;
 }

@@ -18,8 +18,8 @@ struct GemmNtParams {
 };
 struct GemmNtPlan { int NT, MT, nchunks, rows; };
 GemmNtPlan gemm_nt_plan(int N);
-struct GemmNtForm { int NT, MT, WPE, KC; };                // gemm_nt_kernel<NT, MT, EPI, WPE, KC>; the workgroup holds 64 * MT rows
-GemmNtForm gemm_nt_select(int M, int kchunks, const GemmNtPlan& pl);      // host only: what gemm_nt_launch runs (knobs applied)
+struct GemmNtForm { int NT, MT, WPE, KC; };                // gemm_nt_kernel<NT, MT, EPI, WPE>; the workgroup holds 64 * MT rows; KC: K-chunks per LDS stage, always 1
+GemmNtForm gemm_nt_select(int M, const GemmNtPlan& pl);    // host only: what gemm_nt_launch runs (knobs applied)
 hipError_t gemm_nt_launch(const GemmNtParams& p, const GemmNtPlan& pl, int epi, hipStream_t st);
 hipError_t pack_rows_launch(const float* src, long rs, long cs, int nrows, int ncols, int rows, int kchunks,
                             float* packed, hipStream_t st);

@@ -41,10 +41,10 @@ struct RaggedTabs {
 };
 struct FwdPlan { int NT, MT, nchunks, rows, kchunks; };
 FwdPlan pwattn_fwd_plan(int D);
-// Every environment knob of the forward, read in ONE place (fwd_knobs, pwattn_fwd.hip).  rw_mode (NRM_FWD_RW), use13 (NRM_FWD_13X1) and
-// walk (NRM_FWD_WALK) are latched at the first call in the process -- the packed W_p image depends on the first two; ct (NRM_FWD_CT),
-// walk_f32 (NRM_FWD_WALK_F32) and tsplit (NRM_FWD_TSPLIT) are read at every call.  ct / walk_f32: -1 unset, 0, 1.
-struct FwdKnobs { int rw_mode, use13, walk, ct, walk_f32, tsplit; bool tsplit_set; };      // tsplit counts only where tsplit_set
+// Every environment knob of the forward, read in ONE place (fwd_knobs, pwattn_fwd.hip).  walk (NRM_FWD_WALK) is latched at the first
+// call in the process; ct (NRM_FWD_CT), walk_f32 (NRM_FWD_WALK_F32) and tsplit (NRM_FWD_TSPLIT) are read at every call.  ct / walk_f32:
+// -1 unset, 0, 1.  None of them changes the packed W_p image, which depends on D and the arithmetic alone.
+struct FwdKnobs { int walk, ct, walk_f32, tsplit; bool tsplit_set; };      // tsplit counts only where tsplit_set
 FwdKnobs fwd_knobs();
 // What one forward launch runs: chosen by pwattn_fwd_select (host arithmetic only, no HIP call); the launches switch on it and on nothing else.
 enum FwdFamily { FWD_STREAM = 0, FWD_RW_TILE = 1, FWD_WALK_BF16 = 2, FWD_WALK_F32 = 3 };

@@ -316,19 +316,17 @@ __global__ __launch_bounds__(NW * 64, WPE) void pwattn_fwd_kernel(const FwdParam
 
 // Tile table: NT 16-column tiles per N-chunk x MT 16-row tiles per wave.  4*NT*MT accumulator registers must
 // stay within 2 waves/SIMD (<= 256 VGPRs), and 2 workgroups x 2 LDS buffers within 160 KB.
-// Up to 25 column tiles (D <= 400) the whole width is ONE N-chunk: no column padding and a single
-// accumulator-init / epilogue per row tile (measured at D=400: 13x3 in two chunks 4.73 ms, 25x1 4.28 ms) -- except
-// for 21..26 tiles, see pwattn_fwd_plan.
-static const int kNT[10] = {4, 6, 8, 10, 12, 13, 14, 16, 20, 25};
-static const int kMT[10] = {4, 4, 3, 1, 1, 1, 2, 1, 1, 1};     // 10..13 tiles: one row tile per wave, 3 waves/SIMD (3 row tiles spilled)
+// Up to 20 column tiles (D <= 320) the whole width is ONE N-chunk: no column padding and a single
+// accumulator-init / epilogue per row tile -- 21..26 tiles take two, see pwattn_fwd_plan.  Widths of up to 8 tiles (D <= 128) never
+// come here (pwattn_fwd_uses_rw: their whole W_p is one resident slice), so the table starts at 10.
+static const int kNT[6] = {10, 12, 13, 14, 16, 20};
+static const int kMT[6] = {1, 1, 1, 2, 1, 1};                  // 10..13 tiles: one row tile per wave, 3 waves/SIMD (3 row tiles spilled)
 
-// Every environment knob of the forward (pwattn.hpp).  The three latched ones are read at the first call in the process.
+// Every environment knob of the forward (pwattn.hpp).  The latched one is read at the first call in the process.
 FwdKnobs fwd_knobs() {
-    static const int rw_mode = [] { const char* e = getenv("NRM_FWD_RW"); return e ? atoi(e) : 1; }();
-    static const int use13 = [] { const char* e = getenv("NRM_FWD_13X1"); return e && e[0] == '0' ? 0 : 1; }();
     static const int walk = [] { const char* e = getenv("NRM_FWD_WALK"); return e && e[0] == '0' ? 0 : 1; }();
     FwdKnobs kn;
-    kn.rw_mode = rw_mode; kn.use13 = use13; kn.walk = walk;
+    kn.walk = walk;
     const char* e = getenv("NRM_FWD_CT");                             // (read per launch: tests switch forms inside one process)
     kn.ct = e ? (e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1) : -1;
     e = getenv("NRM_FWD_WALK_F32");
@@ -340,16 +338,15 @@ FwdKnobs fwd_knobs() {
 
 FwdPlan pwattn_fwd_plan(int D) {
     const int n16 = (D + 15) / 16;
-    int nch = n16 <= 25 ? 1 : (n16 + 15) / 16;          // wider than 25 tiles: chunks of at most 16 tiles
+    const int nch = n16 <= 20 ? 1 : (n16 + 15) / 16;    // wider than 20 tiles: chunks of at most 16 tiles
     // 21..26 column tiles (320 < D <= 416, incl. D = 400): two N-chunks of 13 tiles with ONE row tile per wave.  That
     // kernel needs 129 VGPRs and 43 KB of LDS, so three workgroups fit a CU (3 waves/SIMD instead of 2) -- measured at
-    // D = 400: 4.14 ms against 4.29 ms for the single 25-tile chunk, although the rows are streamed twice and the last
-    // chunk carries one all-padding tile (its MFMAs are skipped); three chunks of 10 tiles at four workgroups per CU:
-    // 4.27 ms.  NRM_FWD_13X1=0 restores the one-chunk plan.
-    if (fwd_knobs().use13 && n16 >= 21 && n16 <= 26) nch = 2;
+    // D = 400: 4.14 ms against 4.29 ms for a single 25-tile chunk (a form since removed), although the rows are streamed twice
+    // and the last chunk carries one all-padding tile (its MFMAs are skipped); three chunks of 10 tiles at four workgroups per
+    // CU: 4.27 ms.
     const int need = (n16 + nch - 1) / nch;
-    int sel = 9;
-    for (int i = 0; i < 10; ++i) if (kNT[i] >= need) { sel = i; break; }
+    int sel = 5;
+    for (int i = 0; i < 6; ++i) if (kNT[i] >= need) { sel = i; break; }
     FwdPlan pl;
     pl.NT = kNT[sel]; pl.MT = kMT[sel]; pl.nchunks = nch;
     pl.rows = nch * pl.NT * 16; pl.kchunks = n16;
@@ -365,16 +362,14 @@ static bool fwd_compact_t(const FwdKnobs& kn, int H, int block_rows = 64) {
     return H >= 16;
 }
 
-// bf16 forms: always the resident-W forward (pwattn_fwd_rw.hip).  fp32: only where the WHOLE W_p fits one LDS slice
-// (D <= 128; reference default D = 64: 0.128 -> 0.104 ms); with several slices the chunk-streaming kernel below is faster
-// (measured at C3, D = 400, 5 slices: 4.32 vs 4.13 ms; C5, D = 768: 20.5 vs 19.4 ms) and keeps the scores free of float
-// atomics.  NRM_FWD_RW=0 / =2 force the streaming / the resident form for fp32.
+// bf16 forms: the resident-W forward (pwattn_fwd_rw.hip) wherever a slice fits.  fp32: only where the WHOLE W_p is one LDS slice
+// (D <= 128; reference default D = 64: 0.128 -> 0.104 ms against streaming it); with several slices the chunk-streaming kernel
+// below is faster (measured at C3, D = 400, 5 slices: 4.32 vs 4.13 ms; C5, D = 768: 20.5 vs 19.4 ms) and keeps the scores free
+// of float atomics.
 bool pwattn_fwd_uses_rw(int D, int mma) {
-    const int mode = fwd_knobs().rw_mode;
     const RwPlan pl = pwattn_rw_plan(D, mma);
     if (pl.nts == 0) return false;
-    if (mma != 0) return true;
-    return mode == 2 || (mode == 1 && pl.nsplit == 1);
+    return mma != 0 || pl.nsplit == 1;
 }
 
 // THE selector of the forward: which kernel a dense, ragged or history-ragged launch runs, with which template parameters and grid.
@@ -402,7 +397,7 @@ FwdForm pwattn_fwd_select(long M, int B, int T, int H, int D, int mma, bool save
             if (!ragged) f.NW = 8;                 // tuning: 128-row workgroups of 8 waves, two per CU (dense only)
 #endif
             break;
-        default: break;                            // 4x4, 6x4, 8x3, 14x2, 16x1 (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms), 20x1, 25x1
+        default: break;                            // 14x2, 16x1 (compact image + three workgroups per CU measured SLOWER at C5: 19.43 vs 18.76 ms), 20x1
     }
     const int BM = f.NW * f.MT * 16;
     f.tasks = M > 0 ? (M + BM - 1) / BM : 0;
@@ -431,9 +426,6 @@ template <int RAGGED>
 static hipError_t fwd_dispatch(const FwdParams& p, const RaggedTabs& rg, const FwdForm& f, hipStream_t st) {
 #define NRM_FWD(...) launch_fwd_t<RAGGED, __VA_ARGS__>(p, rg, f, st)
     switch (f.NT) {
-        case 4:  return NRM_FWD(4, 4);
-        case 6:  return NRM_FWD(6, 4);
-        case 8:  return NRM_FWD(8, 3);
         case 10: return f.CT ? NRM_FWD(10, 1, 4, true) : NRM_FWD(10, 1, 3);
         case 12: return f.CT ? NRM_FWD(12, 1, 4, true) : NRM_FWD(12, 1, 3);
         case 13:
@@ -445,7 +437,6 @@ static hipError_t fwd_dispatch(const FwdParams& p, const RaggedTabs& rg, const F
         case 14: return NRM_FWD(14, 2);
         case 16: return NRM_FWD(16, 1);
         case 20: return NRM_FWD(20, 1);
-        case 25: return NRM_FWD(25, 1);
     }
 #undef NRM_FWD
     return hipErrorInvalidValue;

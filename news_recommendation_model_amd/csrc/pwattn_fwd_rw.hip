@@ -659,7 +659,7 @@ FwdForm pwattn_fwd_rw_select(long M, int B, int T, int H, int D, int mma, bool s
     const bool hrag = ragged == 2;
     const RwPlan pl = pwattn_rw_plan(D, mma);
     f.NTS = pl.nts; f.nsplit = pl.nsplit;
-    if (pl.nts == 0 || (ragged && (mma != 0 || save_z || pl.nsplit != 1))) return f;          // valid = 0
+    if (pl.nts == 0 || (ragged && (mma != 0 || save_z))) return f;                            // valid = 0
     const bool walkable = hrag || (M % ((long)T * H) == 0 && (long)T * H * D * 4 < (1L << 31));
     int walk_nts = 0, kch = 0;
     // fp32: the walk for the widths that are one resident slice of whole 16-column tiles

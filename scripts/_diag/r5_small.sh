@@ -1,8 +1,8 @@
-# small-shape benches (graph replay) with the round-5 GEMM stage depth / pool split forced off and on
+# small-shape benches (graph replay) with the round-5 pool split forced off and on (the GEMM stage depth it also swept is gone)
 mkdir -p gpurun_out/r5e
 for w in C1-demo ref-default C2-small; do
   for kc in 1 0; do
-    if [ $kc = 1 ]; then export NRM_NT_KC=1 NRM_POOL_JSPLIT=0; else unset NRM_NT_KC NRM_POOL_JSPLIT; fi
+    if [ $kc = 1 ]; then export NRM_POOL_JSPLIT=0; else unset NRM_POOL_JSPLIT; fi
     python bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline > gpurun_out/r5e/${w}_old$kc.json 2> gpurun_out/r5e/${w}_old$kc.err
     python - <<PY
 import json
@@ -12,4 +12,4 @@ print("$w", "round-4 forms" if $kc else "round-5 forms", d["ms_per_step"], "gemm
 PY
   done
 done
-unset NRM_NT_KC NRM_POOL_JSPLIT
+unset NRM_POOL_JSPLIT

@@ -7,7 +7,10 @@ a template parameter or a kernel argument must leave the existing instantiations
     python scripts/asm_diff_instantiations.py OLD NEW [FILE ...]          default: pwattn_fwd pwattn_fwd_rw pool_loss
 
 A kernel of OLD is matched to the kernel of NEW with the same demangled name, or with one more trailing ``false`` template argument
-(a new flag that defaults to off; a kernel that was no template becomes ``name<false>``); the argument list may have grown.  Symbol names, label numbers and comments are normalised away;
+(a new flag that defaults to off; a kernel that was no template becomes ``name<false>``), or with one trailing template argument fewer
+where DROPPED names the kernel and the old argument was the value given there (a parameter that was removed: only its old default
+survives); the argument list may have grown.  A kernel of OLD without a counterpart in NEW is gone (listed, not a difference); the
+kernels of NEW that no kernel of OLD was matched to are counted.  Symbol names, label numbers and comments are normalised away;
 every remaining difference is printed.  Differences in ``.amdhsa_kernarg_size`` and in the offset of an ``s_load`` from the kernel
 argument segment (a hidden argument behind a larger block) are counted apart from real ones, and so is the section directive of a kernel
 that became a template instantiation (``.text`` -> its own comdat ``.section .text.<symbol>``: where the code lies, not what it is).  Exit status 1 on a real difference.
@@ -72,6 +75,8 @@ def summary(name, old, new, ro, rn):
     print(f'  {name}\n    instructions {sum(co.values())}->{sum(cn.values())}  (a) resources: {fmt(a)}  (b) mfma/memory/lds/sync: {fmt(b)}  (c) other vector: {fmt(c)}'
           f'  division pair: {fmt(d)}  scalar: {fmt(e)}')
     return not a and not b and not c
+# template parameters that were removed: {kernel: the value (the old default) whose instantiations survive without the argument}
+DROPPED = {'gemm_nt_kernel': '1'}        # KC, 16-wide K-chunks per LDS stage
 def dem(names):
     r = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True).stdout.split('\n')
     return dict(zip(names, r))
@@ -83,13 +88,16 @@ for f in (sys.argv[3:] or ['pwattn_fwd', 'pwattn_fwd_rw', 'pool_loss']):
     b, bo = funcs(os.path.join(old_dir, f + '.s')); n, no = funcs(os.path.join(new_dir, f + '.s'))
     db, dn = dem(bo), dem(no)
     inv = {v: k for k, v in dn.items()}
-    same = diff = moved = within = 0
+    same = diff = moved = within = gone = 0
+    matched = set()
     if SUMMARY: rb, rn = resources(os.path.join(old_dir, f + '.s')), resources(os.path.join(new_dir, f + '.s'))
     for k in bo:
         d = db[k]
         cand = [d]
         m = re.match(r'^(void nrm::\w+<)([^>]*)(>\()', d)
         if m: cand.append(m.group(1) + m.group(2) + ', false' + m.group(3))
+        if m and m.group(1)[len('void nrm::'):-1] in DROPPED and m.group(2).endswith(', ' + DROPPED[m.group(1)[len('void nrm::'):-1]]):
+            cand.append(m.group(1) + m.group(2).rsplit(', ', 1)[0] + m.group(3))
         elif '<' not in d.split('(')[0]: cand.append('void ' + d.split('(')[0] + '<false>(')
         # prefix match on "name<args>(" since the argument list may have grown
         hit = None
@@ -98,7 +106,8 @@ for f in (sys.argv[3:] or ['pwattn_fwd', 'pwattn_fwd_rw', 'pool_loss']):
             hits = [x for x in dn.values() if x.startswith(key)]
             if len(hits) == 1: hit = inv[hits[0]]
         if hit is None:
-            print(f, 'NO MATCH', d[:120]); diff += 1; continue
+            print(f, 'GONE', d[:120]); gone += 1; continue
+        matched.add(hit)
         if b[k] == n[hit]: same += 1
         else:
             dl = [l for l in difflib.unified_diff(b[k], n[hit], lineterm='', n=0) if not l.startswith(('---', '+++', '@@'))]
@@ -109,7 +118,7 @@ for f in (sys.argv[3:] or ['pwattn_fwd', 'pwattn_fwd_rw', 'pool_loss']):
             if SUMMARY: within += summary(d.split('(')[0], b[k], n[hit], rb.get(k, {}), rn.get(hit, {}))
             else: print(f, 'DIFF', d[:100], len(dl), 'lines'); print('\n'.join(dl[:12]))
     real += diff
-    print(f'{f}: {len(bo)} existing instantiations: {same} identical, {moved} differ only in the kernel-argument size / a hidden-argument offset / the section directive of a kernel that became a template, '
-          f'{diff} really different; the new tree has {len(no)} kernels')
+    print(f'{f}: {len(bo)} existing instantiations: {gone} gone, {same} identical, {moved} differ only in the kernel-argument size / a hidden-argument offset / the section directive of a kernel that became a template, '
+          f'{diff} really different; the new tree has {len(no)} kernels, {len(no) - len(matched)} of them without a counterpart in the old')
     if SUMMARY and diff: print(f'{f}: {within} of the {diff} different kernels keep (a) the resource fields, (b) the matrix / memory / LDS / synchronisation counts and (c) the other vector counts')
 sys.exit(1 if real else 0)

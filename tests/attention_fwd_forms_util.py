@@ -15,12 +15,12 @@ NAME_OF_MMA = {v: k for k, v in MMA_BY_NAME.items()}
 FAMILIES = ("stream", "rw_tile", "walk_bf16", "walk_f32")
 FIELDS = ("valid", "family", "NT", "MT", "WPE", "CT", "NW", "NTS", "KCH", "mma", "save_z", "ragged", "nsplit", "tsplit", "workgroups",
           "tasks", "rounds", "nchunks")                     # out[NRM_PWATTN_FWD_FORM_LEN] of nrm_pwattn_fwd_form, in order
-LATCHED = ("NRM_FWD_RW", "NRM_FWD_13X1", "NRM_FWD_WALK")    # read once per process
+LATCHED = ("NRM_FWD_WALK",)                                # read once per process
 PER_LAUNCH = ("NRM_FWD_CT", "NRM_FWD_WALK_F32", "NRM_FWD_TSPLIT")
 KNOBS = LATCHED + PER_LAUNCH
 WAVES = {"stream": 0, "rw_tile": 16, "walk_bf16": 8, "walk_f32": 8}      # waves of a persistent workgroup
-# the latched settings that select forms the default dispatch never takes: one child process each
-LATCHED_SETTINGS = {"rw0": {"NRM_FWD_RW": "0"}, "rw2": {"NRM_FWD_RW": "2"}, "13x1_0": {"NRM_FWD_13X1": "0"}, "walk0": {"NRM_FWD_WALK": "0"}}
+# the latched settings that change what the default dispatch takes: one child process each
+LATCHED_SETTINGS = {"walk0": {"NRM_FWD_WALK": "0"}}
 
 
 def query(lib, B, T, H, D, mma=F32, save_z=1, ragged=0, N=0, max_count=0, k_max=0, cus=256):
@@ -286,27 +286,15 @@ def round2_shape(lib, case, cus):
 
 
 # 3. the forms behind latched knobs: {setting: [(shape, variants)]} (one round) and {setting: [second-round cases]}, run by
-# tests/attention_fwd_knob_worker.py in a child process each.
-# rw0: the streaming kernel at D <= 128, <4,4>, <6,4> and <8,3>: 357 rows, a full 256- / 192-row workgroup and a partial one.
-# rw2: the fp32 resident tiles in several slices, whose scores are float-atomic sums into a cleared buffer: NTS = 5 in 2 slices (D = 132), 6
-# (164), 8 (196), 4 (500), 3 (628), 2 in 32 slices (1024); and each of them with a second round.  13x1_0: one chunk of 25 tiles, with (388)
-# and without a ragged last tile, H = 16 and H = 7.
-_F32_Z = [("dense", F32, 1), ("dense", F32, 0)]
+# tests/attention_fwd_knob_worker.py in a child process each.  walk0 has none: every form it selects runs by default at another width.
 KNOB_CASES = {
-    "rw0": [((3, 7, 17, D), _F32_ALL) for D in (64, 68, 100)],
-    "rw2": [((3, 5, 17, D), _F32_Z) for D in (132, 164, 196, 500, 628, 1024)],
-    "13x1_0": [((3, 5, 16, 388), _F32_ALL)],
     "walk0": [],
 }
-KNOB_ROUND2 = {"rw2": [(f"rw2-tile-slices-D{D}", T, H, D, {}, _F32_Z) for D, T, H in ((132, 30, 150), (164, 30, 150), (196, 30, 150), (500, 11, 50),
-                                                                                     (628, 11, 50), (1024, 7, 50))]}
+KNOB_ROUND2 = {}
 # Cases that pin a knob's behaviour at a width rather than a form of their own (the closure does not need them: the same instantiations run
-# at other widths).  rw2 at the production width D = 400: five slices, where 132 has two (two float addends commute, five do not).  13x1_0:
-# D = 400 without a ragged last tile, H = 7 (a 64-row workgroup spans ten candidates).  walk0:
+# at other widths).  walk0:
 # the tile-by-tile resident kernel at exactly the widths the bf16 walks shadow, compared with the walks' own scores.
 KNOB_WIDTH_CASES = {
-    "rw2": [((3, 5, 17, 400), _F32_Z)],
-    "13x1_0": [((3, 5, 7, 400), _F32_ALL)],
     "walk0": [((3, 5, 17, D), _BF) for D in (64, 128, 256)],
 }
 

@@ -7,11 +7,11 @@ without a GPU case fails on any machine.  Shapes are (M, K, N): rows, reduction 
 input-gradient GEMM of the same layer is (M, N, K)."""
 
 F32, BF16, BF16X3 = 0, 1, 2
-KNOBS = ("NRM_NT_KC", "NRM_NT_SMALLM", "NRM_NT_NARROW", "NRM_NT_13X2", "NRM_RX_BM", "NRM_RX_MIN_WGS", "NRM_GEMM_F32")
+KNOBS = ("NRM_NT_SMALLM", "NRM_NT_NARROW", "NRM_RX_BM", "NRM_RX_MIN_WGS", "NRM_GEMM_F32")
 
 
 def nt_form(lib, M, N, K):
-    """(NT, MT, WPE, KC) of gemm_nt_kernel for y[M, N] = x[M, K] W^T in fp32."""
+    """(NT, MT, WPE, KC) of gemm_nt_kernel<NT, MT, EPI, WPE> for y[M, N] = x[M, K] W^T in fp32; KC, the K-chunks per LDS stage, is always 1."""
     v = lib.nrm_gemm_nt_form(M, N, K, F32)
     assert v > 0, (M, N, K, v)
     return (v & 255, (v >> 8) & 255, (v >> 16) & 255, (v >> 24) & 255)
@@ -39,15 +39,10 @@ def block_rows(form):
 
 
 # ---------------------------------------------------------------------------------------------- the GPU case lists
-# test_linear_forward_backward (fp32, default dispatch)
+# test_linear_forward_backward (fp32, default dispatch).  (300, 130, 128): <8,1,4>, the one-row-tile form of the 8-tile plan, which no
+# other shape takes; K = 130 is nine chunks, the last one ragged
 LINEAR_SHAPES = [(300, 402, 1608), (257, 1608, 402), (64, 3, 8), (1000, 402, 1), (33, 66, 64),
-                 (5, 272, 68), (192, 400, 400), (700, 402, 400), (700, 400, 402), (3000, 1608, 402), (1300, 402, 1608)]
-
-# test_gemm_nt_stage_depths_are_bit_identical (fp32, NRM_NT_KC = 1 | 2 | 4 | unset); the last two: K = 130 is nine chunks, the last
-# one ragged, neither a multiple of 2 nor of 4 -- <4,1,1,4> (N = 64), <8,1,2,2> and <8,1,1,4> (N = 128, and the dX of both)
-STAGE_DEPTH_SHAPES = [(5120, 1032, 258), (5120, 258, 1032), (3840, 264, 66), (300, 402, 1608), (257, 1608, 402), (33, 66, 64),
-                      (64, 3, 8), (700, 400, 402), (20000, 402, 400), (300, 130, 64), (300, 130, 128)]
-STAGE_DEPTHS = ("1", "2", "4", None)
+                 (5, 272, 68), (192, 400, 400), (700, 402, 400), (700, 400, 402), (3000, 1608, 402), (1300, 402, 1608), (300, 130, 128)]
 
 # test_linear_forward_backward_on_bf16_matrix_cores (bf16x3 and bf16).  (51200, 64, 64) and (15360, 258, 1032): 128- and 64-row blocks.
 # (25600, 128, 200): (RT, G) = (8, 4) forward; its dX (K = 200) is (8, 4) in bf16 and (4, 4) in bf16x3; 13 column tiles over 8 waves.
@@ -78,11 +73,9 @@ CONTAINMENT_CASES = [("f32", M, LARGE_GRID_K, N) for M, N, _ in LARGE_GRID_CASES
 MMA_BY_NAME = {"f32": F32, "bf16": BF16, "bf16x3": BF16X3}
 
 
-def reached_forms(lib, setenv, delenv):
-    """The set of dense_form answers over every launch the GPU cases above make (default latched knobs).  ``setenv`` / ``delenv``:
-    monkeypatch's, for NRM_NT_KC."""
+def reached_forms(lib):
+    """The set of dense_form answers over every launch the GPU cases above make (default latched knobs)."""
     out = set()
-    delenv("NRM_NT_KC", raising=False)
     for M, K, N in LINEAR_SHAPES:
         out |= {dense_form(lib, M, N, K, F32), dense_form(lib, M, K, N, F32)}
     for M, N, _ in LARGE_GRID_CASES:
@@ -90,12 +83,4 @@ def reached_forms(lib, setenv, delenv):
     for mma in (BF16, BF16X3):
         for M, K, N in BF16_LINEAR_SHAPES:
             out |= {dense_form(lib, M, N, K, mma), dense_form(lib, M, K, N, mma)}
-    for kc in STAGE_DEPTHS:
-        if kc is None:
-            delenv("NRM_NT_KC", raising=False)
-        else:
-            setenv("NRM_NT_KC", kc)
-        for M, K, N in STAGE_DEPTH_SHAPES:
-            out |= {dense_form(lib, M, N, K, F32), dense_form(lib, M, K, N, F32)}
-    delenv("NRM_NT_KC", raising=False)
     return out

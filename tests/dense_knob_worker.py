@@ -3,8 +3,7 @@ per process.  The parent sets the environment; this script checks with nrm_gemm_
 for, runs the dense ops against float64 PyTorch and prints ONE JSON line {"which", "forms_ok", "expected", "rel_err": {case: value}}.
 The gates are the parent's.
 
-    python tests/dense_knob_worker.py 13x2          (NRM_NT_13X2=1 NRM_TN_SHAPES=0)
-    python tests/dense_knob_worker.py planned_mt    (NRM_NT_SMALLM=0 NRM_NT_NARROW=0)
+    python tests/dense_knob_worker.py planned_mt    (NRM_NT_SMALLM=0 NRM_NT_NARROW=0 NRM_TN_SHAPES=0)
 """
 import json
 import os
@@ -82,22 +81,15 @@ def main(which):
     lib = native.load()
     nt = lambda M, N, K: dfu.nt_form(lib, M, N, K)               # noqa: E731
     out, n = {}, 0
-    if which == "13x2":
-        linears = [(300, 402, 1608), (257, 1608, 402), (700, 400, 402)]
-        forms_ok = all(nt(M, N, 402) == (13, 2, 2, 1) for N in (402, 1608, 400) for M in (257, 300, 700, 30720))
-        # ... and every 13-wide launch below is that form, forward and input gradient
-        forms_ok = forms_ok and all(nt(M, N, K) == (13, 2, 2, 1) and nt(M, K, N) == (13, 2, 2, 1) for M, K, N in linears)
-        for shape in linears:
-            n += linear_case(out, *shape)
-        for shape in [(640, 400, 402), (130, 2, 1608)]:
-            n += gemm_tn_case(out, *shape)
-    elif which == "planned_mt":
+    if which == "planned_mt":
         linears = [(300, 1032, 258), (300, 264, 66), (33, 66, 64)]
         forms_ok = (all(nt(M, 64, 66) == (4, 4, 2, 1) for M in (33, 300)) and all(nt(M, N, 264) == (8, 3, 2, 1) for N in (258, 66) for M in (33, 64, 300))
                     and nt(300, 1032, 258) == (13, 1, 4, 1) and nt(300, 264, 66) == (8, 3, 2, 1))
         for shape in linears:
             n += linear_case(out, *shape)
         n += mlp_case(out, 64, 264, 66, 264)
+        for shape in [(640, 400, 402), (130, 2, 1608)]:          # gemm_tn on the plain 4x4 / 5x5 wave tiles (NRM_TN_SHAPES=0)
+            n += gemm_tn_case(out, *shape)
     else:
         raise SystemExit(f"unknown knob set {which!r}")
     torch.cuda.synchronize()

@@ -1,8 +1,8 @@
 """CPU: nrm_pwattn_fwd_form reports, without a kernel launch, which forward kernel of the pointwise attention a launch of nrm_pwattn_fwd /
 _fwd_ragged / _fwd_hragged takes -- the selector the launches themselves switch on (csrc/pwattn_fwd.hip pwattn_fwd_select,
 csrc/pwattn_fwd_rw.hip pwattn_fwd_rw_select).  The production answers are pinned, bad arguments refused, the per-launch knobs honoured
-at every call, and the set of forms the selector can return -- under the default latched knobs and under each latched setting, one
-device-free child process each -- is held equal to the set the GPU cases of tests/attention_fwd_forms_util.py reach."""
+at every call, and the set of forms the selector can return -- under the default latched knob and under its other setting, in a
+device-free child process -- is held equal to the set the GPU cases of tests/attention_fwd_forms_util.py reach."""
 import json
 import os
 import subprocess
@@ -23,7 +23,7 @@ def forms(lib, monkeypatch):
     # the latched knobs were read at the first query of this process: these tests describe the default dispatch
     probe = [afu.dense_query(lib, (3, 5, 17, D), mma, 1, CUS) for D, mma in ((64, F32), (400, F32), (64, BF16))]
     assert [(f["family"], afu.template(f)) for f in probe] == [("walk_f32", (4,)), ("stream", (13, 1, 4, 1, 4)), ("walk_bf16", (4, 2))], \
-        "run without NRM_FWD_RW / NRM_FWD_13X1 / NRM_FWD_WALK"
+        "run without NRM_FWD_WALK"
     return lib
 
 
@@ -74,8 +74,8 @@ def test_selections_without_a_kernel(forms):
 
 
 def test_every_history_ragged_selection_has_a_kernel(forms):
-    """A history-ragged workgroup of the streaming kernel holds NW * MT <= 16 row tiles (its compact image has 16 rows): 4 x 4 = 16 at <4,4>
-    and <6,4>, 12 at <8,3>, 8 at <14,2>, 4 otherwise -- every plan passes, so no width and no k_max reaches a selection without a kernel
+    """A history-ragged workgroup of the streaming kernel holds NW * MT <= 16 row tiles (its compact image has 16 rows): 8 at <14,2>, 4
+    otherwise -- every plan passes, so no width and no k_max reaches a selection without a kernel
     from ops.attend_pool_hragged.  Pinned over every width the entry accepts, both sides of k_max = 16, both candidate images."""
     for ct in (None, "0", "1"):
         with afu.env({} if ct is None else {"NRM_FWD_CT": ct}):
@@ -195,7 +195,7 @@ def default_side(lib):
 
 
 def _closure(forms, default_side, latched, skip=None, skip_knob=(None, -1)):
-    """(possible, reached) over the default dispatch and the four latched settings; ``skip``: a case of SMALL_CASES / ROUND2_CASES left out,
+    """(possible, reached) over the default dispatch and the latched setting; ``skip``: a case of SMALL_CASES / ROUND2_CASES left out,
     ``skip_knob``: (setting, index into its KNOB_CASES + KNOB_ROUND2) left out."""
     possible, older = default_side
     possible = set(possible)
@@ -208,9 +208,6 @@ def _closure(forms, default_side, latched, skip=None, skip_knob=(None, -1)):
 
 def test_latched_settings_select_what_they_are_for(default_side, latched):
     fam = lambda which, name, mma=F32: {k[1] for k in latched[which][0] if k[0] == name and k[2] == mma}          # noqa: E731
-    assert {(4, 4, 2, 0, 4), (6, 4, 2, 0, 4), (8, 3, 2, 0, 4)} <= fam("rw0", "stream") and not fam("rw0", "rw_tile") and not fam("rw0", "walk_f32")
-    assert not fam("rw2", "stream") and {k[1] for k in latched["rw2"][0] if k[0] == "rw_tile" and k[2] == F32 and k[5]} == {(n,) for n in (2, 3, 4, 5, 6, 8)}
-    assert (25, 1, 2, 0, 4) in fam("13x1_0", "stream") and not [k for k in default_side[0] if k[1][0] == 25]
     assert not fam("walk0", "walk_bf16", BF16) and not fam("walk0", "walk_bf16", BF16X3) and fam("walk0", "walk_f32") == {(4,), (8,)}
 
 
@@ -223,13 +220,12 @@ def test_every_form_the_selector_returns_has_a_gpu_case(forms, default_side, lat
     assert reached - possible == set(), "forms the sweep does not find: widen the sweep"
     # what the set is today
     fam = lambda name: {k for k in possible if k[0] == name}          # noqa: E731
-    assert {k[1] for k in fam("stream")} == {(4, 4, 2, 0, 4), (6, 4, 2, 0, 4), (8, 3, 2, 0, 4), (10, 1, 3, 0, 4), (10, 1, 4, 1, 4), (12, 1, 3, 0, 4),
-                                             (12, 1, 4, 1, 4), (13, 1, 3, 0, 4), (13, 1, 4, 1, 4), (14, 2, 2, 0, 4), (16, 1, 2, 0, 4),
-                                             (20, 1, 2, 0, 4), (25, 1, 2, 0, 4)}
+    assert {k[1] for k in fam("stream")} == {(10, 1, 3, 0, 4), (10, 1, 4, 1, 4), (12, 1, 3, 0, 4), (12, 1, 4, 1, 4), (13, 1, 3, 0, 4), (13, 1, 4, 1, 4),
+                                             (14, 2, 2, 0, 4), (16, 1, 2, 0, 4), (20, 1, 2, 0, 4)}
     assert {k[1] for k in fam("rw_tile")} == {(n,) for n in (1, 2, 3, 4, 5, 6, 8)}
     assert {k[1] for k in fam("walk_bf16")} == {(4, 2), (8, 4), (8, 8)} and {k[1] for k in fam("walk_f32")} == {(4,), (8,)}
     assert all(not k[7] for k in fam("stream")) and all(k[2] == F32 for k in fam("stream") | fam("walk_f32"))
-    assert len(possible) == 308          # 268 under the default latched knobs, 40 more behind them
+    assert len(default_side[0]) == 268 and len(possible) == 268          # NRM_FWD_WALK=0 selects forms that also run by default at other widths
 
 
 def test_every_new_gpu_case_is_needed(forms, default_side, latched):

@@ -1,8 +1,8 @@
-"""CPU: nrm_gemm_nt_form reports, without a device, which gemm_nt_kernel<NT, MT, EPI, WPE, KC> (fp32) or gemm_nt_rx_kernel<RT, MMA, EPI, G>
+"""CPU: nrm_gemm_nt_form reports, without a device, which gemm_nt_kernel<NT, MT, EPI, WPE> (fp32) or gemm_nt_rx_kernel<RT, MMA, EPI, G>
 (bf16 / bf16x3) a launch of nrm_gemm_nt takes -- the selector the launch itself calls (csrc/gemm.hip gemm_nt_select, csrc/gemm_bf16.hip
 gemm_nt_rx_select).  The answers for the production layers are pinned, and the set of forms the selector can return is held equal to
-the set the GPU cases of tests/dense_forms_util.py reach.  The forms behind the knobs that are latched once per process (NRM_NT_13X2,
-NRM_NT_SMALLM, NRM_NT_NARROW) are enumerated by the child processes of tests/test_gpu_dense.py, not here."""
+the set the GPU cases of tests/dense_forms_util.py reach.  The forms behind the knobs that are latched once per process (NRM_NT_SMALLM,
+NRM_NT_NARROW) are enumerated by the child process of tests/test_gpu_dense.py, not here."""
 import pytest
 
 import dense_forms_util as dfu
@@ -15,7 +15,7 @@ def forms(lib, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     # the latched knobs were read at the first query of this process: these tests describe the default dispatch
     assert dfu.nt_form(lib, 150, 64, 64) == (4, 1, 4, 1) and dfu.nt_form(lib, 150, 258, 64) == (9, 1, 4, 1), "run without NRM_NT_SMALLM / NRM_NT_NARROW"
-    assert dfu.nt_form(lib, 150, 402, 64) == (13, 1, 4, 1), "run without NRM_NT_13X2"
+    assert dfu.nt_form(lib, 150, 402, 64) == (13, 1, 4, 1)
     return lib
 
 
@@ -48,40 +48,26 @@ def test_large_grid_cases_take_their_forms(forms):
         assert dfu.nt_form(forms, M // 2, N, dfu.LARGE_GRID_K)[1] == 1  # half the rows: below 512 workgroups, one row tile per wave
 
 
-def test_stage_depth_cases_reach_the_missing_kc_forms(forms, monkeypatch):
-    got = set()
-    for kc in ("2", "4"):
-        monkeypatch.setenv("NRM_NT_KC", kc)
-        for M, K, N in dfu.STAGE_DEPTH_SHAPES[-2:]:
-            got |= {dfu.nt_form(forms, M, N, K), dfu.nt_form(forms, M, K, N)}
-    assert {(4, 1, 1, 4), (8, 1, 2, 2), (8, 1, 1, 4)} <= got
-
-
 # the issue's sweep, and the row counts of the production layers on top (the 64-row bf16 blocks exist only between the M that is
 # too small for 200 blocks of 64 rows and the M that is enough for 200 blocks of 128)
 SWEEP_M = (1, 150, 5000, 200000, 15360, 30720)
 SWEEP_K = (16, 40, 130, 256, 128)               # 128: four chunks (G = 4) whose 128 bf16x3 rows still fit half the LDS; at K = 256 only bf16's do
 
 
-def test_every_form_the_selector_returns_has_a_gpu_case(forms, monkeypatch):
+def test_every_form_the_selector_returns_has_a_gpu_case(forms):
     possible = set()
-    for kc in (None, "2", "4"):
-        if kc is None:
-            monkeypatch.delenv("NRM_NT_KC", raising=False)
-        else:
-            monkeypatch.setenv("NRM_NT_KC", kc)
-        for M in SWEEP_M:
-            for K in SWEEP_K:
-                for N in range(1, 2101):
-                    possible.add(dfu.dense_form(forms, M, N, K, F32))
-                for mma in (BF16, BF16X3):                          # (the bf16 forms depend on neither N nor NRM_NT_KC)
-                    possible.add(dfu.dense_form(forms, M, 64, K, mma))
-                    possible.add(dfu.dense_form(forms, M, 2100, K, mma))
-    reached = dfu.reached_forms(forms, monkeypatch.setenv, monkeypatch.delenv)
+    for M in SWEEP_M:
+        for K in SWEEP_K:
+            for N in range(1, 2101):
+                possible.add(dfu.dense_form(forms, M, N, K, F32))
+            for mma in (BF16, BF16X3):                              # (the bf16 forms do not depend on N)
+                possible.add(dfu.dense_form(forms, M, 64, K, mma))
+                possible.add(dfu.dense_form(forms, M, 2100, K, mma))
+    reached = dfu.reached_forms(forms)
     assert possible - reached == set(), "forms without a GPU case"
     assert reached - possible == set(), "forms the sweep does not find: widen the sweep"
-    # what the set is today: 5 planned and 4 one-row-tile fp32 forms, two deeper stages for each of the five widths; RT x G for each bf16 arithmetic
-    assert len({f for f in possible if f[0] == "nt"}) == 19
+    # what the set is today: 5 planned and 4 one-row-tile fp32 forms, one K-chunk per LDS stage in all of them; RT x G for each bf16 arithmetic
+    assert len({f for f in possible if f[0] == "nt"}) == 9 and all(f[4] == 1 for f in possible if f[0] == "nt")
     assert {f[1:] for f in possible if f[0] == "rx"} == {(mma, rt, g) for mma in (BF16, BF16X3) for rt in (1, 2, 4, 8) for g in (3, 4)}
 
 
@@ -101,11 +87,6 @@ def test_bad_arguments(forms):
 
 
 def test_knobs_read_at_every_call(forms, monkeypatch):
-    monkeypatch.setenv("NRM_NT_KC", "4")
-    assert dfu.nt_form(forms, 300, 402, 402) == (13, 1, 1, 4)
-    assert dfu.nt_form(forms, 300, 402, 100) == (13, 1, 2, 2)       # seven chunks: fewer than two stages of four
-    assert dfu.nt_form(forms, 300, 402, 40) == (13, 1, 4, 1)        # three chunks: the plain kernel
-    assert dfu.nt_form(forms, 131073, 64, 402) == (4, 4, 2, 1)      # a large grid keeps its planned row tiles
-    monkeypatch.delenv("NRM_NT_KC")
+    assert dfu.rx_form(forms, 51200, 64, 64, BF16) == (8, 3)
     monkeypatch.setenv("NRM_RX_BM", "32")
     assert dfu.rx_form(forms, 51200, 64, 64, BF16) == (2, 3)

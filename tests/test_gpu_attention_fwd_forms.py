@@ -13,8 +13,10 @@ the set the selector returns.  Gates are those of tests/attention_budget.py, unc
      last round, computed from the compute-unit count.  Scores per impression against float64, the saved z of the first and the last two
      impressions (the second round's rows are the last ones), and a NaN planted in the first row of the wave that takes the first
      second-round tile / task.
-  3. test_latched_knobs_in_a_child_process: NRM_FWD_RW=0 | 2, NRM_FWD_13X1=0, NRM_FWD_WALK=0, one fresh python child each
-     (tests/attention_fwd_knob_worker.py); the child prints its figures, the gates are applied here."""
+  3. test_latched_knobs_in_a_child_process: NRM_FWD_WALK=0 in a fresh python child (tests/attention_fwd_knob_worker.py); the child
+     prints its figures, the gates are applied here.
+  4. test_slices_add_b2_once_into_a_cleared_buffer: the several-slice launch path (bf16x3 at D = 132 and 400) adds b2 in one slice only
+     and clears the score buffer its slices add into."""
 import json
 import os
 import subprocess
@@ -49,7 +51,7 @@ def cus(lib, monkeypatch):
     # the latched knobs were read at the first query or launch of this process: these tests describe the default dispatch
     probe = [afu.dense_query(lib, (3, 5, 17, D), mma, 1, n) for D, mma in ((64, F32), (400, F32), (64, BF16))]
     assert [(f["family"], afu.template(f)) for f in probe] == [("walk_f32", (4,)), ("stream", (13, 1, 4, 1, 4)), ("walk_bf16", (4, 2))], \
-        "run without NRM_FWD_RW / NRM_FWD_13X1 / NRM_FWD_WALK"
+        "run without NRM_FWD_WALK"
     return n
 
 
@@ -103,6 +105,38 @@ def test_second_round(lib, cus, case):
     for (kind, mma, z), f, figure in runs:
         _record.append({"test": "round2", "case": case[0], "shape": list(shape), "variant": [kind, afu.NAME_OF_MMA[mma], z],
                         "form": afu._jsonable(afu.key(f)), "rounds": f["rounds"], "figure": figure})
+
+
+def _direct_launch(data, mma, b2=None, prefill=None):
+    """nrm_pwattn_fwd (no z) as ops calls it, into a score buffer of this module's own -> s [B, T, H] on the host."""
+    from news_recommendation_model_amd import native, ops
+    B, T, H, D = data.shape
+    w1, b1, w2, b2_w = data.wd
+    if b2 is not None:
+        b2_w = torch.full_like(b2_w, b2)
+    t, h, u, v, packed, w2v, b2v = ops._attn_operands(data.dev(data.t), data.dev(data.h), w1, b1, w2, b2_w, mma)
+    s = torch.full((B * T * H,), float(prefill), device="cuda") if prefill is not None else torch.empty(B * T * H, device="cuda")
+    native.call("nrm_pwattn_fwd", native.ptr(t), native.ptr(h), native.ptr(u), native.ptr(v), native.ptr(packed), native.ptr(w2v),
+                native.ptr(b2v), None, native.ptr(s), B, T, H, D, mma, native.stream_ptr())
+    torch.cuda.synchronize()
+    return s.cpu().numpy().reshape(B, T, H)
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 17, 132), (3, 5, 17, 400)], ids=lambda s: f"D{s[3]}")
+def test_slices_add_b2_once_into_a_cleared_buffer(lib, cus, shape):
+    """Several column slices (bf16x3: two at D = 132, five at D = 400) add their partial scores with float atomics.  b2 is added by ONE
+    slice: the scores move by exactly the change of b2 (to fp32 rounding of sums of this size, the products being identical and only the
+    order of the atomic adds free); and the launch clears the buffer its slices add into: what was there before is not part of the scores."""
+    f = afu.dense_query(lib, shape, BF16X3, 0, cus)
+    assert f["valid"] and f["family"] == "rw_tile" and f["nsplit"] > 1, f
+    assert f["nsplit"] == {132: 2, 400: 5}[shape[3]]
+    data = afu.Data(shape)
+    s0, s1 = _direct_launch(data, BF16X3, b2=0.0), _direct_launch(data, BF16X3, b2=0.75)
+    tol = 64 * 2.0 ** -24 * max(1.0, float(np.abs(s1).max()))
+    s2 = _direct_launch(data, BF16X3, b2=0.75, prefill=1000.0)
+    print(f"{shape} slices {f['nsplit']}: |s1 - s0 - 0.75| {np.abs(s1 - s0 - 0.75).max():.3e}, |s2 - s1| {np.abs(s2 - s1).max():.3e} (tolerance {tol:.3e})")
+    assert np.abs(s1 - s0 - 0.75).max() <= tol, "b2 does not enter the scores exactly once"
+    assert np.abs(s2 - s1).max() <= tol, "a pre-filled score buffer is added to"
 
 
 @pytest.mark.parametrize("which", sorted(afu.LATCHED_SETTINGS))

@@ -35,42 +35,6 @@ def test_linear_forward_backward(lib, M, K, N, gelu):
     assert rel_err(bg.grad.cpu().numpy(), br.grad.numpy()) < 1e-5
 
 
-@pytest.mark.parametrize("M,K,N", dfu.STAGE_DEPTH_SHAPES)
-def test_gemm_nt_stage_depths_are_bit_identical(lib, monkeypatch, M, K, N):
-    """gemm_nt_kernel<..., KC>: one, two or four 16-wide K-chunks per LDS stage (round 5: built for launches of few workgroups -- the
-    heads of C1 and of the reference's default sizes --, measured no faster there, kept behind NRM_NT_KC).  The chunks are contracted in the same order
-    whatever the stage depth, so forward, input gradient and the GELU / GELU' epilogues must agree bit for bit with KC = 1 (the
-    round-4 kernel, which the float64 comparisons of this file were written against); K / 16 not a multiple of KC, fewer chunks
-    than one stage, a grid that would not pick KC by itself."""
-    from news_recommendation_model_amd import ops
-    g = torch.Generator(device="cpu").manual_seed(M + K + N)
-    x = torch.randn(M, K, generator=g).cuda()
-    w = (torch.randn(N, K, generator=g) / np.sqrt(K)).cuda()
-    b = (torch.randn(N, generator=g) * 0.1).cuda()
-    gy = torch.randn(M, N, generator=g).cuda()
-    out = {}
-    for kc in dfu.STAGE_DEPTHS:                   # None: the default dispatch (KC = 1 since the measurement of round 5)
-        if kc is None:
-            monkeypatch.delenv("NRM_NT_KC", raising=False)
-        else:
-            monkeypatch.setenv("NRM_NT_KC", kc)
-        if K == 130:                              # nine chunks: the forward launch really is the stage depth asked for (nrm_gemm_nt_form)
-            assert dfu.nt_form(lib, M, N, K) == {"1": (N // 16, 1, 4, 1), None: (N // 16, 1, 4, 1), "2": (N // 16, 1, 2, 2), "4": (N // 16, 1, 1, 4)}[kc]
-        res = []
-        for gelu in (False, True):
-            xg = x.clone().requires_grad_(True)
-            y = ops.linear(xg, w, b, gelu=gelu)
-            y.backward(gy)
-            res += [y.detach().clone(), xg.grad.clone()]
-        torch.cuda.synchronize()
-        out[kc] = res
-    for kc in ("2", "4", None):
-        for a, r in zip(out[kc], out["1"]):
-            assert torch.equal(a, r), (kc, float((a - r).abs().max()))
-    ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
-    assert rel_err(out[None][0].cpu().numpy(), ref.cpu().numpy()) < 1e-5
-
-
 @pytest.mark.parametrize("M,K,Hd,N", [(300, 1608, 402, 1608), (257, 1608, 402, 1), (64, 264, 66, 264), (33, 72, 18, 5),
                                       (7, 16, 4, 3), (1000, 256, 64, 1)])
 def test_mlp_gelu_forward_backward(lib, M, K, Hd, N):
@@ -399,19 +363,19 @@ def test_gemm_nt_large_grid_forms(lib, monkeypatch, M, N, form, epilogue):
         assert err < 1e-5
 
 
-# The knobs that are latched once per process (function-local statics of csrc/gemm.hip): each set runs in a child process of its
-# own (tests/dense_knob_worker.py), one after the other; the child prints one JSON line of rel_err values, the gates are here.
-@pytest.mark.parametrize("which", ["13x2", "planned_mt"])
+# The knobs that are latched once per process (function-local statics of csrc/gemm.hip) run in a child process
+# (tests/dense_knob_worker.py); the child prints one JSON line of rel_err values, the gates are here.
+@pytest.mark.parametrize("which", ["planned_mt"])
 def test_latched_gemm_knobs_in_a_child_process(lib, which):
-    """A: NRM_NT_13X2=1 (gemm_nt_kernel<13,2>) with NRM_TN_SHAPES=0 (gemm_tn on the plain 4x4 / 5x5 wave tiles).
-    B: NRM_NT_SMALLM=0 and NRM_NT_NARROW=0: the planned MT > 1 forms (<4,4>, <8,3>) on small grids."""
+    """NRM_NT_SMALLM=0 and NRM_NT_NARROW=0: the planned MT > 1 forms (<4,4>, <8,3>) on small grids; NRM_TN_SHAPES=0: gemm_tn on the plain
+    4x4 / 5x5 wave tiles."""
     import json
     import os
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     env = {k: v for k, v in os.environ.items() if k not in dfu.KNOBS and k != "NRM_TN_SHAPES"}
-    env.update({"13x2": {"NRM_NT_13X2": "1", "NRM_TN_SHAPES": "0"}, "planned_mt": {"NRM_NT_SMALLM": "0", "NRM_NT_NARROW": "0"}}[which])
+    env.update({"planned_mt": {"NRM_NT_SMALLM": "0", "NRM_NT_NARROW": "0", "NRM_TN_SHAPES": "0"}}[which])
     pr = subprocess.run([sys.executable, os.path.join(here, "dense_knob_worker.py"), which], env=env, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=300)
     assert pr.returncode == 0, (pr.returncode, pr.stderr.decode(errors="replace")[-3000:])

@@ -128,10 +128,8 @@ def _attn_case(entry, mma, B, T, H, D, rowgrads=True):
 # (B, T, H, D): B >= 3 (impression 1 has neighbours on both sides); ragged D the dP walk takes (72, 100, 132, 388, 420), exact controls
 # (64, 256, 400), D = 66 (padded by the wrapper); H < 16 and H % 16 != 0 (a 16-row fragment spans impressions).  fp32 chunk-streaming
 # forward plans (D > 128; D <= 128 takes the resident-W forms): 132 -> 10 tiles, 188 -> 12, 196 -> 13, 256 -> 16, 300 -> 20,
-# 388 / 400 -> 2 x 13, 420 -> 2 x 14.  The 4-, 6- and 8-tile plans are not reachable through the default dispatch (a width of at most
-# 8 tiles takes the resident-W forward, a wider one is split into chunks of more than 8 tiles), nor is the 25-tile one (21..26 tiles
-# are two chunks of 13 unless NRM_FWD_13X1=0, a knob latched once per process): tests/test_gpu_attention_fwd_forms.py plants its NaN and
-# Inf rows in them, one child process per latched knob (tests/attention_fwd_knob_worker.py).
+# 388 / 400 -> 2 x 13, 420 -> 2 x 14.  There are no narrower plans (a width of at most 8 tiles takes the resident-W forward, a wider
+# one is split into chunks of more than 8 tiles) and no wider one (21..26 tiles are two chunks of 12 or 13).
 ATTN_SHAPES = [(3, 3, 20, 72), (3, 2, 17, 100), (3, 2, 18, 132), (3, 2, 17, 388), (3, 2, 16, 420), (3, 2, 20, 64), (3, 2, 16, 256),
                (3, 2, 20, 400), (3, 3, 7, 66), (4, 3, 6, 132), (3, 2, 5, 196), (3, 2, 19, 300), (3, 2, 17, 128), (3, 2, 17, 188)]
 
