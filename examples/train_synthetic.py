@@ -7,6 +7,7 @@ launch), host float64 batches staged one ahead, per-impression AUC on the device
     python examples/train_synthetic.py --workload ref-default --compact-history --history-lengths uniform      
     python examples/train_synthetic.py --workload ref-default --compact-candidates --candidate-counts percentile    (section 5f)
     python examples/train_synthetic.py --workload ref-default --from-tables --compact-history --compact-candidates    (section 5g)
+    python examples/train_synthetic.py --workload ref-default --from-tables --graph --batches 100     (section 5g: one graph replay per step)
 """
 import argparse
 import os
@@ -43,7 +44,13 @@ def main():
     ap.add_argument("--from-tables", action="store_true",
                     help="keep the data set on the device as index-based tables (raw synthetic records through tables.ImpressionTables) and write "
                          "every batch there with the assemble kernel (trainer.train_epochs_tables) instead of uploading processed records")
+    ap.add_argument("--graph", action="store_true",
+                    help="with --from-tables: after three eager steps every full batch is ONE replay of a captured step that assembles its own "
+                         "batch at a device-side cursor (trainer.GraphedTableEpoch); the host reads the device once per epoch.  With --ckpt-dir "
+                         "the per-step losses of every epoch are written as the reference writes them (train.py:93-94)")
     args = ap.parse_args()
+    if args.graph and not args.from_tables:
+        raise SystemExit("--graph captures the table-fed epoch: use it with --from-tables")
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
     wl = WORKLOADS[args.workload]
@@ -108,13 +115,18 @@ def main_from_tables(args, wl, B, dims):
     model = trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=args.seed + 1, user_num=user_num))
     opt = trainer.FlatAdam(model, lr=args.lr)
     ckpt_dir = args.ckpt_dir or tempfile.mkdtemp(prefix="nrm_ckpt_")
+    os.makedirs(ckpt_dir, exist_ok=True)
     print(f"{host.n_impressions} impressions, {host.nbytes / 1e6:.1f} MB of tables on the device; a step uploads {8 * B} bytes of indices "
           f"instead of {B * (wl['H'] * dims.history_cols + wl['T'] * (dims.target_cols + 4)) * 8 / 1e6:.1f} MB of float64 rows")
     hist = trainer.train_epochs_tables(model, opt, dev, args.epochs, B, wl["H"], wl["T"], seed=args.seed, drop_last=True,
                                        ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"),
-                                       compact_history=args.compact_history, compact_candidates=args.compact_candidates)
+                                       compact_history=args.compact_history, compact_candidates=args.compact_candidates, graph=args.graph)
     for rec in hist:
-        print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec))
+        print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec)
+              + (" top1_avg={top1_avg:.4f} steps={n}".format(n=len(rec["step_loss"]), **rec) if args.graph else ""))
+        if args.graph and args.ckpt_dir:                                    # train.py:93-94: the epoch's per-step losses, one per line
+            with open(os.path.join(ckpt_dir, f"epoch_{rec['epoch']}.txt"), "w") as f:
+                f.writelines("{:.8f}\n".format(x) for x in rec["step_loss"])
     fresh = trainer.build_model(dims, user_num)
     evaluation.load_checkpoint(fresh, os.path.join(ckpt_dir, f"ckpt_synthetic_epoch_{args.epochs - 1}.pth"))
     batches = (b for i, b in enumerate(tables.TableLoader(dev, B, wl["H"], wl["T"], shuffle=False, drop_last=True)) if i < 4)

@@ -586,6 +586,27 @@ int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B
 /* the form nrm_assemble_batch writes rows in (the answer of the host function the launch switches on, no device call):
  * 4 = 16-byte units (8-byte units for float32 candidate rows), 1 = element by element; -1: bad arguments */
 int nrm_assemble_form(int static_cols, int S);
+/* The same kernel reading its impressions at a DEVICE-side cursor (additive; nrm_assemble_tables keeps its layout): impression b of the
+ * batch is order[*cursor + b], order [n_order] and cursor [1] on the device.  Nothing of the launch depends on host data but the
+ * pointers, so a captured launch assembles another batch at every replay once something on the stream moves the cursor
+ * (nrm_epoch_tally).  A position *cursor + b outside [0, n_order) is clamped into the range and sets err[0] = 1 like an entry outside
+ * the table: a replay past the end of an epoch writes clamped rows, is reported, and reads nothing outside order.  The cursor is read
+ * once per wave (a uniform load), no atomics.  nrm_assemble_batch(sel, B) is the case "no cursor, n_order = B".  n_order >= 1 where
+ * B > 0 (and below 2^62). */
+int nrm_assemble_batch_at(const nrm_assemble_tables* tables, const long* order, long n_order, const long* cursor, int B, int H, int T,
+                          int flags, nrm_stream_t stream);
+
+/* ---- the record of a table-fed epoch kept on the device (additive)
+ * One launch of ONE workgroup at the end of a step, in place of the epoch loop's per-step accumulations (reference train.py:77-94):
+ *   sums[0] += (double)*loss * B           train.py:82 total_loss += loss.item() * B  (one rounded product, one rounded sum: no fma)
+ *   sums[1] += sum of auc[b] >= 0,  counts[0] += rows with auc[b] < 0 (one class in the row),  sums[2] += sum of top1[b]
+ *   step_log[k] = {*loss, mean of the auc[b] >= 0 (0 without one)} with k = counts[1], unless k >= log_cap      train.py:83,93-94
+ *   counts[1] += 1,  *cursor += B
+ * auc / top1 [B] are the outputs of nrm_row_auc.  float64 accumulation in a fixed order (per-thread strided sums, a fixed shuffle
+ * tree, the wave partials in wave order), no atomics: the same bits from run to run.  All stores are plain stores of one lane.
+ * B = 0 launches nothing.  step_log may be null where log_cap = 0. */
+int nrm_epoch_tally(const float* loss, const float* auc, const int* top1, int B, long* cursor, double* sums, long* counts,
+                    float* step_log, long log_cap, nrm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@
 // straight copies of the aligned art_static row, the last one splices read time and scroll behind the type.  A padded row is written in full
 // as +0.0.  The candidate waves first find the source of slot T - 1 with one pass over the impression's list (ballots, no atomics).
 // Reads of art_static and all row stores go through bounded buffer descriptors; every index is clamped to its array before a plain load.
+// Which impression a wave works on is sel[b], or sel[*cursor + b] with a cursor that lives on the device (nrm_assemble_batch_at): that launch
+// depends on no host data, so a captured step assembles another batch at every replay (csrc/epoch.hip moves the cursor).
 #include <cstdint>
 #include <climits>
 #include "common.hpp"
@@ -130,8 +132,14 @@ __global__ __launch_bounds__(256) void assemble_kernel(const AssembleParams p) {
     const long item = (long)blockIdx.x * 4 + wave;
     if (item >= (long)p.B * per) return;
     const int b = (int)(item / per), w = (int)(item - (long)b * per);
-    long n = p.sel[b];
-    if (n < 0 || n >= t.N) {
+    // the impression's place in sel: b, or with a device-side cursor *cursor + b (one uniform load per wave: the pointer is a kernel
+    // argument).  The cursor is first brought into [-B, n_order] -- beyond either end every place of the batch is outside anyway, and
+    // the sum below cannot overflow -- then the place is clamped into sel and reported like an entry outside the table.
+    long pos = b;
+    if (p.cursor) pos += min(max(*p.cursor, -(long)p.B), p.n_order);
+    const bool off_end = pos < 0 || pos >= p.n_order;
+    long n = p.sel[min(max(pos, 0L), p.n_order - 1)];
+    if (off_end || n < 0 || n >= t.N) {
         if (lane == 0) *t.err = 1;
         n = min(max(n, 0L), t.N - 1);
     }
@@ -219,6 +227,7 @@ int assemble_form(int static_cols, int S) {
 
 hipError_t assemble_launch(const AssembleParams& p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
+    if (p.n_order < 1) return hipErrorInvalidValue;
     const long per = (p.H + ASM_ROWS - 1) / ASM_ROWS + (p.T + ASM_ROWS - 1) / ASM_ROWS;
     const long nblk = ((long)p.B * per + 3) / 4;
     if (nblk > 0x7fffffffL) return hipErrorInvalidValue;

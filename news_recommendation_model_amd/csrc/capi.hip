@@ -15,6 +15,7 @@
 #include "scoring.hpp"
 #include "compact.hpp"
 #include "assemble.hpp"
+#include "epoch.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -1009,31 +1010,51 @@ int nrm_frontend_cat_grad(const void* x0, int nrows0, int xcols0, const float* d
 
 int nrm_assemble_form(int static_cols, int S) { return nrm::assemble_form(static_cols, S); }
 
-int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B, int H, int T, int flags, nrm_stream_t stream) {
-    if (!tables) return fail(NRM_EINVAL, "nrm_assemble_batch: null table struct");
+// nrm_assemble_batch (no cursor, n_order = B) and nrm_assemble_batch_at: one validation, one launch
+static int assemble_entry(const char* who, const nrm_assemble_tables* tables, const long* sel, long n_order, const long* cursor, bool at, int B,
+                          int H, int T, int flags, nrm_stream_t stream) {
+    if (!tables) return fail(NRM_EINVAL, "%s: null table struct", who);
     const nrm_assemble_tables& t = *tables;
     if (B < 0 || H <= 0 || T <= 0 || (flags & ~NRM_ASSEMBLE_KEEP_TARGET_SLOT))
-        return fail(NRM_EINVAL, "nrm_assemble_batch: B=%d H=%d T=%d flags=%d (B >= 0, H, T > 0, flags 0 or NRM_ASSEMBLE_KEEP_TARGET_SLOT)", B, H, T, flags);
+        return fail(NRM_EINVAL, "%s: B=%d H=%d T=%d flags=%d (B >= 0, H, T > 0, flags 0 or NRM_ASSEMBLE_KEEP_TARGET_SLOT)", who, B, H, T, flags);
     if (B == 0) return NRM_OK;
+    if (at && (n_order < 1 || n_order >= (1L << 62))) return fail(NRM_EINVAL, "%s: n_order=%ld (1 <= n_order < 2^62 where B > 0)", who, n_order);
+    if (at && !cursor) return fail(NRM_EINVAL, "%s: null pointer (cursor)", who);
     const long sz = t.is_f64 ? 8 : 4;
     if (t.A < 1 || t.A >= (1L << 31) || t.U < 1 || t.U >= (1L << 31) || t.N < 1 || t.E < 0 || t.L < 0)
-        return fail(NRM_EINVAL, "nrm_assemble_batch: A=%ld U=%ld E=%ld N=%ld L=%ld (1 <= A, U < 2^31, N >= 1, E, L >= 0)", t.A, t.U, t.E, t.N, t.L);
+        return fail(NRM_EINVAL, "%s: A=%ld U=%ld E=%ld N=%ld L=%ld (1 <= A, U < 2^31, N >= 1, E, L >= 0)", who, t.A, t.U, t.E, t.N, t.L);
     if (t.static_cols < 1 || t.S != (t.static_cols + 3) / 4 * 4 || t.A * t.S * sz >= (1L << 32))
-        return fail(NRM_EINVAL, "nrm_assemble_batch: static_cols=%d S=%d A=%ld (S = static_cols rounded up to a multiple of 4; art_static below 2^32 bytes)",
-                    t.static_cols, t.S, t.A);
+        return fail(NRM_EINVAL, "%s: static_cols=%d S=%d A=%ld (S = static_cols rounded up to a multiple of 4; art_static below 2^32 bytes)",
+                    who, t.static_cols, t.S, t.A);
     const long hc = 4 + t.static_cols + 2, tc = 4 + t.static_cols;
     if ((long)H * hc * sz >= (1L << 31) || (long)T * tc * sz >= (1L << 31) || (long)B * T >= (1L << 31))
-        return fail(NRM_EINVAL, "nrm_assemble_batch: H=%d T=%d B=%d: the rows of one impression exceed 2^31 bytes (or B*T >= 2^31)", H, T, B);
+        return fail(NRM_EINVAL, "%s: H=%d T=%d B=%d: the rows of one impression exceed 2^31 bytes (or B*T >= 2^31)", who, H, T, B);
     if (!sel || !t.art_static || !t.art_global || !t.art_pub_us || !t.art_id || !t.user_off || !t.user_id || !t.imp_user || !t.imp_time_us ||
         !t.imp_off || !t.imp_target || !t.imp_id || (t.E > 0 && (!t.ev_art || !t.ev_time_us || !t.ev_read || !t.ev_scroll)) || (t.L > 0 && !t.imp_inview) ||
         !t.x_history || !t.x_target || !t.x_global || !t.label || !t.label_id || !t.empty_num || !t.user_id_out || !t.impression_id ||
         !t.history_len || !t.err)
-        return fail(NRM_EINVAL, "nrm_assemble_batch: null pointer");
+        return fail(NRM_EINVAL, "%s: null pointer", who);
     if (((uintptr_t)t.art_static | (uintptr_t)t.x_history | (uintptr_t)t.x_target) & 15)
-        return fail(NRM_EINVAL, "nrm_assemble_batch: art_static, x_history and x_target must be 16-byte aligned");
+        return fail(NRM_EINVAL, "%s: art_static, x_history and x_target must be 16-byte aligned", who);
     nrm::AssembleParams p;
-    p.t = t; p.sel = sel; p.B = B; p.H = H; p.T = T; p.keep_target_slot = (flags & NRM_ASSEMBLE_KEEP_TARGET_SLOT) ? 1 : 0;
+    p.t = t; p.sel = sel; p.cursor = cursor; p.n_order = n_order; p.B = B; p.H = H; p.T = T; p.keep_target_slot = (flags & NRM_ASSEMBLE_KEEP_TARGET_SLOT) ? 1 : 0;
     return check_hip(nrm::assemble_launch(p, (hipStream_t)stream), "assemble_batch");
+}
+
+int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B, int H, int T, int flags, nrm_stream_t stream) {
+    return assemble_entry("nrm_assemble_batch", tables, sel, B, nullptr, false, B, H, T, flags, stream);
+}
+
+int nrm_assemble_batch_at(const nrm_assemble_tables* tables, const long* order, long n_order, const long* cursor, int B, int H, int T,
+                          int flags, nrm_stream_t stream) {
+    return assemble_entry("nrm_assemble_batch_at", tables, order, n_order, cursor, true, B, H, T, flags, stream);
+}
+
+int nrm_epoch_tally(const float* loss, const float* auc, const int* top1, int B, long* cursor, double* sums, long* counts,
+                    float* step_log, long log_cap, nrm_stream_t stream) {
+    if (B < 0 || log_cap < 0) return fail(NRM_EINVAL, "nrm_epoch_tally: B=%d log_cap=%ld (both >= 0)", B, log_cap);
+    if (!loss || !auc || !top1 || !cursor || !sums || !counts || (log_cap > 0 && !step_log)) return fail(NRM_EINVAL, "nrm_epoch_tally: null pointer");
+    return check_hip(nrm::epoch_tally_launch(loss, auc, top1, B, cursor, sums, counts, step_log, log_cap, (hipStream_t)stream), "epoch_tally");
 }
 
 }  // extern "C"

@@ -90,6 +90,8 @@ SIGNATURES = {
     "nrm_ensemble_rank_ragged": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i] + [_c_fp] * 5),     # the first two: HOST arrays
     "nrm_assemble_batch": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),       # the first: a HOST struct (AssembleTables), by pointer
     "nrm_assemble_form": (_c_i, [_c_i, _c_i]),
+    "nrm_assemble_batch_at": (_c_i, [_c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),      # the first: the same HOST struct
+    "nrm_epoch_tally": (_c_i, [_c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp]),
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,
                                  _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp]),

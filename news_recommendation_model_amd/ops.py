@@ -2702,12 +2702,10 @@ def _assemble_outputs(like, ft, B, H, T, hc, tc):
             new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int32))
 
 
-def _assemble_batch_impl(tables, sel, H, T, keep_target_slot, static_cols):
-    """The processed records of the impressions ``sel`` written from device-resident tables by ONE kernel -> (x_history [B, H, hc],
-    x_target [B, T, tc], x_global [B, T, 3] in the tables' floating type, label [B, T] float64, label_id [B, T], empty_num [B], user_id [B],
-    impression_id [B] int64, history_len [B] int32): reference tool/process_data.py:190-252 (batch_type 0 with ``keep_target_slot``, else 2)."""
-    _require_gpu(*tables, sel)
-    ft, B, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
+def _assemble_launch(who, tables, sel, cursor, B, H, T, keep_target_slot, static_cols):
+    """assemble_batch (``cursor`` None: impression b is sel[b]) and assemble_batch_at (impression b is sel[cursor[0] + b]): one launch."""
+    _require_gpu(*tables, sel, cursor)
+    ft, _, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
     outs = _assemble_outputs(sel, ft, B, H, T, hc, tc)
     if B == 0:
         return outs
@@ -2717,7 +2715,7 @@ def _assemble_batch_impl(tables, sel, H, T, keep_target_slot, static_cols):
     if (art_static.dim() != 2 or tuple(art_global.shape) != (A, 3) or tuple(art_pub.shape) != (A,) or tuple(art_id.shape) != (A,)
             or tuple(user_off.shape) != (U + 1,) or any(tuple(t.shape) != (E,) for t in (ev_time, ev_read, ev_scroll))
             or any(tuple(t.shape) != (N,) for t in (imp_time, imp_target, imp_id)) or tuple(imp_off.shape) != (N + 1,)):
-        raise RuntimeError("assemble_batch: the tables do not agree in their sizes (tables.ImpressionTables.validate)")
+        raise RuntimeError(f"{who}: the tables do not agree in their sizes (tables.ImpressionTables.validate)")
     d = native.AssembleTables()
     for name, t in zip(("art_static", "art_global", "art_pub_us", "art_id", "user_off", "ev_art", "ev_time_us", "ev_read", "ev_scroll", "user_id",
                         "imp_user", "imp_time_us", "imp_off", "imp_inview", "imp_target", "imp_id"), tables):
@@ -2728,9 +2726,19 @@ def _assemble_batch_impl(tables, sel, H, T, keep_target_slot, static_cols):
         setattr(d, name, t.data_ptr())
     d.err = index_error_flag(sel.device).data_ptr()
     import ctypes
-    native.call("nrm_assemble_batch", ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), native.ptr(sel.contiguous()), B, int(H), int(T),
-                1 if keep_target_slot else 0, native.stream_ptr())
+    tabs, flags = ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), 1 if keep_target_slot else 0
+    if cursor is None:
+        native.call("nrm_assemble_batch", tabs, native.ptr(sel.contiguous()), B, int(H), int(T), flags, native.stream_ptr())
+    else:
+        native.call("nrm_assemble_batch_at", tabs, native.ptr(sel), sel.shape[0], native.ptr(cursor), B, int(H), int(T), flags, native.stream_ptr())
     return outs
+
+
+def _assemble_batch_impl(tables, sel, H, T, keep_target_slot, static_cols):
+    """The processed records of the impressions ``sel`` written from device-resident tables by ONE kernel -> (x_history [B, H, hc],
+    x_target [B, T, tc], x_global [B, T, 3] in the tables' floating type, label [B, T] float64, label_id [B, T], empty_num [B], user_id [B],
+    impression_id [B] int64, history_len [B] int32): reference tool/process_data.py:190-252 (batch_type 0 with ``keep_target_slot``, else 2)."""
+    return _assemble_launch("assemble_batch", tables, sel, None, sel.shape[0] if sel.dim() == 1 else 0, H, T, keep_target_slot, static_cols)
 
 
 def _assemble_batch_fake(tables, sel, H, T, keep_target_slot, static_cols):
@@ -2740,6 +2748,65 @@ def _assemble_batch_fake(tables, sel, H, T, keep_target_slot, static_cols):
 
 assemble_batch = _op("assemble_batch", "(Tensor[] tables, Tensor sel, int H, int T, bool keep_target_slot, int static_cols) -> "
                      "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _assemble_batch_impl, _assemble_batch_fake)
+
+
+def _assemble_at_check(order, cursor, B):
+    if (order.dim() != 1 or order.dtype != torch.int64 or not order.is_contiguous() or cursor.dtype != torch.int64 or cursor.numel() != 1
+            or not cursor.is_contiguous() or B < 0 or (B > 0 and order.shape[0] < 1)):
+        raise RuntimeError(f"assemble_batch_at: order {tuple(order.shape)} {order.dtype}, cursor {tuple(cursor.shape)} {cursor.dtype}, B={B} (order is a "
+                           "contiguous 1-D int64 tensor with at least one entry, cursor one int64 element on the device, B >= 0)")
+
+
+def _assemble_batch_at_impl(tables, order, cursor, B, H, T, keep_target_slot, static_cols):
+    """``assemble_batch`` for the ``B`` impressions order[cursor[0] .. cursor[0] + B): the cursor is read ON THE DEVICE, so the launch depends
+    on no host data and may be captured -- the nine outputs then come from the capture's pool and are the graph's static batch, rewritten
+    by every replay for wherever ``epoch_tally`` has moved the cursor.  A position outside ``order`` is clamped and raises the index flag."""
+    _assemble_at_check(order, cursor, B)
+    return _assemble_launch("assemble_batch_at", tables, order, cursor, int(B), H, T, keep_target_slot, static_cols)
+
+
+def _assemble_batch_at_fake(tables, order, cursor, B, H, T, keep_target_slot, static_cols):
+    _assemble_at_check(order, cursor, B)
+    ft, _, hc, tc = _assemble_shapes(tables, order, H, T, static_cols)
+    return _assemble_outputs(order, ft, B, H, T, hc, tc)
+
+
+assemble_batch_at = _op("assemble_batch_at", "(Tensor[] tables, Tensor order, Tensor cursor, int B, int H, int T, bool keep_target_slot, "
+                        "int static_cols) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+                        _assemble_batch_at_impl, _assemble_batch_at_fake)
+
+
+# ---- the record of a table-fed epoch on the device (DESIGN.md section 5g)
+def _epoch_tally_check(loss, auc, top1, cursor, sums, counts, step_log):
+    B = auc.shape[0] if auc.dim() == 1 else -1
+    if (loss.numel() != 1 or loss.dtype != torch.float32 or B < 0 or auc.dtype != torch.float32 or tuple(top1.shape) != (B,)
+            or top1.dtype != torch.int32 or cursor.numel() != 1 or cursor.dtype != torch.int64 or tuple(sums.shape) != (3,)
+            or sums.dtype != torch.float64 or tuple(counts.shape) != (2,) or counts.dtype != torch.int64 or step_log.dim() != 2
+            or step_log.shape[1] != 2 or step_log.dtype != torch.float32
+            or not all(t.is_contiguous() for t in (auc, top1, cursor, sums, counts, step_log))):
+        raise RuntimeError(f"epoch_tally: loss {tuple(loss.shape)} {loss.dtype}, auc {tuple(auc.shape)} {auc.dtype}, top1 {tuple(top1.shape)} {top1.dtype}, "
+                           f"cursor {tuple(cursor.shape)} {cursor.dtype}, sums {tuple(sums.shape)} {sums.dtype}, counts {tuple(counts.shape)} {counts.dtype}, "
+                           f"step_log {tuple(step_log.shape)} {step_log.dtype}: expected one float32, [B] float32, [B] int32, one int64, [3] float64, "
+                           "[2] int64, [log_cap, 2] float32, all contiguous")
+    return B
+
+
+def _epoch_tally_impl(loss, auc, top1, cursor, sums, counts, step_log):
+    """One launch at the end of a step (C ABI nrm_epoch_tally): sums += {loss * B, the defined row AUCs, the top-1 hits}, counts += {one-class
+    rows, 1}, step_log[counts[1]] = {loss, the step's mean AUC} while there is room, cursor += B.  ``auc`` / ``top1``: the outputs of
+    ``row_auc``.  float64, fixed order, no atomics."""
+    _require_gpu(loss, auc, top1, cursor, sums, counts, step_log)
+    B = _epoch_tally_check(loss, auc, top1, cursor, sums, counts, step_log)
+    native.call("nrm_epoch_tally", native.ptr(loss), native.ptr(auc), native.ptr(top1), B, native.ptr(cursor), native.ptr(sums), native.ptr(counts),
+                native.ptr(step_log) if step_log.shape[0] else None, step_log.shape[0], native.stream_ptr())
+
+
+def _epoch_tally_fake(loss, auc, top1, cursor, sums, counts, step_log):
+    _epoch_tally_check(loss, auc, top1, cursor, sums, counts, step_log)
+
+
+epoch_tally = _op("epoch_tally", "(Tensor loss, Tensor auc, Tensor top1, Tensor(a!) cursor, Tensor(b!) sums, Tensor(c!) counts, "
+                  "Tensor(d!) step_log) -> ()", _epoch_tally_impl, _epoch_tally_fake)
 
 
 def _history_gather_impl(x_history, hist_off, R, k_max):
@@ -2890,4 +2957,4 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
        "candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
        "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
-       "assemble_batch", "adam_step")
+       "assemble_batch", "assemble_batch_at", "epoch_tally", "adam_step")

@@ -409,12 +409,26 @@ def assemble_batch(tables: ImpressionTables, sel, H, T, keep_target_slot=True):
     """The same dict on the device: ONE launch of the assemble kernel on the current stream, from device-resident tables
     (``tables.to('cuda')``) and ``sel`` (an int64 device tensor of impression indices; repeats and any order are fine).  The three x
     tensors have the tables' floating type.  An index of ``sel`` outside the table is clamped and raises the device index flag
-    (``ops.check_index_errors``).  Eager only."""
+    (``ops.check_index_errors``).  ``sel`` is read by the launch, not by a replay: the form that can be captured is ``assemble_batch_at``."""
     from . import ops
     if not tables.is_device:
         raise RuntimeError("assemble_batch: the tables are host arrays; upload them once with tables.to('cuda') "
                            "(the host statement of the same rows is assemble_host)")
     out = ops.assemble_batch([getattr(tables, name) for name in TABLE_FIELDS], sel, int(H), int(T), bool(keep_target_slot), int(tables.static_cols))
+    return dict(zip(BATCH_KEYS, out))
+
+
+def assemble_batch_at(tables: ImpressionTables, order, cursor, B, H, T, keep_target_slot=True):
+    """``assemble_batch`` for the ``B`` impressions ``order[cursor[0] : cursor[0] + B]``, with ``order`` (int64 [n]) AND ``cursor`` (one int64)
+    on the device: the launch reads no host data, so it may sit inside a stream capture -- the returned tensors are then the graph's
+    static batch, rewritten by every replay for wherever the cursor stands (``trainer.GraphedTableEpoch``).  A position outside ``order`` is
+    clamped into it and raises the device index flag like an index outside the table."""
+    from . import ops
+    if not tables.is_device:
+        raise RuntimeError("assemble_batch_at: the tables are host arrays; upload them once with tables.to('cuda') "
+                           "(the host statement of the same rows is assemble_host)")
+    out = ops.assemble_batch_at([getattr(tables, name) for name in TABLE_FIELDS], order, cursor, int(B), int(H), int(T), bool(keep_target_slot),
+                                int(tables.static_cols))
     return dict(zip(BATCH_KEYS, out))
 
 
@@ -445,10 +459,15 @@ class TableLoader:
             self._next_order = self.rng.permutation(n) if self.shuffle else np.arange(n)
         return self._next_order
 
+    def take_order(self):
+        """The coming epoch's order, consumed: the next call draws the next permutation (what ``__iter__`` starts with)."""
+        order, self._next_order = self.order(), None
+        return order
+
     def __iter__(self):
         import torch
         from . import trainer
-        order, self._next_order = self.order(), None
+        order = self.take_order()
         dev = self.tables.art_static.device
         for i in range(len(self)):
             sel = np.ascontiguousarray(order[i * self.batch_size:(i + 1) * self.batch_size], dtype=np.int64)

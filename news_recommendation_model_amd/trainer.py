@@ -544,6 +544,149 @@ class GraphedTrainStep:
         return self.loss, self.out
 
 
+class GraphedTableEpoch:
+    """A table-fed epoch whose steady state is ONE graph replay per step: no upload, no other launch from the host
+    and no host synchronisation until the epoch ends.
+
+    The captured step is ``assemble_batch_at`` -> ``train_step`` -> ``row_auc`` -> ``epoch_tally``.  The assemble kernel reads its
+    impressions at a cursor that lives on the device and the tally moves that cursor by B at the end of the step, so a replay knows which
+    batch it is on without the host telling it; the tally also keeps what the eager epoch loops accumulate with ATen launches per step --
+    loss * B, the row AUCs, the one-class rows, the per-step loss list of reference train.py:82-94 -- in one packed state buffer that
+    the host reads ONCE per epoch.  ``order`` ([N] int64) stays at one address and is refilled in place by ``begin_epoch``.
+
+    Every impression is consumed exactly once and an epoch applies exactly ceil(N / B) optimizer steps (floor with ``drop_last``): the
+    allocator warm-up ``GraphedTrainStep`` spends three throwaway steps on is here the first ``warmup`` batches of the FIRST epoch, run
+    eagerly through the same ops (cursor and tally stay consistent); then the step is captured -- a capture executes nothing -- and every
+    further full batch is a replay.  A last partial batch runs eagerly through the same ops at its own size, so BatchNorm sees the batch
+    the eager loop sees.  The learning rate and ``alpha`` are kernel arguments baked into a capture: ``begin_epoch`` re-reads
+    ``param_groups[0]['lr']`` as train.py:57 does, and a step whose rate or ``alpha`` differs from the captured one captures again (no
+    warm-up steps then: the allocator is warm).  ``warmup >= 1``: capturing a model that has never run would put every lazy
+    initialisation of a first step inside the capture."""
+
+    def __init__(self, model, optimizer, tables, batch_size, H, T, keep_target_slot=True, alpha=0.95, warmup=3, compact_history=False,
+                 compact_candidates=False):
+        if compact_history:
+            raise RuntimeError("GraphedTableEpoch(compact_history=True): the length groups are planned on the host for every batch; a "
+                               "captured step replays one fixed sequence of launches.  Capture the dense step, or run the eager loop "
+                               "(train_epochs_tables(graph=False))")
+        if compact_candidates:
+            raise RuntimeError("GraphedTableEpoch(compact_candidates=True): the candidate groups are planned on the host for every batch; a "
+                               "captured step replays one fixed sequence of launches.  Capture the dense step, or run the eager loop "
+                               "(train_epochs_tables(graph=False))")
+        if not isinstance(optimizer, FlatAdam):
+            raise TypeError("GraphedTableEpoch needs trainer.FlatAdam (its step counter lives on the device)")
+        from . import native, ops
+        if native.kernel_events is not None:
+            raise RuntimeError("per-kernel event timing cannot be recorded inside a graph capture")
+        if dist.is_available() and dist.is_initialized():
+            raise RuntimeError("GraphedTableEpoch: a process group is initialised; sharding the tables' impressions over ranks is not built "
+                               "(every rank would train the whole epoch).  Run it in a process without a group")
+        if int(warmup) < 1:
+            raise ValueError(f"GraphedTableEpoch(warmup={warmup}): at least one eager step comes before the capture (a model that has never "
+                             "run would do its lazy initialisation inside the capture)")
+        if int(batch_size) < 1:
+            raise ValueError(f"GraphedTableEpoch(batch_size={batch_size})")
+        from .tables import TABLE_FIELDS
+        dev = optimizer.flat_param.device
+        self.model, self.optimizer = model, optimizer
+        self.tables = tables if tables.is_device else tables.to(dev)
+        self._tabs = [getattr(self.tables, name) for name in TABLE_FIELDS]
+        self.batch_size, self.H, self.T, self.keep_target_slot = int(batch_size), int(H), int(T), bool(keep_target_slot)
+        self.alpha, self.warmup = float(alpha), int(warmup)
+        self.N = self.tables.n_impressions
+        if self.N < 1:
+            raise ValueError("GraphedTableEpoch: the tables hold no impression")
+        self.order = torch.zeros(self.N, dtype=torch.int64, device=dev)
+        self._order_host = torch.zeros(self.N, dtype=torch.int64).pin_memory()
+        # ONE buffer of 8-byte words, read once per epoch: cursor | sums [3] float64 | counts [2] | step log [log_cap, 2] float32
+        self.log_cap = (self.N + self.batch_size - 1) // self.batch_size
+        self.state = torch.zeros(6 + self.log_cap, dtype=torch.int64, device=dev)
+        self.cursor, self.counts = self.state[0:1], self.state[4:6]
+        self.sums = self.state[1:4].view(torch.float64)
+        self.step_log = self.state[6:].view(torch.float32).view(self.log_cap, 2)
+        ops.index_error_flag(dev)                           # (pinned: allocated before any capture)
+        self.graph, self.captured = None, None              # captured: the (lr, alpha) inside the graph
+        self.batch = self.loss = self.out = None            # of the latest step; after a replay: the graph's static tensors
+        self.lr = float(optimizer.param_groups[0]["lr"])
+        self.steps_in_epoch = self.eager_steps = self.replays = self.captures = 0
+        self._warm = 0
+
+    def begin_epoch(self, order):
+        """``order``: this epoch's impression order (host, [N]); copied into the device buffer in place, state zeroed, rate re-read."""
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        if order.shape != (self.N,):
+            raise ValueError(f"GraphedTableEpoch.begin_epoch: order {order.shape} for {self.N} impressions")
+        self.model.train()
+        self.lr = float(self.optimizer.param_groups[0]["lr"])
+        self._order_host.copy_(torch.from_numpy(order))
+        self.order.copy_(self._order_host, non_blocking=True)
+        self.state.zero_()
+        self.steps_in_epoch = 0
+
+    def _step_ops(self, n):
+        """one step of ``n`` impressions at the cursor: the SAME four ops eagerly and inside the capture"""
+        from . import ops
+        from .tables import BATCH_KEYS
+        batch = dict(zip(BATCH_KEYS, ops.assemble_batch_at(self._tabs, self.order, self.cursor, n, self.H, self.T, self.keep_target_slot,
+                                                           int(self.tables.static_cols))))
+        loss, out = train_step(self.model, self.optimizer, batch, None, self.alpha)
+        auc, top1 = ops.row_auc(out, batch["label"], None)
+        ops.epoch_tally(loss, auc, top1, self.cursor, self.sums, self.counts, self.step_log)
+        return batch, loss, out
+
+    def _capture(self):
+        self.graph = self._static = None                    # a stale graph and its pool go first
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._static = self._step_ops(self.batch_size)
+        self.graph, self.captured = graph, (self.lr, self.alpha)
+        self.captures += 1
+
+    def step(self, n=None):
+        """The epoch's next step (``n`` impressions; None: a full batch, or what is left of the epoch) -> (loss, out) of it, device tensors
+        that the next step may overwrite."""
+        left = self.N - self.steps_in_epoch * self.batch_size
+        n = min(self.batch_size, left) if n is None else int(n)
+        if n < 1 or n > min(left, self.batch_size):
+            raise RuntimeError(f"GraphedTableEpoch.step: {n} impressions asked for, {max(left, 0)} left in the epoch and at most {self.batch_size} "
+                               "in a step (begin_epoch starts the next epoch)")
+        if n < self.batch_size or self._warm < self.warmup:
+            self.batch, self.loss, self.out = self._step_ops(n)            # (train_step watches the index flag itself)
+            self._warm += n == self.batch_size
+            self.eager_steps += 1
+        else:
+            if self.graph is None or self.captured != (self.lr, self.alpha):
+                self._capture()
+            watch = _index_watch(self.order.device)
+            watch.before_step()                              # an out-of-range id of an earlier replay raises IndexError here
+            self.graph.replay()
+            watch.after_step()
+            self.batch, self.loss, self.out = self._static
+            self.replays += 1
+        self.steps_in_epoch += 1
+        return self.loss, self.out
+
+    def end_epoch(self):
+        """The epoch's ONE host read -> dict(impressions, steps, loss_sum, auc_sum, top1_sum, one_class_rows, step_loss, step_auc); an
+        out-of-range index of any step raises IndexError here at the latest."""
+        from . import ops
+        host = self.state.cpu()                              # (waits for the stream)
+        ops.check_index_errors(self.order.device)
+        sums, steps = host[1:4].view(torch.float64), int(host[5])
+        log = host[6:].view(torch.float32).view(self.log_cap, 2)[:min(steps, self.log_cap)]
+        return {"impressions": int(host[0]), "steps": steps, "loss_sum": float(sums[0]), "auc_sum": float(sums[1]), "top1_sum": float(sums[2]),
+                "one_class_rows": int(host[4]), "step_loss": log[:, 0].tolist(), "step_auc": log[:, 1].tolist()}
+
+    def run_epoch(self, order, drop_last=False):
+        """``begin_epoch``, every step, ``end_epoch``."""
+        self.begin_epoch(order)
+        for _ in range(self.N // self.batch_size):
+            self.step()
+        if self.N % self.batch_size and not drop_last:
+            self.step()
+        return self.end_epoch()
+
+
 def shard_batch(batch, rank, world):
     """Rank ``rank`` of ``world`` takes a contiguous 1/world slice of the impressions."""
     B = batch["user_id"].shape[0]
@@ -696,14 +839,41 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
 
 
 def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuffle=True, seed=0, keep_target_slot=True, device="cuda",
-                        ckpt_path=None, on_batch=None, compact_history=False, max_groups=None, compact_candidates=False, drop_last=False):
+                        ckpt_path=None, on_batch=None, compact_history=False, max_groups=None, compact_candidates=False, drop_last=False,
+                        graph=False, graph_warmup=3):
     """``train_epochs`` over a data set that lives on the device as ``tables.ImpressionTables``: every batch is
     written by the assemble kernel from a few KB of impression indices instead of being uploaded, on the current stream, and carries its
     producer's history lengths and ``empty_num`` on the host, so ``compact_history`` / ``compact_candidates`` plan without a measuring
     kernel or a synchronise.  The per-epoch record, the checkpoints and the index and padding checks are ``train_epochs``'s.  ``tables``:
-    host tables (uploaded once) or device tables."""
+    host tables (uploaded once) or device tables.
+    ``graph=True``: the epochs run through a ``GraphedTableEpoch`` -- after ``graph_warmup`` eager steps every full batch is one graph
+    replay, and the host reads the device once per epoch.  The permutations are the eager loop's (the same ``TableLoader`` generator: one
+    seed, the same impressions in the same order).  The record gains ``step_loss`` / ``step_auc`` (per step, from the device log) and
+    ``top1_avg``; ``on_batch`` is refused (a call per step would need a synchronise per step), and so is everything a captured step
+    cannot do (``GraphedTableEpoch``)."""
     from . import evaluation, ops
     from .tables import TableLoader
+    if graph:
+        if on_batch is not None:
+            raise RuntimeError("train_epochs_tables(graph=True, on_batch=...): a call per step would need a host synchronise per step, which is "
+                               "what the captured epoch removes; the per-step figures are in the record as step_loss and step_auc")
+        runner = GraphedTableEpoch(model, optimizer, tables, batch_size, H, T, keep_target_slot=keep_target_slot, warmup=graph_warmup,
+                                   compact_history=compact_history, compact_candidates=compact_candidates)
+        loader = TableLoader(runner.tables, batch_size, H, T, shuffle=shuffle, seed=seed, keep_target_slot=keep_target_slot, device=device,
+                             drop_last=drop_last)
+        history = []
+        for epoch in range(epochs):
+            lr = optimizer.param_groups[0]["lr"]
+            got = runner.run_epoch(loader.take_order(), drop_last=drop_last)
+            if got["one_class_rows"]:
+                raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+            seen = got["impressions"]
+            history.append({"epoch": epoch, "lr": lr, "impressions": seen, "loss_avg": got["loss_sum"] / max(seen, 1),
+                            "auc_avg": got["auc_sum"] / max(seen, 1), "top1_avg": got["top1_sum"] / max(seen, 1),
+                            "step_loss": got["step_loss"], "step_auc": got["step_auc"]})
+            if ckpt_path is not None:
+                evaluation.save_checkpoint(model, ckpt_path.format(epoch=epoch))
+        return history
     loader = TableLoader(tables, batch_size, H, T, shuffle=shuffle, seed=seed, keep_target_slot=keep_target_slot, device=device, drop_last=drop_last)
     history = []
     for epoch in range(epochs):
