@@ -546,7 +546,10 @@ hipError_t loss_wlast_launch(const float* out, int out_stride, const void* label
 // gradient, bias-corrected, eps added after the sqrt).  Also zeroes the gradient (optimizer.zero_grad()).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n, float lr, float b1, float b2,
-                                                   float eps, float wd, float bc1, float bc2_sqrt, int zero_grad) {
+                                                   float eps, float wd, float step, int zero_grad) {
+    // the bias corrections with adam_prep_kernel's expression and the device's powf: formed on the host they differed from
+    // the device-side state in the last bit (1 - b1^3 at b1 = 0.9), and the two entries did not give the same parameters
+    const float bc1 = 1.0f - powf(b1, step), bc2_sqrt = sqrtf(1.0f - powf(b2, step));
     const long n4 = n >> 2;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<f32x4*>(g)[i];
@@ -637,8 +640,7 @@ static unsigned adam_blocks(long n) {
 hipError_t adam_launch(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                        float wd, int step, int zero_grad, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(adam_blocks(n)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, zero_grad);
+    hipLaunchKernelGGL(adam_kernel, dim3(adam_blocks(n)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, (float)step, zero_grad);
     return hipGetLastError();
 }
 
