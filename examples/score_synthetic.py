@@ -6,6 +6,7 @@ ensemble of two seeded models -- forwards, then ONE launch for softmax / mean / 
     python examples/score_synthetic.py --impressions 200 --batch 80
     python examples/score_synthetic.py --compact      (no forward work on padded candidates: evaluation.predict_ranked_compact)
     python examples/score_synthetic.py --compact-history      (nor on padded history rows: predict_ranked_compact(history=True))
+    python examples/score_synthetic.py --from-tables      (the test set lives on the device as tables: one graph replay per batch)
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from news_recommendation_model_amd import data_io, evaluation, synth, trainer  # noqa: E402
+from news_recommendation_model_amd import data_io, evaluation, synth, tables, trainer  # noqa: E402
 from news_recommendation_model_amd.config import Dims                          # noqa: E402
 
 
@@ -32,13 +33,30 @@ def main():
     ap.add_argument("--compact", action="store_true", help="score ragged lists: live candidates + one representative padded candidate per impression")
     ap.add_argument("--compact-history", action="store_true",
                     help="--compact, and drop the trailing all-zero history rows as well (one representative padded history row per impression)")
+    ap.add_argument("--from-tables", action="store_true",
+                    help="keep the unlabelled test set on the device as index-based tables (raw synthetic records through "
+                         "tables.ImpressionTables) and score it through evaluation.score_tables: every full batch is ONE replay of a captured "
+                         "step, the ranks stay in a device record and the host reads it once per --record-rows impressions")
+    ap.add_argument("--record-rows", type=int, default=None, help="with --from-tables: impressions per drain of the device record (a multiple "
+                                                                  "of --batch; default: the whole pass, one host read)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
+    if args.from_tables and (args.compact or args.compact_history):
+        raise SystemExit("--from-tables captures the dense pass; the compact forms are planned on the host for every batch")
     dims = Dims.for_emb(args.emb, category_label_num=50)
     N, T = args.impressions, args.candidates
     user_num = max(10, N // 4)
     out_dir = args.out_dir or tempfile.mkdtemp(prefix="nrm_score_")
+    if args.from_tables:
+        # batch_type 2 of the reference's ETL: no labels, T = the longest in-view list, the first T entries of every list
+        recs = synth.make_records(dims, 512, user_num, N, seed=0, labelled=False, max_history=2 * args.history,
+                                  list_lens=np.random.default_rng(1).integers(T // 2, T + 1, N))
+        host = tables.ImpressionTables.from_records(*recs, dims, history_max=args.history)
+        models = [trainer.build_model(dims, host.max_user_id + 1, synth.make_state_dict(dims, seed=s, user_num=host.max_user_id + 1)) for s in (1, 5)]
+        zip_path = evaluation.score_tables(models, host.to("cuda"), out_dir, batch_size=args.batch, H=args.history,
+                                           T=int(np.diff(host.imp_off).max()), record_rows=args.record_rows)
+        return show(zip_path, host.n_impressions)
     # a processed test set: impressions with 0 .. T/2 trailing padding candidates (all-zero rows, counted in empty_num)
     batch = synth.make_batch(dims, N, args.history, T, seed=0, user_num=user_num)
     rng = np.random.default_rng(1)
@@ -53,6 +71,10 @@ def main():
     models = [trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=s, user_num=user_num)) for s in (1, 5)]
     # the one-line replacement of test.py's model_test + write_submission_file:
     zip_path = evaluation.score_dataset(models, head, out_dir, batch_size=args.batch, compact=args.compact, compact_history=args.compact_history)
+    show(zip_path, N)
+
+
+def show(zip_path, N):
     with zipfile.ZipFile(zip_path) as z:
         lines = z.read("predictions.txt").decode("utf-8").splitlines()
     assert len(lines) == N

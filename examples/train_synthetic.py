@@ -8,6 +8,7 @@ launch), host float64 batches staged one ahead, per-impression AUC on the device
     python examples/train_synthetic.py --workload ref-default --compact-candidates --candidate-counts percentile    (section 5f)
     python examples/train_synthetic.py --workload ref-default --from-tables --compact-history --compact-candidates    (section 5g)
     python examples/train_synthetic.py --workload ref-default --from-tables --graph --batches 100     (section 5g: one graph replay per step)
+    python examples/train_synthetic.py --workload ref-default --from-tables --graph --validate     (section 5h: validation after every epoch)
 """
 import argparse
 import os
@@ -48,9 +49,15 @@ def main():
                     help="with --from-tables: after three eager steps every full batch is ONE replay of a captured step that assembles its own "
                          "batch at a device-side cursor (trainer.GraphedTableEpoch); the host reads the device once per epoch.  With --ckpt-dir "
                          "the per-step losses of every epoch are written as the reference writes them (train.py:93-94)")
+    ap.add_argument("--validate", action="store_true",
+                    help="with --from-tables: a second set of synthetic records is kept on the device as validation tables and scored after "
+                         "every epoch in batches of 80 (train.py:107-110), through one captured pass where --graph is given "
+                         "(evaluation.GraphedTableScoring); the epoch line is then the reference's")
     args = ap.parse_args()
     if args.graph and not args.from_tables:
         raise SystemExit("--graph captures the table-fed epoch: use it with --from-tables")
+    if args.validate and not args.from_tables:
+        raise SystemExit("--validate scores validation TABLES: use it with --from-tables")
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X: the Modules have no CPU path")
     wl = WORKLOADS[args.workload]
@@ -105,11 +112,14 @@ def main_from_tables(args, wl, B, dims):
     """The same driver with the data resident on the device: raw records -> tables (once) -> one assemble launch per step."""
     rng = np.random.default_rng(args.seed)
     n = args.batches * B
+    n_val = max(n // 5, 80) if args.validate else 0                         # the validation set: further impressions of the same users
     n_users = max(n // 4, 8)
-    recs = synth.make_records(dims, 4096, n_users, n, seed=args.seed, history_lens=rng.integers(0, wl["H"] + 20, n_users),
-                              list_lens=np.clip(rng.geometric(1.0 / (0.7 * wl["T"]), n), 2, 3 * wl["T"]))
-    host = tables.ImpressionTables.from_records(*recs, dims, history_max=wl["H"])
+    recs = synth.make_records(dims, 4096, n_users, n + n_val, seed=args.seed, history_lens=rng.integers(0, wl["H"] + 20, n_users),
+                              list_lens=np.clip(rng.geometric(1.0 / (0.7 * wl["T"]), n + n_val), 2, 3 * wl["T"]))
+    part = lambda lo, hi: {k: v[lo:hi] for k, v in recs[2].items()}      # noqa: E731
+    host = tables.ImpressionTables.from_records(recs[0], recs[1], part(0, n), dims, history_max=wl["H"])
     dev = host.to("cuda")
+    validation = tables.ImpressionTables.from_records(recs[0], recs[1], part(n, n + n_val), dims, history_max=wl["H"]).to("cuda") if n_val else None
     user_num = host.max_user_id + 1
     torch.manual_seed(args.seed)
     model = trainer.build_model(dims, user_num, synth.make_state_dict(dims, seed=args.seed + 1, user_num=user_num))
@@ -120,8 +130,12 @@ def main_from_tables(args, wl, B, dims):
           f"instead of {B * (wl['H'] * dims.history_cols + wl['T'] * (dims.target_cols + 4)) * 8 / 1e6:.1f} MB of float64 rows")
     hist = trainer.train_epochs_tables(model, opt, dev, args.epochs, B, wl["H"], wl["T"], seed=args.seed, drop_last=True,
                                        ckpt_path=os.path.join(ckpt_dir, "ckpt_synthetic_epoch_{epoch}.pth"),
-                                       compact_history=args.compact_history, compact_candidates=args.compact_candidates, graph=args.graph)
+                                       compact_history=args.compact_history, compact_candidates=args.compact_candidates, graph=args.graph,
+                                       validation=validation)
     for rec in hist:
+        if args.validate:                                                   # train.py:110
+            print("[epoch]:{epoch} [avg_loss]:{loss_avg:.3e} [auc_score_t]:{auc_avg:.4f} [TPR_v]:{val_top1:.4f} [auc_score_v]:{val_auc:.4f}"
+                  .format(**rec))
         print("[epoch]:{epoch} [lr]:{lr:.3e} loss_avg={loss_avg:.4f} auc_avg={auc_avg:.4f} impressions={impressions}".format(**rec)
               + (" top1_avg={top1_avg:.4f} steps={n}".format(n=len(rec["step_loss"]), **rec) if args.graph else ""))
         if args.graph and args.ckpt_dir:                                    # train.py:93-94: the epoch's per-step losses, one per line

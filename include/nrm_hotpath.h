@@ -608,6 +608,24 @@ int nrm_assemble_batch_at(const nrm_assemble_tables* tables, const long* order, 
 int nrm_epoch_tally(const float* loss, const float* auc, const int* top1, int B, long* cursor, double* sums, long* counts,
                     float* step_log, long log_cap, nrm_stream_t stream);
 
+/* ---- the record of a table-fed evaluation pass kept on the device (additive, the ABI version is unchanged)
+ * One launch of ONE workgroup at the end of an evaluation step of B impressions whose scoring tail ran at width Tp (1 <= Tp <= T), in
+ * place of the per-batch sums of reference verify.py:25-43 and the per-batch device-to-host copy of test.py:118-130:
+ *   row b of the step is position p = *cursor + b of the pass; rows with p outside [0, n_order) are neither summed nor written
+ *   sums[0] += sum of auc[b] >= 0,        counts[0] += rows with auc[b] < 0 (one class in the row),  sums[1] += sum of top1[b]
+ *   sums[2..4] += sums of metrics[b][0..2] over the rows with metrics[b][0] >= 0,  counts[1] += rows with metrics[b][0] < 0
+ *   counts[2] += 1 (steps),  counts[3] += rows with p inside the pass (the rows written, where there is a record)
+ *   rec_rank[p % cap][0..T) = rank[b][0..Tp) then 0,  rec_live[p % cap] = live[b],  rec_id[p % cap] = impression_id[b]
+ *   *cursor += B (a plain store of one lane, after every row has read the cursor)
+ * auc [B] fp32 / top1 [B] int32 are the outputs of nrm_row_auc, NULL together; metrics [B,3] fp32, rank [B,Tp] int32 and live [B] int32
+ * those of nrm_ensemble_rank (metrics NULL: a data set without labels); impression_id [B] int64; sums [5] float64, counts [4] int64.
+ * rec_rank [cap,T] int32, rec_live [cap] int32, rec_id [cap] int64 are NULL together with cap = 0 (a pass that keeps the sums only);
+ * cap > 0 is a multiple of B.  float64 accumulation in the fixed order of nrm_epoch_tally, no atomics: the same bits from run to run.
+ * All stores are plain stores.  B = 0 launches nothing. */
+int nrm_eval_tally(const float* auc, const int* top1, const float* metrics, const int* rank, const int* live, const long* impression_id,
+                   int B, int T, int Tp, long* cursor, long n_order, double* sums, long* counts, int* rec_rank, int* rec_live, long* rec_id,
+                   long cap, nrm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

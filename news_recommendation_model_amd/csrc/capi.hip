@@ -1057,4 +1057,21 @@ int nrm_epoch_tally(const float* loss, const float* auc, const int* top1, int B,
     return check_hip(nrm::epoch_tally_launch(loss, auc, top1, B, cursor, sums, counts, step_log, log_cap, (hipStream_t)stream), "epoch_tally");
 }
 
+int nrm_eval_tally(const float* auc, const int* top1, const float* metrics, const int* rank, const int* live, const long* impression_id,
+                   int B, int T, int Tp, long* cursor, long n_order, double* sums, long* counts, int* rec_rank, int* rec_live, long* rec_id,
+                   long cap, nrm_stream_t stream) {
+    if (B < 0 || T < 1 || Tp < 1 || n_order < 0 || cap < 0)
+        return fail(NRM_EINVAL, "nrm_eval_tally: B=%d T=%d Tp=%d n_order=%ld cap=%ld (B, n_order, cap >= 0; T, Tp >= 1)", B, T, Tp, n_order, cap);
+    if (Tp > T) return fail(NRM_EINVAL, "nrm_eval_tally: Tp=%d exceeds T=%d (the record row holds T columns)", Tp, T);
+    if (!cursor || !sums || !counts) return fail(NRM_EINVAL, "nrm_eval_tally: null cursor, sums or counts");
+    if (!auc != !top1) return fail(NRM_EINVAL, "nrm_eval_tally: auc and top1 are NULL together (the outputs of nrm_row_auc) or both given");
+    const int n_rec = (rec_rank != nullptr) + (rec_live != nullptr) + (rec_id != nullptr);
+    if ((cap == 0 && n_rec != 0) || (cap > 0 && n_rec != 3))
+        return fail(NRM_EINVAL, "nrm_eval_tally: rec_rank, rec_live and rec_id are NULL together with cap = 0, or all given with cap > 0 (cap=%ld)", cap);
+    if (cap > 0 && (!rank || !live || !impression_id)) return fail(NRM_EINVAL, "nrm_eval_tally: a record (cap=%ld) needs rank, live and impression_id", cap);
+    if (cap > 0 && B > 0 && cap % B) return fail(NRM_EINVAL, "nrm_eval_tally: cap=%ld is no multiple of B=%d (a step's rows stay together in the ring)", cap, B);
+    return check_hip(nrm::eval_tally_launch(auc, top1, metrics, rank, live, impression_id, B, T, Tp, cursor, n_order, sums, counts, rec_rank, rec_live,
+                                            rec_id, cap, (hipStream_t)stream), "eval_tally");
+}
+
 }  // extern "C"

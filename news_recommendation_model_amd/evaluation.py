@@ -16,6 +16,8 @@
   write_predictions / zip_predictions   test.py:76-132: one "<impression id> [r1,r2,...]" line per impression, zipped.
   score_dataset(models, head_path, out_dir)   test.py's model_test + write_submission_file over a processed test set.
   save_checkpoint / load_checkpoint   train.py:95-97 (state_dict minus 'delta'), test.py:160 (strict=False).
+  GraphedTableScoring / validate_tables / score_tables / sweep_checkpoints   train.py:107-110, test.py and verify.py:53-75 over a data
+                                set that lives on the device as tables: one graph replay per batch, one host read per pass.
 """
 from __future__ import annotations
 
@@ -55,6 +57,35 @@ def predict(models, batch):
     return scores, live
 
 
+class _WeightsWatch:
+    """What a captured forward has to know about its models' weights before a replay (the rule in GraphedPredict's docstring, shared with
+    GraphedTableScoring): ``check(have_graphs)`` -> True where an ADDRESS of a parameter or buffer, or the generation of the packed-weight
+    cache, has changed since the last look -- the caller drops its graphs; where only version counters have moved and graphs exist, the
+    packed images are refreshed in place by one eager ``ops.repack_persistent`` launch.  ``refresh()`` takes the present state as seen
+    (after a capture, whose warm-up may have created the images)."""
+
+    def __init__(self, models):
+        self.models = models
+        self.addresses = self.versions = None
+
+    def state(self):
+        tensors = [t for m in self.models for t in list(m.parameters()) + list(m.buffers())]
+        return (tuple(t.data_ptr() for t in tensors) + (ops.packed_weights_generation(),)), tuple(t._version for t in tensors)
+
+    def check(self, have_graphs):
+        addresses, versions = self.state()
+        dropped = addresses != self.addresses
+        if dropped:
+            self.addresses = addresses
+        elif versions != self.versions and have_graphs:
+            ops.repack_persistent([p for m in self.models for p in m.parameters()])      # same buffers the graphs read
+        self.versions = versions
+        return dropped
+
+    def refresh(self):
+        self.addresses, self.versions = self.state()
+
+
 class GraphedPredict:
     """predict() captured into one HIP graph per (input shapes, common-padding trim) and replayed: the reference's test batches
     (80 impressions, test.py:46) are launch-bound when stepped eagerly -- ~0.9 ms of host work for ~0.35 ms of kernels.  Inputs
@@ -75,12 +106,7 @@ class GraphedPredict:
         self.models = list(models)
         self.max_graphs = max_graphs
         self.graphs = {}
-        self._addresses = None
-        self._versions = None
-
-    def _weights_state(self):
-        tensors = [t for m in self.models for t in list(m.parameters()) + list(m.buffers())]
-        return (tuple(t.data_ptr() for t in tensors) + (ops.packed_weights_generation(),)), tuple(t._version for t in tensors)
+        self._weights = _WeightsWatch(self.models)
 
     @torch.no_grad()
     def __call__(self, batch):
@@ -88,13 +114,8 @@ class GraphedPredict:
         if native.kernel_events is not None:
             raise RuntimeError("per-kernel event timing cannot be recorded inside a graph capture")
         dev = next(self.models[0].parameters()).device
-        addresses, versions = self._weights_state()
-        if addresses != self._addresses:
+        if self._weights.check(bool(self.graphs)):
             self.graphs.clear()                                       # captured addresses are gone: capture again
-            self._addresses = addresses
-        elif versions != self._versions and self.graphs:
-            ops.repack_persistent([p for m in self.models for p in m.parameters()])      # same buffers the graphs read
-        self._versions = versions
         e_in = batch["empty_num"]
         trim = int(e_in.min()) if e_in.numel() else 0                 # host decision, as in predict()
         names = ("x_history", "x_target", "x_global", "empty_num")
@@ -118,7 +139,7 @@ class GraphedPredict:
             ent = (graph, static, scores, live)
             while len(self.graphs) >= self.max_graphs:
                 self.graphs.pop(next(iter(self.graphs)))
-            self._addresses, self._versions = self._weights_state()   # (the warm-up may have created the packed images)
+            self._weights.refresh()                                   # (the warm-up may have created the packed images)
         else:
             for k in names:
                 ent[1][k].copy_(batch[k], non_blocking=True)
@@ -386,3 +407,266 @@ def load_checkpoint(model, path):
     """test.py:160: load_state_dict(strict=False); only tensors are read from the file (weights_only)."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
     return model.load_state_dict(sd, strict=False)
+
+
+# ------------------------------------------------------------------------------------------------ table-fed evaluation (DESIGN.md section 5h)
+def scoring_plan(empty_num, N, B, T):
+    """The steps of a pass over ``N`` impressions in batches of ``B``, from the producer's ``empty_num`` IN PASS ORDER (host, [N]) ->
+    [(n, Tp)] per step: n = impressions of the step, Tp = T - min over the step of empty_num -- the width the reference's common trim
+    leaves (test.py:48-56), which decides the batch's scores.  Pure host arithmetic; no device."""
+    import numpy as np
+    e = np.asarray(empty_num, dtype=np.int64).reshape(-1)
+    N, B, T = int(N), int(B), int(T)
+    if e.shape[0] != N or B < 1 or T < 1:
+        raise ValueError(f"scoring_plan: {e.shape[0]} entries of empty_num for N={N}, B={B}, T={T}")
+    plan = []
+    for lo in range(0, N, B):
+        part = e[lo:lo + B]
+        tp = T - int(part.min())
+        if not 1 <= tp <= T:
+            raise ValueError(f"scoring_plan: the batch at impression {lo} would be trimmed to {tp} of {T} candidate columns "
+                             "(empty_num lies outside [0, T) for every one of its impressions)")
+        plan.append((int(part.shape[0]), tp))
+    return plan
+
+
+class GraphedTableScoring:
+    """A validation or scoring pass over device-resident tables whose steady state is ONE graph replay per batch: no
+    upload, no other launch from the host and no host read until the pass ends (or the record is drained).
+
+    The captured step is ``assemble_batch_at`` -> the slice to ``Tp`` columns -> every model's eval-mode forward -> ``ensemble_rank`` ->
+    ``row_auc`` (with labels) -> ``eval_tally``.  The reference trims the padding common to a batch BEFORE the first softmax
+    (test.py:48-56), so a batch's width ``Tp`` changes its scores; the producer knows ``empty_num`` of every impression on the host and a
+    pass runs in a fixed order, so every batch's ``Tp`` is known before the pass starts (``scoring_plan``) and there is one graph per
+    distinct ``Tp`` -- at most ``max_graphs``, least recently used first out, all in one memory pool, all reading the one cursor, the one
+    ``order`` buffer and the one state buffer.  Inside a graph the shapes are the eager call's (``predict_ranked`` over a ``TableLoader``
+    batch), so the logits are the eager path's.  A last partial batch runs eagerly through the same ops at its own size.
+
+    Weights may change between passes; the rule is GraphedPredict's (``_WeightsWatch``): new addresses or a new packed-weight generation
+    drop the graphs, new version counters re-pack the images in place before the first replay.
+
+    The tally keeps the five metric sums, the counts and a ring of ``record_rows`` rows (ranks, live counts, impression ids) in ONE state
+    buffer.  ``record_rows`` None: the whole pass, read once at its end; lower: the host drains the ring every ``record_rows``
+    impressions -- one read per drain.  The partial batch has a record of its own size behind the ring (a step's rows divide the ring it
+    writes), read with the last read."""
+
+    def __init__(self, models, tables, batch_size, H, T, keep_target_slot, with_labels=True, record_rows=None, max_graphs=16, compact=False,
+                 compact_history=False):
+        import torch.distributed as dist
+        from . import native
+        from .tables import TABLE_FIELDS
+        if compact or compact_history:
+            raise RuntimeError("GraphedTableScoring(compact=True / compact_history=True): the ragged forms are planned on the host for every batch; "
+                               "a captured step replays one fixed sequence of launches.  Capture the dense pass, or run the eager one "
+                               "(validate_ranked(..., compact=True) over a TableLoader)")
+        if native.kernel_events is not None:
+            raise RuntimeError("per-kernel event timing cannot be recorded inside a graph capture")
+        if dist.is_available() and dist.is_initialized():
+            raise RuntimeError("GraphedTableScoring: a process group is initialised; sharding the tables' impressions over ranks is not built "
+                               "(every rank would score the whole pass).  Run it in a process without a group")
+        self.models = list(models)
+        if not 1 <= len(self.models) <= 8:
+            raise RuntimeError(f"GraphedTableScoring: {len(self.models)} models; the scoring tail (ensemble_rank) takes 1 .. 8")
+        if int(batch_size) < 1 or int(max_graphs) < 1:
+            raise ValueError(f"GraphedTableScoring(batch_size={batch_size}, max_graphs={max_graphs})")
+        self.batch_size, self.H, self.T, self.keep_target_slot = int(batch_size), int(H), int(T), bool(keep_target_slot)
+        self.with_labels, self.max_graphs = bool(with_labels), int(max_graphs)
+        self.N = tables.n_impressions
+        if self.N < 1:
+            raise ValueError("GraphedTableScoring: the tables hold no impression")
+        B = self.batch_size
+        whole = (self.N + B - 1) // B * B
+        cap = whole if record_rows is None else int(record_rows)
+        if cap < B or cap % B:
+            raise ValueError(f"GraphedTableScoring(record_rows={record_rows}): a positive multiple of batch_size={B}")
+        self.cap, self.tail = min(cap, whole), self.N % B
+        dev = next(self.models[0].parameters()).device
+        self.tables = tables if tables.is_device else tables.to(dev)
+        self._tabs = [getattr(self.tables, name) for name in TABLE_FIELDS]
+        self.empty_all = self.tables.host.empty_num_all(self.T, self.keep_target_slot)
+        self.order = torch.zeros(self.N, dtype=torch.int64, device=dev)
+        self._order_host = torch.zeros(self.N, dtype=torch.int64).pin_memory()
+        # ONE buffer of 8-byte words: cursor | sums [5] float64 | counts [4] | ring: id [cap], live [cap] int32, rank [cap, T] int32 | the
+        # same three for the partial batch
+        words = lambda n_int32: (n_int32 + 1) // 2      # noqa: E731
+        at, self._at = 10, {}
+        for name, rows in (("ring", self.cap), ("tail", self.tail)):
+            self._at[name] = (at, at + rows, at + rows + words(rows))
+            at += rows + words(rows) + words(rows * self.T)
+        self.state = torch.zeros(at, dtype=torch.int64, device=dev)
+        self.cursor, self.counts = self.state[0:1], self.state[6:10]
+        self.sums = self.state[1:6].view(torch.float64)
+        self._rec = {name: self._views(self.state, name) for name in ("ring", "tail") if self._rows(name)}
+        ops.index_error_flag(dev)                               # (pinned: allocated before any capture)
+        self.graphs, self._pool = {}, None
+        self._weights = _WeightsWatch(self.models)
+        self.replays = self.eager_steps = self.captures = self.host_reads = 0
+
+    def _rows(self, name):
+        return self.cap if name == "ring" else self.tail
+
+    def _views(self, state, name):
+        """(rank [rows, T] int32, live [rows] int32, id [rows] int64) of the ring or the partial batch's record inside a state buffer"""
+        rows, (a_id, a_live, a_rank) = self._rows(name), self._at[name]
+        as32 = state.view(torch.int32) if isinstance(state, torch.Tensor) else state.view("int32")
+        return (as32[2 * a_rank:2 * a_rank + rows * self.T].reshape(rows, self.T), as32[2 * a_live:2 * a_live + rows], state[a_id:a_id + rows])
+
+    def _step_ops(self, n, Tp, rec):
+        """one step of ``n`` impressions at the cursor, scored at ``Tp`` columns: the SAME ops eagerly and inside a capture"""
+        from .tables import BATCH_KEYS
+        batch = dict(zip(BATCH_KEYS, ops.assemble_batch_at(self._tabs, self.order, self.cursor, n, self.H, self.T, self.keep_target_slot,
+                                                           int(self.tables.static_cols))))
+        xh, xt, xg, empty = batch["x_history"], batch["x_target"], batch["x_global"], batch["empty_num"]
+        trim = self.T - Tp
+        if trim > 0:                                            # test.py:48-56, decided by the plan instead of a device read
+            xt, xg, empty = xt[:, :-trim], xg[:, :-trim], empty - trim
+        logits = [m(xh, xt, xg) for m in self.models]
+        label = batch["label"][:, :Tp] if self.with_labels else None
+        scores, rank, live, metrics = ops.ensemble_rank(logits, empty, label)
+        auc = top1 = None
+        if self.with_labels:
+            auc, top1 = ops.row_auc(scores, label, live)
+        ops.eval_tally(auc, top1, metrics if self.with_labels else None, rank, live, batch["impression_id"], self.cursor, self.sums,
+                       self.counts, rec[0], rec[1], rec[2], self.N)
+
+    def _capture(self, Tp):
+        """the graph of a full batch at width ``Tp``, built as GraphedPredict builds its own: two warm-up steps on a side stream (allocator,
+        packed weight images) -- which move the cursor and the sums, so the head of the state is put back -- then the capture"""
+        dev = self.order.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            head = self.state[:10].clone()
+            for _ in range(2):
+                self._step_ops(self.batch_size, Tp, self._rec["ring"])
+                self.state[:10].copy_(head)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, pool=self._pool):
+            self._step_ops(self.batch_size, Tp, self._rec["ring"])
+        if self._pool is None:
+            self._pool = graph.pool()
+        while len(self.graphs) >= self.max_graphs:
+            self.graphs.pop(next(iter(self.graphs)))
+        self._weights.refresh()                                 # (the warm-up may have created the packed images)
+        self.captures += 1
+        return graph
+
+    def _read(self):
+        self.host_reads += 1
+        return self.state.cpu().numpy()                         # (waits for the stream)
+
+    @torch.no_grad()
+    def run(self, order=None):
+        """One pass in ``order`` (host, [N]; None: file order) -> dict(auc, top1, mrr, ndcg5, ndcg10 -- means over the pass, absent without
+        labels --, impressions, steps, one_class_rows, no_positive_rows, impression_id [N], rank [N, T], live [N]: host arrays in pass
+        order).  A single-class row raises validate_ranked's ValueError, an out-of-range index IndexError, both at the last read."""
+        import numpy as np
+        from . import native
+        if native.kernel_events is not None:
+            raise RuntimeError("per-kernel event timing cannot be recorded inside a graph capture")
+        N, B, T, cap = self.N, self.batch_size, self.T, self.cap
+        order = np.arange(N, dtype=np.int64) if order is None else np.ascontiguousarray(order, dtype=np.int64)
+        if order.shape != (N,):
+            raise ValueError(f"GraphedTableScoring.run: order {order.shape} for {N} impressions")
+        plan = scoring_plan(self.empty_all[order], N, B, T)
+        for m in self.models:
+            m.eval()
+        if self._weights.check(bool(self.graphs)):
+            self.graphs.clear()                                 # captured addresses are gone: capture again
+            self._pool = None
+        self._order_host.copy_(torch.from_numpy(order))
+        self.order.copy_(self._order_host, non_blocking=True)
+        self.state.zero_()
+        ids, rank, live = np.zeros(N, dtype=np.int64), np.zeros((N, T), dtype=np.int32), np.zeros(N, dtype=np.int32)
+
+        def take(host, name, lo, hi):
+            r_rank, r_live, r_id = self._views(host, name)
+            at = np.arange(lo, hi) % self._rows(name)
+            ids[lo:hi], rank[lo:hi], live[lo:hi] = r_id[at], r_rank[at], r_live[at]
+
+        done = drained = 0
+        for i, (n, Tp) in enumerate(plan):
+            if n == B:
+                graph = self.graphs.pop(Tp, None)
+                if graph is None:
+                    graph = self._capture(Tp)
+                self.graphs[Tp] = graph                         # (re-inserted last: most recently used)
+                graph.replay()
+                self.replays += 1
+            else:
+                self._step_ops(n, Tp, self._rec["tail"])
+                self.eager_steps += 1
+            done += n
+            if n == B and done - drained == cap and i + 1 < len(plan) and plan[i + 1][0] == B:
+                take(self._read(), "ring", drained, done)      # the ring is full and another full batch follows: drain it
+                drained = done
+        host = self._read()
+        ops.check_index_errors(self.order.device)
+        full = N - self.tail
+        take(host, "ring", drained, full)
+        if self.tail:
+            take(host, "tail", full, N)
+        sums, counts = host[1:6].view(np.float64), host[6:10]
+        if int(host[0]) != N or int(counts[3]) != N or int(counts[2]) != len(plan):
+            raise RuntimeError(f"GraphedTableScoring.run: the device record holds {int(counts[3])} impressions in {int(counts[2])} steps, cursor "
+                               f"{int(host[0])}; the pass has {N} in {len(plan)}")
+        out = {"impressions": N, "steps": len(plan), "one_class_rows": int(counts[0]), "no_positive_rows": int(counts[1]),
+               "impression_id": ids, "rank": rank, "live": live}
+        if self.with_labels:
+            if counts[0] > 0:
+                raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+            out.update({k: float(v) / N for k, v in zip(("auc", "top1", "mrr", "ndcg5", "ndcg10"), sums.tolist())})
+        return out
+
+
+def validate_tables(models, tables, batch_size=80, *, H, T, keep_target_slot=True, graph=True, runner=None):
+    """reference train.py:107-110 / verify.py:19-43 over a validation set that lives on the device as ``ImpressionTables``, in file order
+    -> validate_ranked's dict {"auc", "top1", "mrr", "ndcg5", "ndcg10"}.  ``graph=True``: one ``GraphedTableScoring`` pass (``runner``: one
+    built earlier for these models and tables, whose graphs are then reused); ``graph=False``: ``validate_ranked`` over a ``TableLoader``."""
+    if not graph:
+        from .tables import TableLoader
+        dev = next(models[0].parameters()).device
+        return validate_ranked(models, TableLoader(tables, batch_size, H, T, shuffle=False, keep_target_slot=keep_target_slot, device=dev))
+    if runner is None:
+        runner = GraphedTableScoring(models, tables, batch_size, H, T, keep_target_slot)
+    got = runner.run()
+    return {k: got[k] for k in ("auc", "top1", "mrr", "ndcg5", "ndcg10")}
+
+
+def score_tables(models, tables, out_dir, batch_size=80, *, H, T, keep_target_slot=False, name="predictions", graph=True, record_rows=None):
+    """test.py's ``model_test`` + ``write_submission_file`` for a test set that lives on the device as ``ImpressionTables`` (no labels needed)
+    -> path of ``<out_dir>/<name>.zip`` holding ``predictions.txt``, in file order.  ``graph=True``: a ``GraphedTableScoring`` pass without
+    labels whose ranks stay in the device record until it is drained (``record_rows``: impressions per drain; None: the whole pass, one
+    host read); ``graph=False``: predict_ranked + write_predictions per ``TableLoader`` batch (one device-to-host copy each)."""
+    import os
+    os.makedirs(out_dir, exist_ok=True)
+    txt_path = os.path.join(out_dir, "predictions.txt")
+    if graph:
+        got = GraphedTableScoring(models, tables, batch_size, H, T, keep_target_slot, with_labels=False, record_rows=record_rows).run()
+        write_predictions(txt_path, got["impression_id"], got["rank"], got["live"])
+    else:
+        from .tables import TableLoader
+        dev = next(models[0].parameters()).device
+        open(txt_path, "w").close()
+        for batch in TableLoader(tables, batch_size, H, T, shuffle=False, keep_target_slot=keep_target_slot, device=dev):
+            _scores, rank, live = predict_ranked(models, batch)
+            write_predictions(txt_path, batch["impression_id"], rank, live, append=True)
+        ops.check_index_errors(dev)
+    return zip_predictions(txt_path, os.path.join(out_dir, f"{name}.zip"))
+
+
+def sweep_checkpoints(paths, model, tables, batch_size=80, *, H, T, keep_target_slot=True, graph=True):
+    """reference verify.py:53-75: every checkpoint of ``paths`` loaded into the SAME ``model`` (``load_checkpoint``) and validated over the
+    tables -- through ONE ``GraphedTableScoring`` where ``graph``, so the graphs captured for the first checkpoint serve them all and only
+    the packed weight images are refreshed -> {"results": [validate_tables' dict per path], "best": the path with the highest AUC, "best_auc"}.
+    Ties go to the later path: the reference compares with ``>=``."""
+    runner = GraphedTableScoring([model], tables, batch_size, H, T, keep_target_slot) if graph else None
+    results, best, best_auc = [], None, -1.0
+    for path in paths:
+        load_checkpoint(model, path)
+        got = validate_tables([model], tables, batch_size, H=H, T=T, keep_target_slot=keep_target_slot, graph=graph, runner=runner)
+        results.append(got)
+        if got["auc"] >= best_auc:
+            best, best_auc = path, got["auc"]
+    return {"results": results, "best": best, "best_auc": best_auc}

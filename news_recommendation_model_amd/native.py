@@ -92,6 +92,7 @@ SIGNATURES = {
     "nrm_assemble_form": (_c_i, [_c_i, _c_i]),
     "nrm_assemble_batch_at": (_c_i, [_c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),      # the first: the same HOST struct
     "nrm_epoch_tally": (_c_i, [_c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp]),
+    "nrm_eval_tally": (_c_i, [_c_fp] * 6 + [_c_i] * 3 + [_c_fp, _c_l] + [_c_fp] * 5 + [_c_l, _c_fp]),
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
                                  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_fp, _c_fp,  _c_i, _c_i, _c_i, _c_i, _c_i,
                                  _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp]),

@@ -2809,6 +2809,56 @@ epoch_tally = _op("epoch_tally", "(Tensor loss, Tensor auc, Tensor top1, Tensor(
                   "Tensor(d!) step_log) -> ()", _epoch_tally_impl, _epoch_tally_fake)
 
 
+# ---- the record of a table-fed evaluation pass on the device
+def _eval_tally_check(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id, n_order):
+    B = live.shape[0] if live.dim() == 1 else -1
+    Tp = rank.shape[1] if rank.dim() == 2 else -1
+    rec = (rec_rank, rec_live, rec_id)
+    ok = (B >= 0 and Tp >= 1 and rank.shape[0] == B and rank.dtype == torch.int32 and live.dtype == torch.int32
+          and tuple(impression_id.shape) == (B,) and impression_id.dtype == torch.int64 and (auc is None) == (top1 is None)
+          and (auc is None or (tuple(auc.shape) == (B,) and auc.dtype == torch.float32 and tuple(top1.shape) == (B,) and top1.dtype == torch.int32))
+          and (metrics is None or (tuple(metrics.shape) == (B, 3) and metrics.dtype == torch.float32))
+          and cursor.numel() == 1 and cursor.dtype == torch.int64 and tuple(sums.shape) == (5,) and sums.dtype == torch.float64
+          and tuple(counts.shape) == (4,) and counts.dtype == torch.int64 and n_order >= 0
+          and (all(t is None for t in rec) or all(t is not None for t in rec))
+          and all(t is None or t.is_contiguous() for t in (auc, top1, metrics, rank, live, impression_id, cursor, sums, counts) + rec))
+    cap, T = 0, Tp
+    if ok and rec_rank is not None:
+        cap, T = (rec_rank.shape if rec_rank.dim() == 2 else (-1, -1))
+        ok = (cap >= 1 and T >= Tp and rec_rank.dtype == torch.int32 and tuple(rec_live.shape) == (cap,) and rec_live.dtype == torch.int32
+              and tuple(rec_id.shape) == (cap,) and rec_id.dtype == torch.int64 and (B == 0 or cap % B == 0))
+    if not ok:
+        d = lambda t: "None" if t is None else f"{tuple(t.shape)} {t.dtype}"      # noqa: E731
+        raise RuntimeError(f"eval_tally: auc {d(auc)}, top1 {d(top1)}, metrics {d(metrics)}, rank {d(rank)}, live {d(live)}, impression_id "
+                           f"{d(impression_id)}, cursor {d(cursor)}, sums {d(sums)}, counts {d(counts)}, rec_rank {d(rec_rank)}, rec_live {d(rec_live)}, "
+                           f"rec_id {d(rec_id)}, n_order={n_order}: expected [B] float32 and [B] int32 (None together), [B, 3] float32 or None, "
+                           "[B, Tp] int32, [B] int32, [B] int64, one int64, [5] float64, [4] int64, and [cap, T] int32, [cap] int32, [cap] int64 "
+                           "(None together) with T >= Tp and cap a multiple of B, all contiguous; n_order >= 0")
+    return B, int(T), int(Tp), int(cap)
+
+
+def _eval_tally_impl(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id, n_order):
+    """One launch at the end of an evaluation step (C ABI nrm_eval_tally): sums += {the defined row AUCs, the top-1 hits, rr, nDCG@5, nDCG@10 of
+    the rows with a live positive}, counts += {one-class rows, rows without a live positive, 1, rows inside the pass}, the step's ranks
+    (zero-filled to the record's width), live counts and impression ids into record row (cursor + b) % cap, cursor += B.  Rows at a
+    position outside [0, n_order) are skipped.  ``auc`` / ``top1``: the outputs of ``row_auc``; ``metrics`` / ``rank`` / ``live``: those of
+    ``ensemble_rank``.  float64, fixed order, no atomics."""
+    _require_gpu(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id)
+    B, T, Tp, cap = _eval_tally_check(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id, n_order)
+    p = lambda t: native.ptr(t) if t is not None else None      # noqa: E731
+    native.call("nrm_eval_tally", p(auc), p(top1), p(metrics), native.ptr(rank), native.ptr(live), native.ptr(impression_id), B, T, Tp,
+                native.ptr(cursor), int(n_order), native.ptr(sums), native.ptr(counts), p(rec_rank), p(rec_live), p(rec_id), cap, native.stream_ptr())
+
+
+def _eval_tally_fake(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id, n_order):
+    _eval_tally_check(auc, top1, metrics, rank, live, impression_id, cursor, sums, counts, rec_rank, rec_live, rec_id, n_order)
+
+
+eval_tally = _op("eval_tally", "(Tensor? auc, Tensor? top1, Tensor? metrics, Tensor rank, Tensor live, Tensor impression_id, Tensor(a!) cursor, "
+                 "Tensor(b!) sums, Tensor(c!) counts, Tensor(d!)? rec_rank, Tensor(e!)? rec_live, Tensor(f!)? rec_id, int n_order) -> ()",
+                 _eval_tally_impl, _eval_tally_fake)
+
+
 def _history_gather_impl(x_history, hist_off, R, k_max):
     """x_history [B, H, cols] -> [R, cols] (bitwise, dtype kept): row j < K_b of impression b goes to row hist_off[b] + j.  One launch."""
     _require_gpu(x_history, hist_off)
@@ -2957,4 +3007,4 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
        "candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
        "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
-       "assemble_batch", "assemble_batch_at", "epoch_tally", "adam_step")
+       "assemble_batch", "assemble_batch_at", "epoch_tally", "eval_tally", "adam_step")

@@ -840,7 +840,7 @@ def train_epochs(model, optimizer, make_loader, epochs, device="cuda", ckpt_path
 
 def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuffle=True, seed=0, keep_target_slot=True, device="cuda",
                         ckpt_path=None, on_batch=None, compact_history=False, max_groups=None, compact_candidates=False, drop_last=False,
-                        graph=False, graph_warmup=3):
+                        graph=False, graph_warmup=3, validation=None, validation_batch=80, validation_graph=None):
     """``train_epochs`` over a data set that lives on the device as ``tables.ImpressionTables``: every batch is
     written by the assemble kernel from a few KB of impression indices instead of being uploaded, on the current stream, and carries its
     producer's history lengths and ``empty_num`` on the host, so ``compact_history`` / ``compact_candidates`` plan without a measuring
@@ -850,9 +850,24 @@ def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuf
     replay, and the host reads the device once per epoch.  The permutations are the eager loop's (the same ``TableLoader`` generator: one
     seed, the same impressions in the same order).  The record gains ``step_loss`` / ``step_auc`` (per step, from the device log) and
     ``top1_avg``; ``on_batch`` is refused (a call per step would need a synchronise per step), and so is everything a captured step
-    cannot do (``GraphedTableEpoch``)."""
+    cannot do (``GraphedTableEpoch``).
+    ``validation``: a second set of tables (labelled) -- after every epoch's checkpoint the model is validated over it in batches of
+    ``validation_batch`` as reference train.py:107-110 does, the record gains ``val_auc``, ``val_top1``, ``val_mrr``, ``val_ndcg5`` and
+    ``val_ndcg10``, and the model is put back into train mode.  ``validation_graph`` (None: as ``graph``): through one
+    ``evaluation.GraphedTableScoring`` kept for all epochs, else ``validate_ranked`` over a ``TableLoader``.  None: nothing changes."""
     from . import evaluation, ops
     from .tables import TableLoader
+    validate_epoch = None
+    if validation is not None:
+        val_graph = bool(graph if validation_graph is None else validation_graph)
+        val_runner = evaluation.GraphedTableScoring([model], validation, validation_batch, H, T, keep_target_slot) if val_graph else None
+        val_tables = val_runner.tables if val_graph else (validation if validation.is_device else validation.to(device))
+
+        def validate_epoch(rec):
+            got = evaluation.validate_tables([model], val_tables, validation_batch, H=H, T=T, keep_target_slot=keep_target_slot, graph=val_graph,
+                                             runner=val_runner)
+            model.train()
+            rec.update({"val_" + k: v for k, v in got.items()})
     if graph:
         if on_batch is not None:
             raise RuntimeError("train_epochs_tables(graph=True, on_batch=...): a call per step would need a host synchronise per step, which is "
@@ -873,6 +888,8 @@ def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuf
                             "step_loss": got["step_loss"], "step_auc": got["step_auc"]})
             if ckpt_path is not None:
                 evaluation.save_checkpoint(model, ckpt_path.format(epoch=epoch))
+            if validate_epoch is not None:
+                validate_epoch(history[-1])
         return history
     loader = TableLoader(tables, batch_size, H, T, shuffle=shuffle, seed=seed, keep_target_slot=keep_target_slot, device=device, drop_last=drop_last)
     history = []
@@ -903,4 +920,6 @@ def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuf
                         "loss_avg": float(loss_sum / max(seen, 1)), "auc_avg": float(auc_sum / max(seen, 1))})
         if ckpt_path is not None:
             evaluation.save_checkpoint(model, ckpt_path.format(epoch=epoch))
+        if validate_epoch is not None:
+            validate_epoch(history[-1])
     return history
