@@ -174,6 +174,26 @@ MIN_SAVING = 0.25       # a plan that drops less than this share of the B * H hi
 GROUPS_CAP = 64         # csrc/compact.hpp HISTORY_GROUPS_MAX
 
 
+def _upload(plan, parts, device):
+    """The group plans' ``upload``: the int32 host arrays ``parts`` (attribute names) of ``plan`` as device views of ONE buffer copied from
+    pinned host memory (non-blocking).  Cached on the plan."""
+    import torch
+    if plan.device_tables is not None and plan.device_tables["perm"].device == torch.device(device):
+        return plan.device_tables
+    arrays = [getattr(plan, name) for name in parts]
+    host = torch.empty(sum(len(a) for a in arrays), dtype=torch.int32)
+    if torch.cuda.is_available():
+        host = host.pin_memory()
+    host.numpy()[:] = np.concatenate(arrays)
+    dev = host.to(device, non_blocking=True)
+    tabs, o = {"_host": host}, 0                # (the pinned source lives as long as the copy may run)
+    for name, a in zip(parts, arrays):
+        tabs[name] = dev[o:o + len(a)]
+        o += len(a)
+    plan.device_tables = tabs
+    return tabs
+
+
 class HistoryGroupPlan:
     """Length groups of one batch (host numpy; ``upload`` puts the tables on a device with ONE pinned copy).
 
@@ -198,21 +218,7 @@ class HistoryGroupPlan:
     def upload(self, device):
         """-> dict of int32 device views (perm, inverse, bounds, row_off, H_g) of ONE buffer copied from pinned host memory
         (non-blocking).  Cached on the plan."""
-        import torch
-        if self.device_tables is not None and self.device_tables["perm"].device == torch.device(device):
-            return self.device_tables
-        parts = [("perm", self.perm), ("inverse", self.inverse), ("bounds", self.bounds), ("row_off", self.row_off), ("H_g", self.H_g)]
-        host = torch.empty(sum(len(p) for _, p in parts), dtype=torch.int32)
-        if torch.cuda.is_available():
-            host = host.pin_memory()
-        host.numpy()[:] = np.concatenate([p for _, p in parts])
-        dev = host.to(device, non_blocking=True)
-        tabs, o = {"_host": host}, 0
-        for name, p in parts:
-            tabs[name] = dev[o:o + len(p)]
-            o += len(p)
-        self.device_tables = tabs
-        return tabs
+        return _upload(self, ("perm", "inverse", "bounds", "row_off", "H_g"), device)
 
 
 def _cut_sorted(height, max_groups):
@@ -309,21 +315,7 @@ class CandidateGroupPlan:
 
     def upload(self, device):
         """-> dict of int32 device views (perm, bounds, row_off, T_g, expand) of ONE buffer copied from pinned host memory (non-blocking)."""
-        import torch
-        if self.device_tables is not None and self.device_tables["perm"].device == torch.device(device):
-            return self.device_tables
-        parts = [("perm", self.perm), ("bounds", self.bounds), ("row_off", self.row_off), ("T_g", self.T_g), ("expand", self.expand)]
-        host = torch.empty(sum(len(p) for _, p in parts), dtype=torch.int32)
-        if torch.cuda.is_available():
-            host = host.pin_memory()
-        host.numpy()[:] = np.concatenate([p for _, p in parts])
-        dev = host.to(device, non_blocking=True)
-        tabs, o = {"_host": host}, 0
-        for name, p in parts:
-            tabs[name] = dev[o:o + len(p)]
-            o += len(p)
-        self.device_tables = tabs
-        return tabs
+        return _upload(self, ("perm", "bounds", "row_off", "T_g", "expand"), device)
 
 
 def plan_candidate_groups(empty_num, T, max_groups=None, history_plan=None):

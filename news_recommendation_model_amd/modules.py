@@ -187,73 +187,43 @@ class UserInvariantInterestModel(nn.Module):
     def forward_parts_grouped(self, x_history_arena, x_target, plan):
         """forward_parts on length groups: ``x_history_arena`` [R, cols] are the plan's kept history rows
         (``ops.history_gather_groups``), ``x_target`` [B, T, cols] is in the plan's SORTED order; -> the same four blocks in sorted order.
-        The front end and w1 are row-wise and run on the R rows unchanged; only the two attention + pool nodes know about the groups.
-        A plan that carries candidate groups (``plan.cand``) takes ``x_target`` as the candidate arena [N, cols]
-        (``ops.candidate_gather_groups``) and returns the four blocks as arena rows [N, width]."""
+        The front end and w1 are row-wise and run on the R history rows and the candidate rows unchanged; only the two attention + pool
+        nodes know about the groups.  A plan that carries candidate groups (``plan.cand``) takes ``x_target`` as the
+        candidate arena [N, cols] (``ops.candidate_gather_groups``) and returns the four blocks as arena rows [N, width]."""
         ops._require_gpu(x_history_arena, x_target)
         cand = getattr(plan, "cand", None)
-        if cand is not None:
-            return self._forward_parts_cgrouped(x_history_arena, x_target, plan, cand)
-        B, T = x_target.shape[0], x_target.shape[1]
-        if x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or B != plan.B or B * T == 0 or plan.R == 0:
-            raise RuntimeError(f"forward_grouped: plan for {plan.B} impressions / {plan.R} kept history rows, got a history arena "
-                               f"{tuple(x_history_arena.shape)} and targets {tuple(x_target.shape)}")
+        if cand is None:
+            B, T = x_target.shape[0], x_target.shape[1]
+            if x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or B != plan.B or B * T == 0 or plan.R == 0:
+                raise RuntimeError(f"forward_grouped: plan for {plan.B} impressions / {plan.R} kept history rows, got a history arena "
+                                   f"{tuple(x_history_arena.shape)} and targets {tuple(x_target.shape)}")
+            x_target = x_target.reshape(B * T, x_target.shape[2])                               # the rows of the sorted batch
+        else:
+            if (x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or x_target.dim() != 2 or x_target.shape[0] != cand.N
+                    or cand.B != plan.B or cand.N == 0 or plan.R == 0):
+                raise RuntimeError(f"forward_grouped: plan for {plan.R} kept history rows / {cand.N} candidate rows, got a history arena "
+                                   f"{tuple(x_history_arena.shape)} and a candidate arena {tuple(x_target.shape)}")
         if not self.grouped_attention_applies():
             raise RuntimeError("forward_grouped: an attention of this model does not take the fused attention + pool node (feature width "
                                "not a multiple of 4, a non-GELU MLP or a substituted module): run the dense forward")
         sen = self.sentiment_embedding[0]
         lab_h, ti_h, lab_t, ti_t = ops.frontend_pair_fwd(
-            x_history_arena, x_target.reshape(B * T, x_target.shape[2]), int(self._dims.n_subcat), int(self._dims.pca_vector),
+            x_history_arena, x_target, int(self._dims.n_subcat), int(self._dims.pca_vector),
             self.category_embedding[0].weight, sen.weight, sen.bias, self.type_embedding[0].weight, self.year_embedding[0].weight,
             self.month_embedding[0].weight, self.day_embedding[0].weight, self.hour_embedding[0].weight)
-        ti_h, ti_t = ti_h.detach(), ti_t.detach().unflatten(0, (B, T))
-        lab_t = lab_t.reshape(B, T, -1) if lab_t.is_contiguous() else lab_t.unflatten(0, (B, T))
+        ti_h, ti_t = ti_h.detach(), ti_t.detach()
         lab_h = ops.linear(lab_h, self.w1.weight, self.w1.bias)                                       # [R, D_l]
+        if cand is None:                        # the attention node and the caller take the sorted batch as [B, T, width]
+            ti_t = ti_t.unflatten(0, (B, T))
+            lab_t = lab_t.reshape(B, T, -1) if lab_t.is_contiguous() else lab_t.unflatten(0, (B, T))
 
         def attend(att, t, h):
             m = att.mlp
             return ops.attend_and_pool_grouped(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, plan, mma=att.mma)
 
         # two streams as in forward_parts; the choice goes by the z elements the groups really have
-        side = ops.branch_stream(lab_t) if self.uses_two_streams(plan.R * T * lab_h.shape[1]) else None
-        if side is not None:
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            ti_t.record_stream(side)
-            ti_h.record_stream(side)
-            with torch.cuda.stream(side):
-                pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
-            pooled_lab = attend(self.label_attention, lab_t, lab_h)
-            main.wait_stream(side)
-            pooled_ti.record_stream(main)
-        else:
-            pooled_lab = attend(self.label_attention, lab_t, lab_h)
-            pooled_ti = attend(self.text_img_attention, ti_t, ti_h)
-        return pooled_lab, pooled_ti, lab_t, ti_t
-
-    def _forward_parts_cgrouped(self, x_history_arena, x_target_arena, plan, cand):
-        """forward_parts_grouped on groups trimmed in the candidate axis too: every layer up to the attention is row-wise in the candidate
-        and runs on the N arena rows."""
-        if (x_history_arena.dim() != 2 or x_history_arena.shape[0] != plan.R or x_target_arena.dim() != 2 or x_target_arena.shape[0] != cand.N
-                or cand.B != plan.B or cand.N == 0 or plan.R == 0):
-            raise RuntimeError(f"forward_grouped: plan for {plan.R} kept history rows / {cand.N} candidate rows, got a history arena "
-                               f"{tuple(x_history_arena.shape)} and a candidate arena {tuple(x_target_arena.shape)}")
-        if not self.grouped_attention_applies():
-            raise RuntimeError("forward_grouped: an attention of this model does not take the fused attention + pool node (feature width "
-                               "not a multiple of 4, a non-GELU MLP or a substituted module): run the dense forward")
-        sen = self.sentiment_embedding[0]
-        lab_h, ti_h, lab_t, ti_t = ops.frontend_pair_fwd(
-            x_history_arena, x_target_arena, int(self._dims.n_subcat), int(self._dims.pca_vector),
-            self.category_embedding[0].weight, sen.weight, sen.bias, self.type_embedding[0].weight, self.year_embedding[0].weight,
-            self.month_embedding[0].weight, self.day_embedding[0].weight, self.hour_embedding[0].weight)
-        ti_h, ti_t = ti_h.detach(), ti_t.detach()
-        lab_h = ops.linear(lab_h, self.w1.weight, self.w1.bias)                                       # [R, D_l]
-
-        def attend(att, t, h):
-            m = att.mlp
-            return ops.attend_and_pool_cgrouped(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, plan, mma=att.mma)
-
-        z_rows = sum(int(n) * int(tg) * int(hg) for n, tg, hg in zip(plan.bounds[1:] - plan.bounds[:-1], cand.T_g, plan.H_g))
+        z_rows = plan.R * T if cand is None else sum(int(n) * int(tg) * int(hg) for n, tg, hg in
+                                                     zip(plan.bounds[1:] - plan.bounds[:-1], cand.T_g, plan.H_g))
         side = ops.branch_stream(lab_t) if self.uses_two_streams(z_rows * lab_h.shape[1]) else None
         if side is not None:
             main = torch.cuda.current_stream()
@@ -463,11 +433,8 @@ class UserModel(nn.Module):
             raise RuntimeError(f"forward_compact: plan for {plan.B} impressions / {plan.N} rows, got {B} / {N} target and {xg_compact.shape[0]} global rows")
         if B * H == 0 or N == 0:
             raise RuntimeError("cannot reshape tensor of 0 elements (empty batch / history / candidate list)")
-        for att in (inv.label_attention, inv.text_img_attention):
-            mlp = getattr(att, "mlp", None)
-            if not (type(att) is PointwiseAttentionExpanded and isinstance(mlp, MLP) and isinstance(mlp.activation, nn.GELU)
-                    and mlp.activation.approximate == "none"):
-                raise RuntimeError("forward_compact: the ragged attention implements the reference default (PointwiseAttentionExpanded, exact GELU) only")
+        if not (inv._fused_node_applies(inv.label_attention) and inv._fused_node_applies(inv.text_img_attention)):
+            raise RuntimeError("forward_compact: the ragged attention implements the reference default (PointwiseAttentionExpanded, exact GELU) only")
         tabs = plan.upload(x_history.device)
         with torch.no_grad():
             sen = inv.sentiment_embedding[0]
@@ -487,13 +454,7 @@ class UserModel(nn.Module):
                 pooled.append(ops.attend_pool_ragged(t, h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, tabs["cand_imp"],
                                                      tabs["cand_off"], plan.max_count, mma=att.mma))
             eu_L = self.instant_interest_model(xg_compact)
-            rows = ops.concat_last((pooled[0], pooled[1], eu_L, lab_t[0], ti_t[0]))                 # [N, width]
-            g = self.gate
-            if isinstance(g.activation, nn.GELU) and g.activation.approximate == "none":
-                gated = ops.gate_block(rows, self.bn, g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias)
-            else:
-                gated = g.forward_times(ops.batch_norm(rows, self.bn), rows)
-            return self._tail(gated).reshape(N)
+            return self._head(ops.concat_last((pooled[0], pooled[1], eu_L, lab_t[0], ti_t[0])))     # rows [N, width] -> logits [N]
 
     def loss(self, id, out, label, alpha=0.95):
         # any number of candidates: one wave per impression, in registers up to T = 256, re-reading the row beyond (csrc/pool_loss.hip)

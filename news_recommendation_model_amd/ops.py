@@ -1890,129 +1890,91 @@ def attend_and_pool(target, history, fc1_weight, fc1_bias, fc2_weight, fc2_bias,
 #   The batch is sorted by history length and cut into groups (compact.plan_history_groups); group g -- sorted
 # impressions b0[g] .. b0[g + 1] - 1, each trimmed to hg[g] <= H history rows, from row row_off[g] of the history arena h [R, D] -- runs through
 # the DENSE forward and backward kernels with H = hg[g].  Only the pool knows that where hg[g] < H the group's last row is a padded row that
-# stands for w_g = H - hg[g] + 1 equal rows.  The group table travels as host integers: the launches are per group (_attn_blocks_fwd,
-# _attn_blocks_bwd; the layout of the arena, s and z: _group_layout).
-def _attend_pool_grouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
-    """t [B, T, D] (sorted order), h [R, D] (the arena) -> (pooled [B, T, D], s [S], z [Z * D] or empty).  s and z hold
-    sum_g B_g T H_g (D) elements instead of B T H (D); s is UNWEIGHTED (the weight is applied where the pool reads it)."""
-    _require_gpu(t, h, w1, b1, w2, b2)
-    B, T, D = t.shape
-    groups, R, S, Z = _group_layout(group_b0, group_h, T)
-    if (h.dim() != 2 or h.shape[0] != R or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4 or groups[-1][1] != B
-            or max(group_h) > H):
-        raise RuntimeError(f"grouped attention: target {tuple(t.shape)}, history arena {tuple(h.shape)}, fc1 {tuple(w1.shape)}, groups of "
-                           f"{list(group_b0)} x {list(group_h)} rows (H = {H}) do not agree (feature width must be a multiple of 4)")
-    return _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, True)
-
-
-def _attend_pool_grouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, H, save_z, mma):
-    _, _, S, Z = _group_layout(group_b0, group_h, t.shape[1])
-    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
-    return f(*t.shape), f(S), f(Z * t.shape[2] if save_z else 0)
-
-
-attend_pool_grouped_fwd = _op("attend_pool_grouped_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
-                              "int[] group_b0, int[] group_h, int H, bool save_z, int mma) -> (Tensor, Tensor, Tensor)",
-                              _attend_pool_grouped_fwd_impl, _attend_pool_grouped_fwd_fake)
-
-
-def _attend_pool_grouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
-    """Backward of the grouped node from the pooled gradient g [B, T, D]: _attn_blocks_bwd over the plan's groups."""
-    _require_gpu(g, t, h, w1, w2, s, z)
-    groups, _, _, Z = _group_layout(group_b0, group_h, t.shape[1])
-    return _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, pool=(*_pooled_grad_rows(g, *t.shape), s))
-
-
-def _attend_pool_grouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, H, mma, need_dt, need_dh):
-    B, T, D = t.shape
-    f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
-    return (f(B, T, D) if need_dt else f(0)), (f(h.shape[0], D) if need_dh else f(0)), f(D, 4 * D), f(D), f(D + 4)
-
-
-attend_pool_grouped_bwd = _op("attend_pool_grouped_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
-                              "int[] group_b0, int[] group_h, int H, int mma, bool need_dt, bool need_dh) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
-                              _attend_pool_grouped_bwd_impl, _attend_pool_grouped_bwd_fake)
-
-
-_attention_node("attend_pool_grouped_fwd", attend_pool_grouped_bwd, 5, True, False)
-
-
-def attend_and_pool_grouped(target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
-    """[B, T, D] candidates in the plan's SORTED order x the grouped history arena [R, D] (``compact.plan_history_groups`` +
-    ``history_gather_groups``, then whatever row-wise layers lead to the attention) -> pooled [B, T, D] in sorted order: what
-    ``attend_and_pool`` gives the dense [B, H, D] history whose rows j >= H_g - 1 of every impression of a trimmed group are all equal.
-    One autograd node, every arithmetic; the feature width must be a multiple of 4 (no padded fallback: the caller runs dense then)."""
-    args = (target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
-    _require_gpu(*args)
-    if target.dim() != 3 or target.shape[-1] % 4 or target.shape[0] != plan.B or plan.B == 0:
-        raise RuntimeError(f"attend_and_pool_grouped: target {tuple(target.shape)} for a plan of {plan.B} impressions (needs [B, T, D], D a "
-                           "multiple of 4, B > 0)")
-    save_z = torch.is_grad_enabled() and any(a.requires_grad for a in args)
-    return attend_pool_grouped_fwd(*args, [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], int(plan.H), save_z, resolve_mma(mma))[0]
-
-
-# (DESIGN.md section 5f)  The same node on groups that are trimmed in the candidate axis as well: group g keeps group_t[g] <= T candidate
-# columns, t is the candidate arena [N, D] (N = sum_g B_g T_g; compact.plan_candidate_groups + candidate_gather_groups).  The attention and
-# the pool are row-wise in the candidate: a group is the dense [B_g, T_g, H_g] problem, and nothing here knows the candidate weight.
-def _attend_pool_cgrouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
-    """t [N, D] (the candidate arena), h [R, D] (the history arena) -> (pooled [N, D], s [S], z [Z * D] or empty)."""
+# stands for w_g = H - hg[g] + 1 equal rows.    The groups may be trimmed in the candidate axis as well: group g keeps
+# group_t[g] <= T candidate columns and t is the candidate arena [N, D] (N = sum_g B_g T_g; compact.plan_candidate_groups +
+# candidate_gather_groups); with group_t = [T] * G the arena is the [B * T, D] rows of the sorted batch.  The attention and the pool are
+# row-wise in the candidate: a group is the dense [B_g, T_g, H_g] problem, and nothing here knows the candidate weight.  The group table
+# travels as host integers: the launches are per group (_attn_blocks_fwd, _attn_blocks_bwd; the layout of the arenas, s and z: _group_layout).
+def _attend_pool_grouped_fwd_impl(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
+    """t [N, D] (the candidate arena), h [R, D] (the history arena) -> (pooled [N, D], s [S], z [Z * D] or empty).  s and z hold
+    sum_g B_g T_g H_g (D) elements instead of B T H (D); s is UNWEIGHTED (the weight is applied where the pool reads it)."""
     _require_gpu(t, h, w1, b1, w2, b2)
     groups, R, S, Z = _group_layout(group_b0, group_h, T, group_t)
     D = t.shape[-1]
     N = groups[-1][8] + (groups[-1][1] - groups[-1][0]) * groups[-1][7]
     if (t.dim() != 2 or t.shape[0] != N or h.dim() != 2 or h.shape[0] != R or h.shape[1] != D or tuple(w1.shape) != (D, 4 * D) or D % 4
             or max(group_h) > H):
+        if all(int(x) == T for x in group_t):              # the sorted batch as rows: the groups are cut in the history axis only
+            raise RuntimeError(f"grouped attention: target rows {tuple(t.shape)} (B * T = {groups[-1][1]} * {T}), history arena {tuple(h.shape)}, "
+                               f"fc1 {tuple(w1.shape)}, groups of {list(group_b0)} x {list(group_h)} rows (H = {H}) do not agree (feature width "
+                               "must be a multiple of 4)")
         raise RuntimeError(f"grouped attention: candidate arena {tuple(t.shape)}, history arena {tuple(h.shape)}, fc1 {tuple(w1.shape)}, groups of "
                            f"{list(group_b0)} x {list(group_t)} x {list(group_h)} rows (T = {T}, H = {H}) do not agree (feature width must be a "
                            "multiple of 4)")
     return _attn_blocks_fwd(t, h, w1, b1, w2, b2, groups, S, Z, H, save_z, mma, True)
 
 
-def _attend_pool_cgrouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
+def _attend_pool_grouped_fwd_fake(t, h, w1, b1, w2, b2, group_b0, group_h, group_t, H, T, save_z, mma):
     _, _, S, Z = _group_layout(group_b0, group_h, T, group_t)
     f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
     return f(*t.shape), f(S), f(Z * t.shape[1] if save_z else 0)
 
 
-attend_pool_cgrouped_fwd = _op("attend_pool_cgrouped_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
-                               "int[] group_b0, int[] group_h, int[] group_t, int H, int T, bool save_z, int mma) -> (Tensor, Tensor, Tensor)",
-                               _attend_pool_cgrouped_fwd_impl, _attend_pool_cgrouped_fwd_fake)
+attend_pool_grouped_fwd = _op("attend_pool_grouped_fwd", "(Tensor t, Tensor h, Tensor fc1_weight, Tensor fc1_bias, Tensor fc2_weight, Tensor fc2_bias, "
+                              "int[] group_b0, int[] group_h, int[] group_t, int H, int T, bool save_z, int mma) -> (Tensor, Tensor, Tensor)",
+                              _attend_pool_grouped_fwd_impl, _attend_pool_grouped_fwd_fake)
 
 
-def _attend_pool_cgrouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
-    """Backward of the candidate-grouped node from the pooled gradient g [N, D] (read in place when it is a column block of the head gradient)."""
+def _attend_pool_grouped_bwd_impl(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
+    """Backward of the grouped node from the pooled gradient g [N, D] (read in place when it is a column block of the head gradient):
+    _attn_blocks_bwd over the plan's groups.  The rowdot launches take a group's rows with T_g of them to an impression, so where every
+    group keeps all T columns the in-place test is the dense node's, on g as [B, T, D]."""
     _require_gpu(g, t, h, w1, w2, s, z)
     groups, _, _, Z = _group_layout(group_b0, group_h, T, group_t)
-    g3, ldg = _pooled_grad_rows(g.unsqueeze(0), 1, t.shape[0], t.shape[1])
-    return _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, pool=(g3[0], ldg, s))
+    N, D = t.shape
+    as_batch = (N // T, T) if all(int(x) == T for x in group_t) else (1, N)
+    return _attn_blocks_bwd(t, h, w1, w2, z, groups, Z, H, mma, need_dt, need_dh, pool=(*_pooled_grad_rows(g.unflatten(0, as_batch), *as_batch, D), s))
 
 
-def _attend_pool_cgrouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
+def _attend_pool_grouped_bwd_fake(g, t, h, w1, w2, s, z, group_b0, group_h, group_t, H, T, mma, need_dt, need_dh):
     N, D = t.shape
     f = lambda *shape: t.new_empty(shape, dtype=torch.float32)      # noqa: E731
     return (f(N, D) if need_dt else f(0)), (f(h.shape[0], D) if need_dh else f(0)), f(D, 4 * D), f(D), f(D + 4)
 
 
-attend_pool_cgrouped_bwd = _op("attend_pool_cgrouped_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
-                               "int[] group_b0, int[] group_h, int[] group_t, int H, int T, int mma, bool need_dt, bool need_dh) -> "
-                               "(Tensor, Tensor, Tensor, Tensor, Tensor)", _attend_pool_cgrouped_bwd_impl, _attend_pool_cgrouped_bwd_fake)
+attend_pool_grouped_bwd = _op("attend_pool_grouped_bwd", "(Tensor g, Tensor t, Tensor h, Tensor fc1_weight, Tensor fc2_weight, Tensor s, Tensor(a!) z, "
+                              "int[] group_b0, int[] group_h, int[] group_t, int H, int T, int mma, bool need_dt, bool need_dh) -> "
+                              "(Tensor, Tensor, Tensor, Tensor, Tensor)", _attend_pool_grouped_bwd_impl, _attend_pool_grouped_bwd_fake)
 
 
-_attention_node("attend_pool_cgrouped_fwd", attend_pool_cgrouped_bwd, 7, True, False)
+_attention_node("attend_pool_grouped_fwd", attend_pool_grouped_bwd, 7, True, False)
 
 
-def attend_and_pool_cgrouped(target_arena, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
-    """The candidate arena [N, D] of ``plan.cand`` (a ``compact.CandidateGroupPlan`` cut along ``plan``'s groups) x the grouped history arena
-    [R, D] -> pooled [N, D]: row for row what ``attend_and_pool_grouped`` gives the kept cells of the sorted [B, T, D] batch."""
-    args = (target_arena, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
+def attend_and_pool_grouped(target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias, plan, mma=None):
+    """The candidates x the grouped history arena [R, D] (``compact.plan_history_groups`` + ``history_gather_groups``, then whatever row-wise
+    layers lead to the attention) -> pooled, shaped like ``target``: what ``attend_and_pool`` gives the dense [B, H, D] history whose rows
+    j >= H_g - 1 of every impression of a trimmed group are all equal.  ``target``: [B, T, D] in the plan's SORTED order or, where the plan
+    carries ``plan.cand`` (a ``compact.CandidateGroupPlan`` cut along its groups), the candidate arena [N, D] -- row for row the kept cells
+    of the sorted batch.  One autograd node, every arithmetic; the feature width must be a multiple of 4 (no padded fallback: the caller
+    runs dense then)."""
+    args = (target, history_arena, fc1_weight, fc1_bias, fc2_weight, fc2_bias)
     _require_gpu(*args)
-    cand = plan.cand
-    if target_arena.dim() != 2 or target_arena.shape[-1] % 4 or target_arena.shape[0] != cand.N or cand.N == 0:
-        raise RuntimeError(f"attend_and_pool_cgrouped: candidate arena {tuple(target_arena.shape)} for a plan of {cand.N} rows (needs [N, D], D a "
-                           "multiple of 4, N > 0)")
+    cand = getattr(plan, "cand", None)
+    if cand is None:
+        if target.dim() != 3 or target.shape[-1] % 4 or target.shape[0] != plan.B or plan.B == 0:
+            raise RuntimeError(f"attend_and_pool_grouped: target {tuple(target.shape)} for a plan of {plan.B} impressions (needs [B, T, D], D a "
+                               "multiple of 4, B > 0)")
+        T = target.shape[1]
+        group_t = [T] * len(plan.H_g)
+    else:
+        if target.dim() != 2 or target.shape[-1] % 4 or target.shape[0] != cand.N or cand.N == 0:
+            raise RuntimeError(f"attend_and_pool_grouped: candidate arena {tuple(target.shape)} for a plan of {cand.N} rows (needs [N, D], D a "
+                               "multiple of 4, N > 0)")
+        T, group_t = int(cand.T), [int(x) for x in cand.T_g]
     save_z = torch.is_grad_enabled() and any(a.requires_grad for a in args)
-    return attend_pool_cgrouped_fwd(*args, [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], [int(x) for x in cand.T_g], int(plan.H),
-                                    int(cand.T), save_z, resolve_mma(mma))[0]
+    pooled = attend_pool_grouped_fwd(target.flatten(0, -2), *args[1:], [int(x) for x in plan.bounds], [int(x) for x in plan.H_g], group_t,
+                                     int(plan.H), T, save_z, resolve_mma(mma))[0]
+    return pooled if cand is not None else pooled.view(target.shape)
 
 
 def _history_gather_groups_impl(x_history, perm, bounds, row_off, H_g, R):
@@ -3005,6 +2967,6 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "frontend_pair_fwd", "frontend_pair_bwd", "row_auc", "ensemble_rank", "compact_gather", "attend_pool_ragged_fwd", "ensemble_rank_ragged",
        "history_len", "history_gather", "history_tiles", "attend_pool_hragged_fwd",
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
-       "candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
+       "candidate_gather_groups", "batch_norm_stats_roww", "batch_norm_apply_roww",
        "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
        "assemble_batch", "assemble_batch_at", "epoch_tally", "eval_tally", "adam_step")

@@ -364,6 +364,19 @@ def _empty_num_host(batch):
     return e.detach().cpu().numpy() if hasattr(e, "detach") else e
 
 
+def _history_plan(batch, max_groups):
+    """The length groups of the batch's histories (``compact.plan_history_groups``), from the lengths the prefetcher measured or ones
+    measured now."""
+    from . import compact
+    xh = batch["x_history"]
+    pre = batch.get("history_len_host")                      # attach_history_len's entry: valid for the tensor it was measured on only
+    if pre is None or (pre[2], pre[3]) != (xh.data_ptr(), xh._version):
+        pre = history_len_host(xh)                           # nobody measured THESE rows: measure now, at the cost of a synchronise
+    host, done = pre[0], pre[1]
+    done.synchronize()                                       # the side stream's copy only -- not the compute stream
+    return compact.plan_history_groups(host.numpy(), xh.shape[1], max_groups=max_groups)
+
+
 def _compact_candidates_forward(model, batch, alpha, max_groups, compact_history):
     """forward + loss of train_step(compact_candidates=True) -> (loss, out [B, T] in the caller's order), or None where the candidate axis
     has nothing worth dropping or the model does not take the row-weight head (the caller then tries compact_history alone, then dense)."""
@@ -382,13 +395,7 @@ def _compact_candidates_forward(model, batch, alpha, max_groups, compact_history
         raise ValueError("train_step(compact_candidates=True): a candidate that empty_num counts as padding differs from the other padded "
                          "candidates of its impression in x_target, x_global or label, in a batch of an earlier step (which ran on the "
                          "compacted rows and HAS BEEN APPLIED); train this data with the dense step")
-    hist = None
-    if compact_history:
-        pre = batch.get("history_len_host")
-        if pre is None or (pre[2], pre[3]) != (xh.data_ptr(), xh._version):
-            pre = history_len_host(xh)
-        pre[1].synchronize()
-        hist = compact.plan_history_groups(pre[0].numpy(), xh.shape[1], max_groups=max_groups)
+    hist = _history_plan(batch, max_groups) if compact_history else None
     cand = compact.plan_candidate_groups(empty, xt.shape[1], max_groups=max_groups, history_plan=hist)
     if cand.dense or cand.B == 0:
         return None
@@ -407,16 +414,11 @@ def _compact_candidates_forward(model, batch, alpha, max_groups, compact_history
 def _compact_forward(model, batch, alpha, max_groups):
     """forward + loss of train_step(compact_history=True) -> (loss, out in the caller's order), or None where the step runs dense: a
     model whose attentions do not take the fused node, or a plan with nothing worth dropping."""
-    from . import compact, ops
+    from . import ops
     if not (hasattr(model, "compact_history_applies") and model.compact_history_applies()):
         return None
     xh = batch["x_history"]
-    pre = batch.get("history_len_host")                      # attach_history_len's entry: valid for the tensor it was measured on only
-    if pre is None or (pre[2], pre[3]) != (xh.data_ptr(), xh._version):
-        pre = history_len_host(xh)                           # nobody measured THESE rows: measure now, at the cost of a synchronise
-    host, done = pre[0], pre[1]
-    done.synchronize()                                       # the side stream's copy only -- not the compute stream
-    plan = compact.plan_history_groups(host.numpy(), xh.shape[1], max_groups=max_groups)
+    plan = _history_plan(batch, max_groups)
     if plan.dense or plan.B == 0:
         return None
     tabs = plan.upload(xh.device)

@@ -219,7 +219,7 @@ def test_new_entries_validate_on_the_host(lib):
     assert loss(B=0) == 0
 
 
-NEW_OPS = ("candidate_gather_groups", "attend_pool_cgrouped_fwd", "attend_pool_cgrouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
+NEW_OPS = ("candidate_gather_groups", "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "batch_norm_stats_roww", "batch_norm_apply_roww",
            "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped")
 
 
@@ -247,11 +247,11 @@ def test_new_ops_are_registered_with_fakes_and_refuse_cpu_tensors():
         Z = 3 * 3 * 6 + 3 * 5 * 18 + 3 * 7 * 37
         R = 3 * 6 + 3 * 18 + 3 * 37
         for save_z in (True, False):
-            pooled, s, z = torch.ops.nrm.attend_pool_cgrouped_fwd(c(45, 16), c(R, 16), c(16, 64), c(16), c(1, 16), c(1), b0, hg, tg, 37, 7, save_z, 0)
+            pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(c(45, 16), c(R, 16), c(16, 64), c(16), c(1, 16), c(1), b0, hg, tg, 37, 7, save_z, 0)
             assert (tuple(pooled.shape), tuple(s.shape), tuple(z.shape)) == ((45, 16), (S,), (Z * 16 if save_z else 0,))
         for need_dt, need_dh in ((True, True), (False, False)):
-            dt, dh, dw1, db1, acc = torch.ops.nrm.attend_pool_cgrouped_bwd(c(45, 16), c(45, 16), c(R, 16), c(16, 64), c(1, 16), c(S), c(Z * 16),
-                                                                           b0, hg, tg, 37, 7, 0, need_dt, need_dh)
+            dt, dh, dw1, db1, acc = torch.ops.nrm.attend_pool_grouped_bwd(c(45, 16), c(45, 16), c(R, 16), c(16, 64), c(1, 16), c(S), c(Z * 16),
+                                                                          b0, hg, tg, 37, 7, 0, need_dt, need_dh)
             assert tuple(dt.shape) == ((45, 16) if need_dt else (0,)) and tuple(dh.shape) == ((R, 16) if need_dh else (0,))
             assert (tuple(dw1.shape), tuple(db1.shape), tuple(acc.shape)) == ((16, 64), (16,), (20,))
         mean, rstd = torch.ops.nrm.batch_norm_stats_roww(c(45, 24), c(24), c(24), 0.1, 1e-5, c(45), 63)

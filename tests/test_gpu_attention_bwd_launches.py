@@ -173,7 +173,7 @@ def _fused(rng, need_dt, need_dh, grouped):
 
     def forward():
         if grouped:
-            pooled = ops.attend_pool_grouped_fwd(t, h, *w, GROUP_B0, GROUP_H, H, True, ops.MMA_F32)[0]
+            pooled = ops.attend_pool_grouped_fwd(t.flatten(0, 1), h, *w, GROUP_B0, GROUP_H, [T] * len(GROUP_H), H, T, True, ops.MMA_F32)[0].view_as(g)
         else:
             pooled = ops.attend_and_pool(t, h, *w, mma="f32")
         return (pooled * g).sum().backward
@@ -242,10 +242,10 @@ def test_one_full_height_group_is_bitwise_the_dense_forward(lib):
     t = torch.from_numpy(rng.standard_normal((B, T, D)).astype(np.float32)).to(dev)
     h = torch.from_numpy(rng.standard_normal((B, H, D)).astype(np.float32)).to(dev)
     pooled, s, z = torch.ops.nrm.attend_pool_fwd(t, h, *w, True, 0)
-    pooled_g, s_g, z_g = torch.ops.nrm.attend_pool_grouped_fwd(t, h.reshape(B * H, D), *w, [0, B], [H], H, True, 0)
+    pooled_g, s_g, z_g = torch.ops.nrm.attend_pool_grouped_fwd(t.reshape(B * T, D), h.reshape(B * H, D), *w, [0, B], [H], [T], H, T, True, 0)
     torch.cuda.synchronize()
     assert tuple(s.shape) == (B, T, H) and tuple(z.shape) == (B, T, H, D) and z_g.numel() == z.numel() and s_g.numel() >= s.numel()
     bits = lambda x: x.contiguous().view(torch.int32)                      # noqa: E731
-    assert torch.equal(bits(pooled_g), bits(pooled))
+    assert torch.equal(bits(pooled_g.reshape(B, T, D)), bits(pooled))
     assert torch.equal(bits(s_g[:s.numel()].reshape(B, T, H)), bits(s)) and torch.equal(bits(z_g.reshape(B, T, H, D)), bits(z))
     assert float(pooled.abs().max()) > 0 and float(z.abs().max()) > 0

@@ -677,9 +677,9 @@ def test_opcheck_on_the_new_ops(lib):
     D, H, hg = 16, 9, [3, 9, 9]
     R = sum((b0[i + 1] - b0[i]) * hg[i] for i in range(3))
     args = (r(N, D), r(R, D), 0.1 * r(D, 4 * D), 0.1 * r(D), r(1, D), r(1), b0, hg, tg, H, T, True, 0)
-    torch.library.opcheck(torch.ops.nrm.attend_pool_cgrouped_fwd.default, args, test_utils=tests)
-    pooled, s, z = torch.ops.nrm.attend_pool_cgrouped_fwd(*args)
-    torch.library.opcheck(torch.ops.nrm.attend_pool_cgrouped_bwd.default,
+    torch.library.opcheck(torch.ops.nrm.attend_pool_grouped_fwd.default, args, test_utils=tests)
+    pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(*args)
+    torch.library.opcheck(torch.ops.nrm.attend_pool_grouped_bwd.default,
                           (r(N, D), args[0], args[1], args[2], args[4], s, z.detach(), b0, hg, tg, H, T, 0, True, True), test_utils=tests)
 
 

@@ -360,6 +360,10 @@ def test_three_lockstep_optimizer_steps_agree_with_the_dense_step(lib, step_case
     torch.cuda.synchronize()
 
 
+# what only a step on compacted CANDIDATE lists launches (tests/test_gpu_candidate_train.py asserts them of that step)
+WEIGHTED_ENTRIES = ("nrm_colreduce_roww", "nrm_bn_backward_roww", "nrm_loss_fwd_bwd_wlast")
+
+
 def test_a_dense_plan_is_bitwise_the_dense_step(lib, step_case, monkeypatch):
     """All L_b = H: the plan is dense and the step continues as compact_history=False does.  Four dense and four dense-plan steps run
     alternately from the same state.  Every dense-plan step issues exactly the dense step's native calls, with the same integer
@@ -389,6 +393,8 @@ def test_a_dense_plan_is_bitwise_the_dense_step(lib, step_case, monkeypatch):
         lens = [k for k, x in enumerate(c) if x[0] == "nrm_history_len"]
         assert len(lens) == 1 and c[:lens[0]] + c[lens[0] + 1:] == calls[0][0]
     assert all(c == calls[0][0] for c in calls[0])
+    names = [x[0] for x in calls[0][0]]                 # the dense step passes no row weight: the plain kernels, none of the weighted ones
+    assert not [e for e in WEIGHTED_ENTRIES if e in names] and all(e in names for e in ("nrm_colreduce", "nrm_bn_backward", "nrm_loss_fwd_bwd"))
     for r in dense[1:] + plan_runs:
         assert r[0] == dense[0][0] and r[1].tobytes() == dense[0][1].tobytes()
     bitwise = spread = 0
@@ -426,6 +432,8 @@ def test_prefetcher_measures_the_lengths_on_a_side_stream(lib, step_case, monkey
     tb = trainer.attach_history_len(trainer.batch_to_device(batch, "cuda"))
     trainer.train_step(model, opt, tb, compact_history=True, max_groups=4)
     assert seen.count("nrm_history_len") == 1 and seen.count("nrm_history_gather_groups") == 1
+    # the history-only compacted step keeps every candidate row: unweighted BatchNorm and loss kernels, none of the weighted ones
+    assert not [e for e in WEIGHTED_ENTRIES if e in seen] and all(e in seen for e in ("nrm_colreduce", "nrm_bn_backward", "nrm_loss_fwd_bwd"))
     tb["x_history"].copy_(tb["x_history"].flip(0))                       # other lengths in the same buffer
     del seen[:]
     loss_stale, _ = trainer.train_step(model, opt, tb, compact_history=True, max_groups=4)
@@ -496,11 +504,13 @@ def test_opcheck_on_the_new_ops(lib):
     w = [_dev(case.w[k]) for k in ab.WKEYS]
     b0, hg = [int(x) for x in plan.bounds], [int(x) for x in plan.H_g]
     tests = ("test_schema", "test_faketensor", "test_autograd_registration")
-    args = (_dev(case.t[plan.perm]), _dev(arena), *w, b0, hg, 37, True, 0)
+    tg = [3] * plan.G
+    args = (_dev(case.t[plan.perm]).flatten(0, 1), _dev(arena), *w, b0, hg, tg, 37, 3, True, 0)
     torch.library.opcheck(torch.ops.nrm.attend_pool_grouped_fwd.default, args, test_utils=tests)
     pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(*args)
     z = z.detach()
-    torch.library.opcheck(torch.ops.nrm.attend_pool_grouped_bwd.default, (_dev(case.g[plan.perm]), args[0], args[1], w[0], w[2], s, z, b0, hg, 37, 0, True, True),
+    torch.library.opcheck(torch.ops.nrm.attend_pool_grouped_bwd.default, (_dev(case.g[plan.perm]).flatten(0, 1), args[0], args[1], w[0], w[2], s, z, b0, hg, tg, 37, 3,
+                                                                            0, True, True),
                           test_utils=tests)
     tabs = plan.upload("cuda")
     x = _dev(np.random.default_rng(0).standard_normal((7, 37, 12)))

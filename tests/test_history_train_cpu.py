@@ -162,23 +162,51 @@ def test_new_ops_are_registered_with_fakes_and_refuse_cpu_tensors():
     with pytest.raises((RuntimeError, NotImplementedError)):
         torch.ops.nrm.history_gather_groups(torch.zeros(2, 3, 4), i32(1, 0), i32(0, 2), i32(0, 4), i32(2), 4)
     with pytest.raises((RuntimeError, NotImplementedError)):
-        torch.ops.nrm.attend_pool_grouped_fwd(torch.zeros(2, 3, 8), torch.zeros(4, 8), torch.zeros(8, 32), torch.zeros(8), torch.zeros(1, 8),
-                                              torch.zeros(1), [0, 2], [2], 5, False, 0)
+        torch.ops.nrm.attend_pool_grouped_fwd(torch.zeros(6, 8), torch.zeros(4, 8), torch.zeros(8, 32), torch.zeros(8), torch.zeros(1, 8),
+                                              torch.zeros(1), [0, 2], [2], [3], 5, 3, False, 0)
     with FakeTensorMode():
         c = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device="cuda")      # noqa: E731
         i = lambda n: c(n, dtype=torch.int32)                    # noqa: E731
         xh = torch.ops.nrm.history_gather_groups(c(9, 37, 80, dtype=torch.float64), i(9), i(4), i(4), i(3), 164)
         assert (tuple(xh.shape), xh.dtype) == ((164, 80), torch.float64)
-        b0, hg = [0, 3, 7, 9], [6, 18, 37]
+        b0, hg, tg = [0, 3, 7, 9], [6, 18, 37], [5, 5, 5]
         S = (((3 * 5 * 6 + 63) // 64 * 64 + 4 * 5 * 18 + 63) // 64 * 64 + 2 * 5 * 37 + 63) // 64 * 64
         for save_z in (True, False):
-            pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(c(9, 5, 16), c(164, 16), c(16, 64), c(16), c(1, 16), c(1), b0, hg, 37, save_z, 0)
-            assert (tuple(pooled.shape), tuple(s.shape), tuple(z.shape)) == ((9, 5, 16), (S,), (164 * 5 * 16 if save_z else 0,))
+            pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(c(9 * 5, 16), c(164, 16), c(16, 64), c(16), c(1, 16), c(1), b0, hg, tg, 37, 5, save_z, 0)
+            assert (tuple(pooled.view(9, 5, 16).shape), tuple(s.shape), tuple(z.shape)) == ((9, 5, 16), (S,), (164 * 5 * 16 if save_z else 0,))
         for need_dt, need_dh in ((True, True), (False, False)):
-            dt, dh, dw1, db1, acc = torch.ops.nrm.attend_pool_grouped_bwd(c(9, 5, 16), c(9, 5, 16), c(164, 16), c(16, 64), c(1, 16), c(S), c(164 * 5 * 16),
-                                                                          b0, hg, 37, 0, need_dt, need_dh)
-            assert tuple(dt.shape) == ((9, 5, 16) if need_dt else (0,)) and tuple(dh.shape) == ((164, 16) if need_dh else (0,))
+            dt, dh, dw1, db1, acc = torch.ops.nrm.attend_pool_grouped_bwd(c(9 * 5, 16), c(9 * 5, 16), c(164, 16), c(16, 64), c(1, 16), c(S), c(164 * 5 * 16),
+                                                                          b0, hg, tg, 37, 5, 0, need_dt, need_dh)
+            assert tuple(dt.view(-1, 5, 16).shape if need_dt else dt.shape) == ((9, 5, 16) if need_dt else (0,))
+            assert tuple(dh.shape) == ((164, 16) if need_dh else (0,))
             assert (tuple(dw1.shape), tuple(db1.shape), tuple(acc.shape)) == ((16, 64), (16,), (20,))
+
+
+def test_merged_grouped_node_fakes_are_the_3d_forms_reshaped():
+    """The one grouped attention + pool node on a uniform-T plan of 3 groups (B = 9, T = 5, H = 37, D = 16): its fake shapes are what the
+    node that took t as [B, T, D] returned, reshaped -- pooled and dt [B * T, D], s [S] with every group's block on a 256-byte boundary,
+    z [Z * D] with Z = R * T, dh [R, D] -- written out here without the layout helper the fakes use."""
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    B, T, H, D = 9, 5, 37, 16
+    b0, hg = [0, 3, 7, 9], [6, 18, 37]
+    n = [b0[g + 1] - b0[g] for g in range(3)]
+    R = sum(n[g] * hg[g] for g in range(3))
+    Z = R * T
+    S = sum((n[g] * T * hg[g] + 63) // 64 * 64 for g in range(3))
+    assert (R, S) == (164, 896)
+    with FakeTensorMode():
+        c = lambda *s: torch.empty(*s, dtype=torch.float32, device="cuda")      # noqa: E731
+        w = (c(D, 4 * D), c(D), c(1, D), c(1))
+        for save_z in (True, False):
+            pooled, s, z = torch.ops.nrm.attend_pool_grouped_fwd(c(B * T, D), c(R, D), *w, b0, hg, [T] * 3, H, T, save_z, 0)
+            assert [tuple(x.shape) for x in (pooled, s, z)] == [(B * T, D), (S,), (Z * D if save_z else 0,)]
+            assert pooled.dtype == s.dtype == z.dtype == torch.float32
+        for need_dt, need_dh in ((True, True), (True, False), (False, True), (False, False)):
+            out = torch.ops.nrm.attend_pool_grouped_bwd(c(B * T, D), c(B * T, D), c(R, D), w[0], w[2], c(S), c(Z * D), b0, hg, [T] * 3, H, T, 0,
+                                                        need_dt, need_dh)
+            assert [tuple(x.shape) for x in out] == [(B * T, D) if need_dt else (0,), (R, D) if need_dh else (0,), (D, 4 * D), (D,), (D + 4,)]
+        with pytest.raises(RuntimeError, match="not a partition"):       # a group_t that does not go with group_h
+            torch.ops.nrm.attend_pool_grouped_fwd(c(B * T, D), c(R, D), *w, b0, hg, [T] * 2, H, T, True, 0)
 
 
 def test_model_and_trainer_interfaces_without_a_gpu():
