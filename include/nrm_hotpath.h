@@ -410,7 +410,11 @@ int nrm_ensemble_rank(const float* const* logits, const long* row_stride, const 
  * nrm_pwattn_fwd_ragged: nrm_pwattn_fwd without a z store for candidate rows t, v [N, D] (row c belongs to impression cand_imp[c]),
  *   history rows h, u [B, H, D], scores s [N, H].  fp32 arithmetic only: mma other than NRM_MMA_F32 is refused.  max_count = the
  *   longest list (max over b of cand_off[b + 1] - cand_off[b]).
- * nrm_pool_bmm_ragged: out[c, :] = sum_j s[c, j] h[cand_imp[c], j, :] for s [N, H], h [B, H, D], out [N, D].
+ * nrm_pool_bmm_ragged: out[c, :] = sum_j s[c, j] h[cand_imp[c], j, :] for s [N, H], h [B, H, D], out [N, D].  List b is the rows
+ *   c0_b .. c1_b - 1 with c0_b = clamp(cand_off[b], 0, N) and c1_b = clamp(cand_off[b + 1], c0_b, N); max_count is the longest list.
+ *   The entry WRITES exactly the rows of the lists (two lists must not own the same row) and LEAVES every other row of out as it
+ *   was: the rows before the first list and behind the last one.  (Should max_count be smaller than a list, that list's rows from
+ *   max_count on are either written or left.)  The planners of compact.py give every row to a list: no row of `pooled` is left.
  * nrm_ensemble_rank_ragged: nrm_ensemble_rank for compact logits: model m's entry c lies at logits[m][c * col_stride[m]]
  *   (col_stride NULL = 1); impression b owns the entries cand_off[b] .. cand_off[b + 1] - 1, the last of which stands for pad_mult[b]
  *   padded columns where pad_mult[b] > 0:
@@ -446,7 +450,14 @@ int nrm_ensemble_rank_ragged(const float* const* logits, const long* col_stride,
  * nrm_pwattn_fwd_hragged: nrm_pwattn_fwd_ragged for history rows h, u [R, D] and scores s [16 Mt]; rows of a tile past its valid ones
  *   are written as 0.  fp32 arithmetic only: mma other than NRM_MMA_F32 is refused.
  * nrm_pool_bmm_hragged: out[c, :] = sum_{j < K_b} w_j s[c, j] h[hist_off[b] + j, :], w_j = 1 except w_{K_b - 1} = hist_mult[b] where
- *   hist_mult[b] > 0; s is read, never changed. */
+ *   hist_mult[b] > 0; s is read, never changed.  With the lists of nrm_pool_bmm_ragged, r0_b = clamp(hist_off[b], 0, R), K_b =
+ *   clamp(hist_off[b + 1], r0_b, R) - r0_b, nt_b = ceil(K_b / 16) and t0_b = clamp(tile_pre[b], 0, Mt), the scores of candidate i of list b
+ *   are s[16 (t0_b + i nt_b) + j], j < K_b (the columns K_b .. 16 nt_b of its tiles are not read), and the entry WRITES the first
+ *   min(c1_b - c0_b, floor((Mt - t0_b) / nt_b)) rows of every list with K_b >= 1: never past the scores there are.  It LEAVES as they
+ *   were the rows of a list with K_b = 0, the rows a list is cut short of, and the rows no list owns.  build_plan keeps K_b >= 1
+ *   wherever H >= 1 and its tile_pre holds every candidate's tiles, so ops.attend_pool_hragged_fwd returns no unwritten row.
+ *   B is not limited to 65535 as in the dense pool entries: the launch is a one-dimensional grid of (impression, slab, row group)
+ *   tasks and refuses only a task count past 2^31 workgroups. */
 int nrm_history_len(const void* x_history, int cols, int is_f64, int B, int H, int* hist_len, nrm_stream_t stream);
 int nrm_history_gather(const void* x_history, int cols, int is_f64, const int* hist_off, int B, int H, int R, int k_max, void* xh_compact,
                        nrm_stream_t stream);

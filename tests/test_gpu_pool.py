@@ -1,4 +1,5 @@
-"""GPU: the dense pool pair (pool_loss.hip) through nrm_pool_bmm and nrm_pool_rowdot, element by element against the float64 statements
+"""GPU: every instantiation of pool_loss.hip's two matrix-core kernels through its C entry -- nrm_pool_bmm, nrm_pool_rowdot, and (below)
+nrm_pool_bmm_ragged, nrm_pool_bmm_hragged, nrm_pool_bmm_wlast, nrm_pool_rowdot_wlast -- element by element against the float64 statements
 of pool_util.  Bounds (derived in pool_util's docstring from the fp32 MFMA being a chain of fused multiply-adds): J U sum_j |W X| for the
 batched product in either form (plus U (|prior| + |ref|) with `accumulate`), D U sum_d |g h| for the row dots; one-hot W / g must give
 the selected row of X / column of h BITWISE.  tests/test_pool_cpu.py shows that this very check rejects six one-line mutants.
@@ -7,6 +8,12 @@ nrm_pool_bmm: the full product of I in 1 .. 65 and J in 1 .. 130 at D = 68, B = 
 and W = s^T (wsi = 1), ldx = D and D + 4 (NaN in the padding), accumulate 0 and 1, three families, and in the three settings of
 NRM_POOL_JSPLIT (the launcher reads it at every launch).  nrm_pool_rowdot: T x H x D x ldg x B as listed in pool_util, zero_n in {0, 3, 300}
 on a NaN-filled zero_out.  Sentinels behind every output.
+
+The ragged and the weighted entries: cases, bounds ((J + 1) U sum_j w_j |W X| where a weight that is no power of two touches a term) and the
+fifteen further mutants are listed in pool_util's docstring.  Lists of up to 130 candidates (three 64-row groups) next to empty and
+one-row lists, kept histories of 1 .. 65 rows, NaN in every score the kernels promise not to read, table entries outside the arrays
+(clamped by the rule of nrm_hotpath.h; rows of `out` that no list owns or that have no scores keep their sentinel bits), the weighted
+row in every wave's range / row group / trip, wlast = 1 bitwise the dense entry.
 
 No test of this file creates a stream or captures a graph.  Set NRM_HEAD_POOL_RECORD=<path> to merge the worst error / bound per entry
 into a JSON file (profiles/head_pool_bounds.json is such a record; no gate is derived from it)."""
@@ -57,6 +64,37 @@ class Native:
     def rowdot(self, gmem, ldg, hmem, ds, B, T, H, D, zero_out, zero_n):
         g, h, o, z = _d(gmem), _d(hmem), _d(ds), _d(zero_out)
         native.call("nrm_pool_rowdot", native.ptr(g), ldg, native.ptr(h), native.ptr(o), B, T, H, D, native.ptr(z), zero_n, native.stream_ptr())
+        torch.cuda.synchronize()
+        return o.cpu().numpy(), z.cpu().numpy()
+
+    def bmm_ragged(self, smem, hmem, out, cand_off, B, N, max_count, H, D, form):
+        assert os.environ.get("NRM_POOL_JSPLIT") == form
+        s, h, o, co = _d(smem), _d(hmem), _d(out), _d(cand_off)
+        native.call("nrm_pool_bmm_ragged", native.ptr(s), native.ptr(h), native.ptr(o), native.ptr(co), B, N, max_count, H, D, native.stream_ptr())
+        torch.cuda.synchronize()
+        return o.cpu().numpy()
+
+    def bmm_hragged(self, smem, hmem, out, cand_off, hist_off, hist_mult, tile_pre, B, N, max_count, R, Mt, k_max, D, form):
+        assert os.environ.get("NRM_POOL_JSPLIT") == form
+        s, h, o, tabs = _d(smem), _d(hmem), _d(out), [_d(t) for t in (cand_off, hist_off, hist_mult, tile_pre)]
+        assert all(t.dtype == torch.int32 for t in tabs)
+        native.call("nrm_pool_bmm_hragged", native.ptr(s), native.ptr(h), native.ptr(o), *[native.ptr(t) for t in tabs], B, N, max_count, R, Mt, k_max, D,
+                    native.stream_ptr())
+        torch.cuda.synchronize()
+        return o.cpu().numpy()
+
+    def bmm_wlast(self, wmem, wsb, wsi, wsj, xmem, ldx, out, B, I, J, D, accumulate, wlast, wlast_row, form):
+        assert os.environ.get("NRM_POOL_JSPLIT") == form
+        w, x, o = _d(wmem), _d(xmem), _d(out)
+        native.call("nrm_pool_bmm_wlast", native.ptr(w), wsb, wsi, wsj, native.ptr(x), ldx, native.ptr(o), B, I, J, D, accumulate, float(wlast), wlast_row,
+                    native.stream_ptr())
+        torch.cuda.synchronize()
+        return o.cpu().numpy()
+
+    def rowdot_wlast(self, gmem, ldg, hmem, ds, B, T, H, D, zero_out, zero_n, wlast):
+        g, h, o, z = _d(gmem), _d(hmem), _d(ds), _d(zero_out)
+        native.call("nrm_pool_rowdot_wlast", native.ptr(g), ldg, native.ptr(h), native.ptr(o), B, T, H, D, native.ptr(z), zero_n, float(wlast),
+                    native.stream_ptr())
         torch.cuda.synchronize()
         return o.cpu().numpy(), z.cpu().numpy()
 
@@ -112,6 +150,104 @@ def test_pool_rowdot_per_element(lib, D):
                     ran += 1
     print(f"D={D}: {ran} launches, worst error / bound {worst:.3f}")
     assert ran == len(pu.ROWDOT_B) * len(pu.ROWDOT_T) * len(pu.ROWDOT_H) * 2 * 4
+
+
+def _set_form(monkeypatch, jsplit):
+    if jsplit is None:
+        monkeypatch.delenv("NRM_POOL_JSPLIT", raising=False)
+    else:
+        monkeypatch.setenv("NRM_POOL_JSPLIT", jsplit)
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_cases():
+    """made once, shared by the three forms, never changed"""
+    return ([pu.ragged_case(order, H, D, family) for order, H, D in pu.ragged_shapes() for family in pu.BMM_FAMILIES]
+            + [pu.ragged_clamped(family, which) for family in pu.BMM_FAMILIES for which in (0, 1)])
+
+
+@functools.lru_cache(maxsize=None)
+def _hragged_cases():
+    return ([pu.hragged_case(D, family) for D in pu.RAGGED_D for family in pu.BMM_FAMILIES]
+            + [pu.hragged_clamped(family) for family in pu.BMM_FAMILIES])
+
+
+@functools.lru_cache(maxsize=None)
+def _wlast_case(I, J, ldx, layout, family):
+    return pu.make_wlast(I, J, ldx, layout, family)
+
+
+@pytest.mark.parametrize("jsplit", pu.FORMS)
+def test_pool_bmm_ragged_per_element(lib, monkeypatch, jsplit):
+    """lists of 0 .. 130 candidates (three 64-row groups, empty lists first, in the middle and last), H through one wave's and four waves'
+    ranges, clamped tables; rows no list owns keep their bits"""
+    _set_form(monkeypatch, jsplit)
+    be, ran, worst = Native(), 0, 0.0
+    for c in _ragged_cases():
+        res = pu.check_ragged(be, c, jsplit)
+        assert ("pool_bmm_ragged.onehot" in res) == (c["family"] == "onehot")
+        _hold((jsplit, c["cand_off"].tolist(), c["H"], c["D"], c["family"]), res)
+        worst = max(worst, res["pool_bmm_ragged"])
+        ran += 1
+    print(f"NRM_POOL_JSPLIT={jsplit}: {ran} launches, worst error / bound {worst:.3f}")
+    assert ran == (len(pu.ragged_shapes()) + 2) * len(pu.BMM_FAMILIES)
+
+
+@pytest.mark.parametrize("jsplit", pu.FORMS)
+def test_pool_bmm_hragged_per_element(lib, monkeypatch, jsplit):
+    """kept histories of 1 .. 65 rows under lists of 0 .. 130 candidates, hist_mult 0, 2, 3, 37, NaN in the unread score columns, clamped
+    tables (a history of no rows and a list cut short by Mt leave their rows of `out` alone)"""
+    _set_form(monkeypatch, jsplit)
+    be, ran, worst = Native(), 0, 0.0
+    for c in _hragged_cases():
+        res = pu.check_hragged(be, c, jsplit)
+        assert ("pool_bmm_hragged.onehot" in res) == (c["family"] == "onehot")
+        _hold((jsplit, c["cand_off"].tolist(), c["D"], c["family"]), res)
+        worst = max(worst, res["pool_bmm_hragged"])
+        ran += 1
+    print(f"NRM_POOL_JSPLIT={jsplit}: {ran} launches, worst error / bound {worst:.3f}")
+    assert ran == (len(pu.RAGGED_D) + 1) * len(pu.BMM_FAMILIES)
+
+
+@pytest.mark.parametrize("row", (0, 1))
+@pytest.mark.parametrize("jsplit", pu.FORMS)
+def test_pool_bmm_wlast_per_element(lib, monkeypatch, jsplit, row):
+    """wlast_row = 0: row J - 1 in the range of wave 0, 1, 2 and 3 of the JSPLIT form; wlast_row = 1: row I - 1 in the first, second and third
+    64-row group and in every 16-row tile position, onto a non-zero prior; wlast = 1 gives the bits of nrm_pool_bmm"""
+    _set_form(monkeypatch, jsplit)
+    be, ran, worst, key = Native(), 0, 0.0, f"pool_bmm_wlast.r{row}"
+    for I, J, ldx in pu.wlast_shapes(row):
+        for layout in (pu.LAYOUTS if row else pu.LAYOUTS[:1]):
+            for family in pu.BMM_FAMILIES:
+                c = _wlast_case(I, J, ldx, layout, family)
+                for w in pu.WEIGHTS:
+                    for accumulate in ((0, 1) if row else (0,)):
+                        res = pu.check_wlast(be, c, w, row, accumulate, jsplit)
+                        assert (key + ".onehot" in res) == (family == "onehot" and not accumulate) and (key + ".dense_bits" in res) == (w == 1)
+                        _hold((jsplit, row, layout, I, J, ldx, family, w, accumulate), res)
+                        worst = max(worst, res[key])
+                        ran += 1
+    print(f"NRM_POOL_JSPLIT={jsplit} wlast_row={row}: {ran} launches, worst error / bound {worst:.3f}")
+    assert ran == len(pu.wlast_shapes(row)) * (4 if row else 1) * len(pu.BMM_FAMILIES) * len(pu.WEIGHTS)
+
+
+@pytest.mark.parametrize("D", pu.ROWDOT_WLAST_D)
+def test_pool_rowdot_wlast_per_element(lib, D):
+    """column H - 1 in the first, second and third trip of 64 history rows; wlast = 1 gives the bits of nrm_pool_rowdot"""
+    be, ran, worst = Native(), 0, 0.0
+    for B, T, H, d, ldg in pu.rowdot_wlast_shapes():
+        if d != D:
+            continue
+        for family in pu.ROWDOT_FAMILIES:
+            c = pu.make_rowdot(B, T, H, D, ldg, family)
+            for w in pu.WEIGHTS:
+                res = pu.check_rowdot_wlast(be, c, w, pu.ZERO_N[ran % 3])
+                assert ("pool_rowdot_wlast.onehot" in res) == (family == "onehot") and ("pool_rowdot_wlast.dense_bits" in res) == (w == 1)
+                _hold((B, T, H, D, ldg, family, w), res)
+                worst = max(worst, res["pool_rowdot_wlast"])
+                ran += 1
+    print(f"D={D}: {ran} launches, worst error / bound {worst:.3f}")
+    assert ran == len(pu.ROWDOT_WLAST_H) * len(pu.ROWDOT_WLAST_T) * 2 * len(pu.ROWDOT_FAMILIES) * len(pu.WEIGHTS)
 
 
 def test_zz_worst_ratios():

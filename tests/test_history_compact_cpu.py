@@ -145,6 +145,9 @@ def test_history_entries_validate_on_the_host(lib):
     assert pool(D=18) != 0 and lib.nrm_last_error().startswith(b"nrm_pool_bmm_hragged")
     assert pool(mc=6) != 0 and pool(km=10) != 0 and pool(Mt=1 << 27) != 0
     assert pool(B=0, N=0, mc=0, R=0, Mt=0, km=0) == 0
+    # no B <= 65535 refusal as in the dense pool entries: neither this entry nor nrm_pwattn_fwd_hragged in front of it has a grid dimension
+    # per impression (the launch is a 1-D grid of tasks and refuses a task count past 2^31 workgroups), so the values pass validation
+    assert pool(B=65536, R=0, Mt=0, km=0) == 0 and fwd(B=65536, R=0, km=0) == 0
 
     assert lib.nrm_history_len(None, 80, 1, 3, 5, f, None) != 0 and b"null" in lib.nrm_last_error()
     assert lib.nrm_history_len(f, 0, 1, 3, 5, f, None) != 0 and lib.nrm_last_error().startswith(b"nrm_history_len")
