@@ -8,6 +8,7 @@ launch), host float64 batches staged one ahead, per-impression AUC on the device
     python examples/train_synthetic.py --workload ref-default --compact-candidates --candidate-counts percentile    (section 5f)
     python examples/train_synthetic.py --workload ref-default --from-tables --compact-history --compact-candidates    (section 5g)
     python examples/train_synthetic.py --workload ref-default --from-tables --graph --batches 100     (section 5g: one graph replay per step)
+    python examples/train_synthetic.py --workload ref-default --from-tables --graph-grouped --compact-history --batches 100     (section 5i)
     python examples/train_synthetic.py --workload ref-default --from-tables --graph --validate     (section 5h: validation after every epoch)
 """
 import argparse
@@ -49,13 +50,20 @@ def main():
                     help="with --from-tables: after three eager steps every full batch is ONE replay of a captured step that assembles its own "
                          "batch at a device-side cursor (trainer.GraphedTableEpoch); the host reads the device once per epoch.  With --ckpt-dir "
                          "the per-step losses of every epoch are written as the reference writes them (train.py:93-94)")
+    ap.add_argument("--graph-grouped", action="store_true",
+                    help="with --from-tables and --compact-history and / or --compact-candidates: the captured epoch on compacted batches "
+                         "(trainer.GroupedTableEpoch, DESIGN.md section 5i) -- one group plan per epoch, every batch sorted by length on the host")
     ap.add_argument("--validate", action="store_true",
                     help="with --from-tables: a second set of synthetic records is kept on the device as validation tables and scored after "
                          "every epoch in batches of 80 (train.py:107-110), through one captured pass where --graph is given "
                          "(evaluation.GraphedTableScoring); the epoch line is then the reference's")
     args = ap.parse_args()
+    if args.graph_grouped:
+        if not (args.compact_history or args.compact_candidates):
+            raise SystemExit("--graph-grouped captures the COMPACTED step: give --compact-history and / or --compact-candidates")
+        args.graph = "grouped"
     if args.graph and not args.from_tables:
-        raise SystemExit("--graph captures the table-fed epoch: use it with --from-tables")
+        raise SystemExit("--graph / --graph-grouped capture the table-fed epoch: use them with --from-tables")
     if args.validate and not args.from_tables:
         raise SystemExit("--validate scores validation TABLES: use it with --from-tables")
     if not torch.cuda.is_available():

@@ -607,6 +607,27 @@ int nrm_assemble_form(int static_cols, int S);
 int nrm_assemble_batch_at(const nrm_assemble_tables* tables, const long* order, long n_order, const long* cursor, int B, int H, int T,
                           int flags, nrm_stream_t stream);
 
+/* The cursor form writing STRAIGHT INTO THE GROUPED ARENAS of a static group plan (additive, the ABI version is unchanged; DESIGN.md
+ * section 5i).  The batch arrives sorted by length (the host sorts every batch's slice of order): place b of the batch belongs to group g
+ * with bounds[g] <= b < bounds[g + 1], which keeps h_g[g] <= H history rows and t_g[g] <= T candidate slots per impression.
+ *   history row j < h_g[g] of place b  -> row hist_row_off[g] + (b - bounds[g]) * h_g[g] + j of tables->x_history, here [R, hc]
+ *   candidate slot s < t_g[g]          -> row cand_row_off[g] + (b - bounds[g]) * t_g[g] + s of tables->x_target [N, tc], tables->x_global
+ *                                         [N, 3], label_arena [N] float64 and row_weight [N] fp32 = T - t_g[g] + 1 on slot t_g[g] - 1, else 1
+ * -- bit for bit the rows nrm_history_gather_groups / nrm_candidate_gather_groups copy out of nrm_assemble_batch_at's dense tensors with the
+ * identity permutation; the dense x tensors are never written.  label [B, T], label_id, empty_num, user_id_out, impression_id and
+ * history_len are written as nrm_assemble_batch_at writes them.  A block of 16 history rows at or beyond h_g[g] exits at once.
+ * An impression with h_g[g] or more events where h_g[g] < H, or t_g[g] or more live candidates where t_g[g] < T, does not fit its group and
+ * sets misfit[0] = 1; its kept rows are written all the same.  The tables (int32, device) are clamped entry by entry, and an impression
+ * whose rows would not lie inside [0, R) / [0, N) writes none of them and sets the flag: nothing is written outside the arenas whatever the
+ * tables hold.  1 <= G <= 64, R, N >= 1.  Plain vector stores, no atomics. */
+typedef struct nrm_assemble_groups {
+    const int* bounds; const int* h_g; const int* hist_row_off; const int* t_g; const int* cand_row_off;
+    int G, R, N;
+    double* label_arena; float* row_weight; int* misfit;
+} nrm_assemble_groups;
+int nrm_assemble_groups_at(const nrm_assemble_tables* tables, const nrm_assemble_groups* groups, const long* order, long n_order,
+                           const long* cursor, int B, int H, int T, int flags, nrm_stream_t stream);
+
 /* ---- the record of a table-fed epoch kept on the device (additive)
  * One launch of ONE workgroup at the end of a step, in place of the epoch loop's per-step accumulations (reference train.py:77-94):
  *   sums[0] += (double)*loss * B           train.py:82 total_loss += loss.item() * B  (one rounded product, one rounded sum: no fma)

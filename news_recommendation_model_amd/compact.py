@@ -178,7 +178,7 @@ def _upload(plan, parts, device):
     """The group plans' ``upload``: the int32 host arrays ``parts`` (attribute names) of ``plan`` as device views of ONE buffer copied from
     pinned host memory (non-blocking).  Cached on the plan."""
     import torch
-    if plan.device_tables is not None and plan.device_tables["perm"].device == torch.device(device):
+    if plan.device_tables is not None and plan.device_tables[parts[0]].device == torch.device(device):
         return plan.device_tables
     arrays = [getattr(plan, name) for name in parts]
     host = torch.empty(sum(len(a) for a in arrays), dtype=torch.int32)
@@ -398,4 +398,147 @@ def full_height_history_plan(cand, H):
     plan.R, plan.saving, plan.dense = cand.B * H, 0.0, True
     plan.device_tables = None
     plan.cand = cand
+    return plan
+
+
+# ------------------------------------------------------------------------------------------------ training: one group plan per epoch
+#   A table-fed epoch knows every impression's history length and empty_num on the host before it starts, and the order
+# INSIDE a batch is free (loss, BatchNorm statistics and the tally do not depend on it).  Every full batch's slice of the epoch's order is
+# sorted by length on the host, and ONE plan is cut that every full batch fits: the height of sorted position i is the maximum over the
+# batches.  The plan is static and the batch arrives sorted (perm = identity), so the grouped step is one fixed sequence of launches.
+def _epoch_lengths(hist_len, empty_num, H, T):
+    L = np.clip(np.asarray(hist_len).reshape(-1).astype(np.int64), 0, int(H))
+    n = int(T) - np.clip(np.asarray(empty_num).reshape(-1).astype(np.int64), 0, int(T))
+    if L.shape != n.shape:
+        raise ValueError(f"epoch plan: {L.shape[0]} history lengths and {n.shape[0]} empty_num entries")
+    return L, n
+
+
+def sort_epoch_order(hist_len, empty_num, order, B, H, T, compact_history):
+    """``order`` with every full batch's slice [i * B, (i + 1) * B) stably sorted ascending by history length (``compact_history``) or by
+    ``n_b = T - empty_b``; the trailing partial batch is left as it is.  Batch membership does not change."""
+    L, n = _epoch_lengths(hist_len, empty_num, H, T)
+    order = np.array(order, dtype=np.int64).reshape(-1)
+    B = int(B)
+    nb = order.shape[0] // B if B > 0 else 0
+    if order.size and (order.min() < 0 or order.max() >= L.shape[0]):
+        raise IndexError(f"epoch plan: order holds an impression outside [0, {L.shape[0]})")
+    if nb:
+        full = order[:nb * B].reshape(nb, B)
+        key = (L if compact_history else n)[full]
+        order[:nb * B] = np.take_along_axis(full, np.argsort(key, axis=1, kind="stable"), axis=1).reshape(-1)
+    return order
+
+
+class EpochGroupPlan:
+    """One static group plan for all full batches of an epoch (host numpy; ``upload`` puts the tables on a device with ONE pinned copy).
+
+      B, H, T, G, quantum   impressions of a full batch, history rows, candidate columns, groups, the multiple a trimmed height is rounded to
+      n_batches             full batches the plan was cut for
+      order [N]             the epoch's order with every full batch sorted (``sort_epoch_order``)
+      hist                  ``HistoryGroupPlan`` with ``perm = inverse = arange(B)`` (the batch arrives sorted); ``hist.cand`` is ``cand``
+      cand                  None, or the ``CandidateGroupPlan`` along the same order and cuts (identity ``perm``, static ``expand``)
+      bounds [G + 1], H_g [G], hist_row_off [G + 1], T_g [G], cand_row_off [G + 1], expand [B * T]
+                            what the grouped assemble kernel and the step read (T_g = T, cand_row_off = bounds * T without ``cand``)
+      R, N                  rows of the history and of the candidate arena
+      saving                ``1 - R / (B H)``, with candidate groups ``1 - sum_g B_g T_g H_g / (B T H)``
+      dense                 nothing trimmed, no full batch, or ``saving`` below ``min_saving`` (None: ``MIN_SAVING``)
+    """
+
+    __slots__ = ("B", "H", "T", "G", "quantum", "n_batches", "order", "hist", "cand", "compact_history", "compact_candidates", "bounds", "H_g",
+                 "hist_row_off", "T_g", "cand_row_off", "expand", "R", "N", "saving", "dense", "device_tables")
+
+    def upload(self, device):
+        """-> dict of int32 device views (bounds, H_g, hist_row_off, T_g, cand_row_off, expand) of ONE buffer copied from pinned host memory."""
+        return _upload(self, ("bounds", "H_g", "hist_row_off", "T_g", "cand_row_off", "expand"), device)
+
+    def fits(self, hist_len, empty_num, order):
+        """Whether every full batch of ANOTHER epoch (its lengths and order; sorted here the way the plan's own order was) fits this plan:
+        every member of group g has ``L < H_g`` or ``H_g == H``, and ``n_b < T_g`` or ``T_g == T``."""
+        L, n = _epoch_lengths(hist_len, empty_num, self.H, self.T)
+        order = sort_epoch_order(L, self.T - n, order, self.B, self.H, self.T, self.compact_history)
+        nb = order.shape[0] // self.B
+        if nb == 0:
+            return True
+        full = order[:nb * self.B].reshape(nb, self.B)
+        size = np.diff(self.bounds)
+        h_pos, t_pos = np.repeat(self.H_g, size).astype(np.int64), np.repeat(self.T_g, size).astype(np.int64)
+        return bool((((L[full] < h_pos) | (h_pos == self.H)) & ((n[full] < t_pos) | (t_pos == self.T))).all())
+
+
+def plan_epoch_groups(hist_len, empty_num, order, B, H, T, compact_history, compact_candidates, max_groups=None, quantum=16, min_saving=None):
+    """``hist_len`` / ``empty_num`` [N]: every impression's history length and trailing padded candidates (host arrays:
+    ``tables.history_len`` / ``tables.empty_num_all``), ``order`` the epoch's impression order.  Sorts every full batch of ``order`` by
+    length and cuts ONE plan for all of them with the dynamic programme of ``plan_history_groups`` over the ENVELOPE: the position-wise
+    maximum over the full batches of ``min(H, q * ceil((L + 1) / q))`` -- or, with ``compact_candidates`` alone, of ``min(T, n_b + 1)``.
+    There is no joint planner: with both flags the cuts are the history's and every group additionally gets
+    ``T_g = min(T, 1 + max n_b)`` over its positions in all full batches."""
+    B, H, T, q = int(B), int(H), int(T), int(quantum)
+    max_groups = MAX_GROUPS if max_groups is None else int(max_groups)
+    if B < 1 or H < 1 or T < 1 or q < 1 or not 1 <= max_groups <= GROUPS_CAP:
+        raise ValueError(f"plan_epoch_groups: B={B} H={H} T={T} quantum={q} max_groups={max_groups} (B, H, T, quantum >= 1, 1 <= max_groups <= "
+                         f"{GROUPS_CAP})")
+    if not (compact_history or compact_candidates):
+        raise ValueError("plan_epoch_groups: neither compact_history nor compact_candidates")
+    if B * H >= 2 ** 31 or B * T >= 2 ** 31:
+        raise ValueError("plan_epoch_groups: more than 2^31 history or candidate rows")
+    L, n = _epoch_lengths(hist_len, empty_num, H, T)
+    order = sort_epoch_order(L, T - n, order, B, H, T, compact_history)
+    nb = order.shape[0] // B
+    full = order[:nb * B].reshape(nb, B)
+    height = np.minimum(H, q * ((L[full] + q) // q)).max(axis=0) if nb else np.full(B, H, dtype=np.int64)        # the envelope, per position
+    width = np.minimum(T, n[full] + 1).max(axis=0) if nb else np.full(B, T, dtype=np.int64)
+    if compact_history:                                          # rows sorted by L: the position-wise maximum is non-decreasing as well
+        bounds = np.array([0] + _cut_sorted(height, max_groups), dtype=np.int64)
+    else:
+        height = np.full(B, H, dtype=np.int64)
+        bounds = np.array([0] + _cut_sorted(width, max_groups), dtype=np.int64)
+    G = len(bounds) - 1
+    size = np.diff(bounds)
+    H_g = np.array([int(height[bounds[g + 1] - 1]) for g in range(G)], dtype=np.int64)
+    T_g = (np.array([int(width[bounds[g]:bounds[g + 1]].max()) for g in range(G)], dtype=np.int64) if compact_candidates
+           else np.full(G, T, dtype=np.int64))
+    with_cand = bool(compact_candidates and (T_g < T).any())
+    hist_row_off, cand_row_off = np.zeros(G + 1, dtype=np.int64), np.zeros(G + 1, dtype=np.int64)
+    np.cumsum(size * H_g, out=hist_row_off[1:])
+    np.cumsum(size * T_g, out=cand_row_off[1:])
+    ident = np.arange(B, dtype=np.int32)
+    hist = HistoryGroupPlan()
+    hist.B, hist.H, hist.G, hist.quantum = B, H, G, q if compact_history else 1
+    hist.hist_len = ((L[full].max(axis=0) if nb else np.zeros(B)) if compact_history else np.full(B, H)).astype(np.int32)
+    hist.perm, hist.inverse = ident, ident.copy()
+    hist.bounds, hist.H_g, hist.w_g, hist.row_off = bounds.astype(np.int32), H_g.astype(np.int32), (H - H_g + 1).astype(np.int32), hist_row_off.astype(np.int32)
+    hist.R = int(hist_row_off[G])
+    hist.saving = 1.0 - hist.R / (B * H)
+    hist.device_tables, hist.cand = None, None
+    group = np.repeat(np.arange(G, dtype=np.int64), size)        # group of sorted position b
+    first = cand_row_off[group] + (np.arange(B) - bounds[group]) * T_g[group]
+    expand = first[:, None] + np.minimum(np.arange(T, dtype=np.int64)[None, :], (T_g[group] - 1)[:, None])
+    saving = 1.0 - float((size * T_g * H_g).sum()) / (B * T * H)
+    cand = None
+    if with_cand:
+        cand = CandidateGroupPlan()
+        cand.B, cand.T, cand.G = B, T, G
+        cand.count = (n[full].max(axis=0) if nb else np.zeros(B)).astype(np.int32)
+        cand.perm, cand.inverse = ident, ident.copy()
+        cand.bounds, cand.T_g, cand.w_g, cand.row_off = bounds.astype(np.int32), T_g.astype(np.int32), (T - T_g + 1).astype(np.int32), cand_row_off.astype(np.int32)
+        cand.N = int(cand_row_off[G])
+        cand.expand = expand.reshape(-1).astype(np.int32)
+        cand.saving = saving
+        cand.device_tables = None
+        hist.cand = cand
+    floor = MIN_SAVING if min_saving is None else float(min_saving)
+    hist.dense = bool((H_g == H).all()) or hist.saving < floor
+    if cand is not None:
+        cand.dense = saving < floor
+    plan = EpochGroupPlan()
+    plan.B, plan.H, plan.T, plan.G, plan.quantum, plan.n_batches = B, H, T, G, q, nb
+    plan.order, plan.hist, plan.cand = order, hist, cand
+    plan.compact_history, plan.compact_candidates = bool(compact_history), bool(compact_candidates)
+    plan.bounds, plan.H_g, plan.hist_row_off = hist.bounds, hist.H_g, hist.row_off
+    plan.T_g, plan.cand_row_off, plan.expand = T_g.astype(np.int32), cand_row_off.astype(np.int32), expand.reshape(-1).astype(np.int32)
+    plan.R, plan.N = hist.R, int(cand_row_off[G])
+    plan.saving = saving
+    plan.dense = nb == 0 or bool((H_g == H).all() and (T_g == T).all()) or saving < floor
+    plan.device_tables = None
     return plan

@@ -1010,9 +1010,10 @@ int nrm_frontend_cat_grad(const void* x0, int nrows0, int xcols0, const float* d
 
 int nrm_assemble_form(int static_cols, int S) { return nrm::assemble_form(static_cols, S); }
 
-// nrm_assemble_batch (no cursor, n_order = B) and nrm_assemble_batch_at: one validation, one launch
+// nrm_assemble_batch (no cursor, n_order = B), nrm_assemble_batch_at and nrm_assemble_groups_at (groups: the plan whose arenas the x
+// pointers of the table struct are): one validation, one launch
 static int assemble_entry(const char* who, const nrm_assemble_tables* tables, const long* sel, long n_order, const long* cursor, bool at, int B,
-                          int H, int T, int flags, nrm_stream_t stream) {
+                          int H, int T, int flags, nrm_stream_t stream, const nrm_assemble_groups* groups = nullptr) {
     if (!tables) return fail(NRM_EINVAL, "%s: null table struct", who);
     const nrm_assemble_tables& t = *tables;
     if (B < 0 || H <= 0 || T <= 0 || (flags & ~NRM_ASSEMBLE_KEEP_TARGET_SLOT))
@@ -1038,7 +1039,16 @@ static int assemble_entry(const char* who, const nrm_assemble_tables* tables, co
         return fail(NRM_EINVAL, "%s: art_static, x_history and x_target must be 16-byte aligned", who);
     nrm::AssembleParams p;
     p.t = t; p.sel = sel; p.cursor = cursor; p.n_order = n_order; p.B = B; p.H = H; p.T = T; p.keep_target_slot = (flags & NRM_ASSEMBLE_KEEP_TARGET_SLOT) ? 1 : 0;
-    return check_hip(nrm::assemble_launch(p, (hipStream_t)stream), "assemble_batch");
+    if (!groups) return check_hip(nrm::assemble_launch(p, (hipStream_t)stream), "assemble_batch");
+    const nrm_assemble_groups& g = *groups;
+    if (g.G < 1 || g.G > nrm::HISTORY_GROUPS_MAX || g.R < 1 || g.N < 1 || (long)g.R > (long)B * H || (long)g.N > (long)B * T)
+        return fail(NRM_EINVAL, "%s: G=%d R=%d N=%d (1 <= G <= %d, 1 <= R <= B*H, 1 <= N <= B*T)", who, g.G, g.R, g.N, nrm::HISTORY_GROUPS_MAX);
+    if (!g.bounds || !g.h_g || !g.hist_row_off || !g.t_g || !g.cand_row_off || !g.label_arena || !g.row_weight || !g.misfit)
+        return fail(NRM_EINVAL, "%s: null pointer (group tables)", who);
+    nrm::AssembleGroupsParams q;
+    q.a = p; q.bounds = g.bounds; q.h_g = g.h_g; q.hist_row_off = g.hist_row_off; q.t_g = g.t_g; q.cand_row_off = g.cand_row_off;
+    q.label_arena = g.label_arena; q.row_weight = g.row_weight; q.misfit = g.misfit; q.G = g.G; q.R = g.R; q.N = g.N;
+    return check_hip(nrm::assemble_groups_launch(q, (hipStream_t)stream), "assemble_groups");
 }
 
 int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B, int H, int T, int flags, nrm_stream_t stream) {
@@ -1048,6 +1058,12 @@ int nrm_assemble_batch(const nrm_assemble_tables* tables, const long* sel, int B
 int nrm_assemble_batch_at(const nrm_assemble_tables* tables, const long* order, long n_order, const long* cursor, int B, int H, int T,
                           int flags, nrm_stream_t stream) {
     return assemble_entry("nrm_assemble_batch_at", tables, order, n_order, cursor, true, B, H, T, flags, stream);
+}
+
+int nrm_assemble_groups_at(const nrm_assemble_tables* tables, const nrm_assemble_groups* groups, const long* order, long n_order,
+                           const long* cursor, int B, int H, int T, int flags, nrm_stream_t stream) {
+    if (!groups) return fail(NRM_EINVAL, "nrm_assemble_groups_at: null group struct");
+    return assemble_entry("nrm_assemble_groups_at", tables, order, n_order, cursor, true, B, H, T, flags, stream, groups);
 }
 
 int nrm_epoch_tally(const float* loss, const float* auc, const int* top1, int B, long* cursor, double* sums, long* counts,

@@ -91,6 +91,7 @@ SIGNATURES = {
     "nrm_assemble_batch": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),       # the first: a HOST struct (AssembleTables), by pointer
     "nrm_assemble_form": (_c_i, [_c_i, _c_i]),
     "nrm_assemble_batch_at": (_c_i, [_c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),      # the first: the same HOST struct
+    "nrm_assemble_groups_at": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp]),      # the first two: HOST structs
     "nrm_epoch_tally": (_c_i, [_c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp]),
     "nrm_eval_tally": (_c_i, [_c_fp] * 6 + [_c_i] * 3 + [_c_fp, _c_l] + [_c_fp] * 5 + [_c_l, _c_fp]),
     "nrm_frontend_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,  _c_fp, _c_i, _c_i,  _c_fp, _c_fp, _c_i,
@@ -130,6 +131,13 @@ class AssembleTables(ctypes.Structure):
                 + [(n, ctypes.c_int) for n in ("S", "static_cols", "is_f64")]
                 + [(n, ctypes.c_void_p) for n in ("x_history", "x_target", "x_global", "label", "label_id", "empty_num", "user_id_out",
                                                   "impression_id", "history_len", "err")])
+
+
+class AssembleGroups(ctypes.Structure):
+    """nrm_assemble_groups of include/nrm_hotpath.h"""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("bounds", "h_g", "hist_row_off", "t_g", "cand_row_off")]
+                + [(n, ctypes.c_int) for n in ("G", "R", "N")]
+                + [(n, ctypes.c_void_p) for n in ("label_arena", "row_weight", "misfit")])
 
 
 _lib = None

@@ -2664,13 +2664,8 @@ def _assemble_outputs(like, ft, B, H, T, hc, tc):
             new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int32))
 
 
-def _assemble_launch(who, tables, sel, cursor, B, H, T, keep_target_slot, static_cols):
-    """assemble_batch (``cursor`` None: impression b is sel[b]) and assemble_batch_at (impression b is sel[cursor[0] + b]): one launch."""
-    _require_gpu(*tables, sel, cursor)
-    ft, _, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
-    outs = _assemble_outputs(sel, ft, B, H, T, hc, tc)
-    if B == 0:
-        return outs
+def _assemble_struct(who, tables, ft, static_cols, device):
+    """the input half of ``native.AssembleTables`` (the caller sets the output pointers), after the tables' sizes have been compared"""
     (art_static, art_global, art_pub, art_id, user_off, ev_art, ev_time, ev_read, ev_scroll, user_id, imp_user, imp_time, imp_off, imp_inview,
      imp_target, imp_id) = tables
     A, U, E, N, L = art_static.shape[0], user_id.shape[0], ev_art.shape[0], imp_user.shape[0], imp_inview.shape[0]
@@ -2684,9 +2679,20 @@ def _assemble_launch(who, tables, sel, cursor, B, H, T, keep_target_slot, static
         setattr(d, name, t.data_ptr())
     d.A, d.U, d.E, d.N, d.L = A, U, E, N, L
     d.S, d.static_cols, d.is_f64 = art_static.shape[1], static_cols, 1 if ft == torch.float64 else 0
+    d.err = index_error_flag(device).data_ptr()
+    return d
+
+
+def _assemble_launch(who, tables, sel, cursor, B, H, T, keep_target_slot, static_cols):
+    """assemble_batch (``cursor`` None: impression b is sel[b]) and assemble_batch_at (impression b is sel[cursor[0] + b]): one launch."""
+    _require_gpu(*tables, sel, cursor)
+    ft, _, hc, tc = _assemble_shapes(tables, sel, H, T, static_cols)
+    outs = _assemble_outputs(sel, ft, B, H, T, hc, tc)
+    if B == 0:
+        return outs
+    d = _assemble_struct(who, tables, ft, static_cols, sel.device)
     for name, t in zip(("x_history", "x_target", "x_global", "label", "label_id", "empty_num", "user_id_out", "impression_id", "history_len"), outs):
         setattr(d, name, t.data_ptr())
-    d.err = index_error_flag(sel.device).data_ptr()
     import ctypes
     tabs, flags = ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), 1 if keep_target_slot else 0
     if cursor is None:
@@ -2736,6 +2742,92 @@ def _assemble_batch_at_fake(tables, order, cursor, B, H, T, keep_target_slot, st
 assemble_batch_at = _op("assemble_batch_at", "(Tensor[] tables, Tensor order, Tensor cursor, int B, int H, int T, bool keep_target_slot, "
                         "int static_cols) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
                         _assemble_batch_at_impl, _assemble_batch_at_fake)
+
+
+# ---- the batch written straight into the grouped arenas of a static group plan
+_group_fit_flag = {}
+
+
+def group_fit_flag(device):
+    """int32 flag in pinned host memory, set to 1 by ``assemble_groups_at`` when an impression does not fit the group its place in the
+    (sorted) batch belongs to, or the plan's tables do not add up.  Same mechanics as ``index_error_flag``; one per device."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    key = str(device)
+    if key not in _group_fit_flag:
+        _group_fit_flag[key] = torch.zeros(1, dtype=torch.int32).pin_memory()
+    return _group_fit_flag[key]
+
+
+def check_group_fit(device="cuda"):
+    """Wait for the device, then turn a raised group-fit flag into a ValueError (and clear it)."""
+    device = torch.device(device)
+    flag = group_fit_flag(device)
+    torch.cuda.synchronize(device if device.index is not None else None)
+    if int(flag[0]):
+        flag.zero_()
+        raise ValueError("assemble_groups_at: an impression has more events or live candidates than the group of its place in the batch "
+                         "keeps (the batch is not sorted the way the plan was cut, or the plan is another epoch's), or the plan's tables do "
+                         "not add up; every step enqueued so far ran on the trimmed rows and HAS BEEN APPLIED")
+
+
+def _assemble_groups_check(order, cursor, B, H, T, bounds, H_g, hist_row_off, T_g, cand_row_off, R, N):
+    _assemble_at_check(order, cursor, B)
+    G = H_g.shape[0] if H_g.dim() == 1 else -1
+    tabs = (bounds, H_g, hist_row_off, T_g, cand_row_off)
+    if (not 1 <= G <= 64 or any(t.dtype != torch.int32 or not t.is_contiguous() for t in tabs) or tuple(bounds.shape) != (G + 1,)
+            or tuple(hist_row_off.shape) != (G + 1,) or tuple(T_g.shape) != (G,) or tuple(cand_row_off.shape) != (G + 1,)
+            or (B > 0 and not (1 <= R <= B * H and 1 <= N <= B * T))):
+        raise RuntimeError(f"assemble_groups_at: bounds {tuple(bounds.shape)}, H_g {tuple(H_g.shape)}, hist_row_off {tuple(hist_row_off.shape)}, T_g "
+                           f"{tuple(T_g.shape)}, cand_row_off {tuple(cand_row_off.shape)}, R={R}, N={N} for B={B}, H={H}, T={T} (contiguous int32 "
+                           "tables of 1 <= G <= 64 groups, 1 <= R <= B * H, 1 <= N <= B * T)")
+
+
+def _assemble_groups_outputs(like, ft, B, T, R, N, hc, tc):
+    new = lambda shape, dt: like.new_empty(shape, dtype=dt)      # noqa: E731
+    return (new((R, hc), ft), new((N, tc), ft), new((N, 3), ft), new((N,), torch.float64), new((N,), torch.float32), new((B, T), torch.float64),
+            new((B, T), torch.int64), new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int64), new((B,), torch.int32))
+
+
+def _assemble_groups_at_impl(tables, order, cursor, B, H, T, keep_target_slot, static_cols, bounds, H_g, hist_row_off, T_g, cand_row_off, R, N):
+    """``assemble_batch_at`` writing straight into the grouped arenas of a static plan (``compact.plan_epoch_groups``; the five tables are
+    int32 on the device) -> (history arena [R, hc], candidate arena [N, tc], x_global arena [N, 3] in the tables' floating type, label arena
+    [N] float64, row weight [N] fp32, label [B, T] float64, label_id [B, T], empty_num [B], user_id [B], impression_id [B] int64, history_len
+    [B] int32).  The arenas hold the bits ``history_gather_groups`` / ``candidate_gather_groups`` copy out of ``assemble_batch_at``'s dense
+    tensors with the identity permutation; an impression that does not fit its group raises ``group_fit_flag``.  Reads no host data."""
+    B, H, T, R, N = int(B), int(H), int(T), int(R), int(N)
+    _assemble_groups_check(order, cursor, B, H, T, bounds, H_g, hist_row_off, T_g, cand_row_off, R, N)
+    _require_gpu(*tables, order, cursor, bounds, H_g, hist_row_off, T_g, cand_row_off)
+    ft, _, hc, tc = _assemble_shapes(tables, order, H, T, static_cols)
+    outs = _assemble_groups_outputs(order, ft, B, T, R, N, hc, tc)
+    if B == 0:
+        return outs
+    d = _assemble_struct("assemble_groups_at", tables, ft, static_cols, order.device)
+    for name, t in zip(("x_history", "x_target", "x_global", None, None, "label", "label_id", "empty_num", "user_id_out", "impression_id",
+                        "history_len"), outs):
+        if name is not None:
+            setattr(d, name, t.data_ptr())
+    g = native.AssembleGroups()
+    g.bounds, g.h_g, g.hist_row_off, g.t_g, g.cand_row_off = (t.data_ptr() for t in (bounds, H_g, hist_row_off, T_g, cand_row_off))
+    g.G, g.R, g.N = H_g.shape[0], R, N
+    g.label_arena, g.row_weight, g.misfit = outs[3].data_ptr(), outs[4].data_ptr(), group_fit_flag(order.device).data_ptr()
+    import ctypes
+    native.call("nrm_assemble_groups_at", ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), ctypes.cast(ctypes.pointer(g), ctypes.c_void_p),
+                native.ptr(order), order.shape[0], native.ptr(cursor), B, H, T, 1 if keep_target_slot else 0, native.stream_ptr())
+    return outs
+
+
+def _assemble_groups_at_fake(tables, order, cursor, B, H, T, keep_target_slot, static_cols, bounds, H_g, hist_row_off, T_g, cand_row_off, R, N):
+    _assemble_groups_check(order, cursor, B, H, T, bounds, H_g, hist_row_off, T_g, cand_row_off, R, N)
+    ft, _, hc, tc = _assemble_shapes(tables, order, H, T, static_cols)
+    return _assemble_groups_outputs(order, ft, B, T, R, N, hc, tc)
+
+
+assemble_groups_at = _op("assemble_groups_at", "(Tensor[] tables, Tensor order, Tensor cursor, int B, int H, int T, bool keep_target_slot, "
+                         "int static_cols, Tensor bounds, Tensor H_g, Tensor hist_row_off, Tensor T_g, Tensor cand_row_off, int R, int N) -> "
+                         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+                         _assemble_groups_at_impl, _assemble_groups_at_fake)
 
 
 # ---- the record of a table-fed epoch on the device (DESIGN.md section 5g)
@@ -2969,4 +3061,4 @@ OPS = ("pwattn_fwd", "pwattn_bwd", "head_tail_fwd", "head_tail_bwd", "linear_fwd
        "attend_pool_grouped_fwd", "attend_pool_grouped_bwd", "history_gather_groups",
        "candidate_gather_groups", "batch_norm_stats_roww", "batch_norm_apply_roww",
        "batch_norm_bwd_roww", "gate_block_roww_fwd", "gate_block_roww_bwd", "softmax_bce_loss_grouped",
-       "assemble_batch", "assemble_batch_at", "epoch_tally", "eval_tally", "adam_step")
+       "assemble_batch", "assemble_batch_at", "assemble_groups_at", "epoch_tally", "eval_tally", "adam_step")

@@ -432,6 +432,28 @@ def assemble_batch_at(tables: ImpressionTables, order, cursor, B, H, T, keep_tar
     return dict(zip(BATCH_KEYS, out))
 
 
+GROUP_KEYS = ("x_history_arena", "x_target_arena", "x_global_arena", "label_arena", "row_weight", "label", "label_id", "empty_num", "user_id",
+              "impression_id", "history_len")
+
+
+def assemble_groups_at(tables: ImpressionTables, order, cursor, B, H, T, plan, keep_target_slot=True):
+    """``assemble_batch_at`` writing straight into the grouped arenas of ``plan`` (a ``compact.EpochGroupPlan``, or anything with its
+    ``upload``, ``R`` and ``N``): the ``B`` impressions ``order[cursor[0] : cursor[0] + B]`` must arrive sorted the way
+    the plan was cut (``plan.order``).  -> dict of ``GROUP_KEYS``: the history arena [R, hc], the candidate arenas [N, tc] / [N, 3] / label
+    [N] / row weight [N] -- the bits ``ops.history_gather_groups`` / ``ops.candidate_gather_groups`` give on the dense batch, which is never
+    written -- and the dense kernel's label [B, T], label_id, empty_num, user_id, impression_id and history_len.  An impression that does
+    not fit its group raises the device flag ``ops.check_group_fit`` reads.  No host data is read: the launch may be captured."""
+    from . import ops
+    if not tables.is_device:
+        raise RuntimeError("assemble_groups_at: the tables are host arrays; upload them once with tables.to('cuda') "
+                           "(the host statement of the same rows is assemble_host)")
+    tabs = plan.upload(order.device)
+    out = ops.assemble_groups_at([getattr(tables, name) for name in TABLE_FIELDS], order, cursor, int(B), int(H), int(T), bool(keep_target_slot),
+                                 int(tables.static_cols), tabs["bounds"], tabs["H_g"], tabs["hist_row_off"], tabs["T_g"], tabs["cand_row_off"],
+                                 int(plan.R), int(plan.N))
+    return dict(zip(GROUP_KEYS, out))
+
+
 class TableLoader:
     """Batches of a data set that lives on the device as ``ImpressionTables``: the epoch's permutation is drawn on the host (numpy, seeded),
     ``sel`` -- a few KB -- is uploaded per batch, and the batch is written by ``assemble_batch`` on the current stream.  Yields the device

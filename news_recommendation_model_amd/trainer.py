@@ -429,6 +429,31 @@ def _compact_forward(model, batch, alpha, max_groups):
     return loss, out_sorted.detach().index_select(0, tabs["inverse"])
 
 
+def _backward_and_step(loss, optimizer, reducer=None, defer_reductions=True):
+    """The backward half of a step (train.py:73-75): backward, the gradient collective, the optimizer step, zero_grad."""
+    if isinstance(optimizer, FlatAdam):
+        from . import ops
+        ops.begin_step()                              # (stream ordering of the two attentions' backward contractions: ops._chain)
+        # nobody reads a weight gradient between backward() and collect_grads(): the step's slab reductions (one per weight
+        # gradient) are recorded during backward and run as ONE launch when FlatAdam gathers the gradients.  A gradient that
+        # exists already would be accumulated into before its reduction ran: then (and on request) reductions run at once.
+        defer = defer_reductions and all(p.grad is None for p in optimizer.params)
+        seed = ops.unit_grad(loss) if loss.dim() == 0 and loss.dtype == torch.float32 else None     # (see ops.unit_grad)
+        if defer:
+            with ops.deferred_slab_reductions():
+                loss.backward(seed)
+        else:
+            loss.backward(seed)
+        optimizer.all_reduce_grads()
+        optimizer.step(zero_grad=True)                # Adam + zero_grad fused in one launch
+    else:
+        loss.backward()
+        if reducer is not None:
+            reducer.reduce()
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=False)
+
+
 def train_step(model, optimizer, batch, reducer: FlatGradReducer | None = None, alpha=0.95, defer_reductions=True,
                strict_ids=False, compact_history=False, max_groups=None, compact_candidates=False):
     """One step of train.py:69-75 on device-resident tensors; returns (loss, out) detached.  An out-of-range id of an EARLIER
@@ -472,27 +497,7 @@ def train_step(model, optimizer, batch, reducer: FlatGradReducer | None = None, 
     else:
         out = model(batch["x_history"], batch["x_target"], batch["x_global"])
         loss = model.loss(batch["user_id"], out, batch["label"], alpha)
-    if isinstance(optimizer, FlatAdam):
-        from . import ops
-        ops.begin_step()                              # (stream ordering of the two attentions' backward contractions: ops._chain)
-        # nobody reads a weight gradient between backward() and collect_grads(): the step's slab reductions (one per weight
-        # gradient) are recorded during backward and run as ONE launch when FlatAdam gathers the gradients.  A gradient that
-        # exists already would be accumulated into before its reduction ran: then (and on request) reductions run at once.
-        defer = defer_reductions and all(p.grad is None for p in optimizer.params)
-        seed = ops.unit_grad(loss) if loss.dim() == 0 and loss.dtype == torch.float32 else None     # (see ops.unit_grad)
-        if defer:
-            with ops.deferred_slab_reductions():
-                loss.backward(seed)
-        else:
-            loss.backward(seed)
-        optimizer.all_reduce_grads()
-        optimizer.step(zero_grad=True)                # Adam + zero_grad fused in one launch
-    else:
-        loss.backward()
-        if reducer is not None:
-            reducer.reduce()
-        optimizer.step()
-        optimizer.zero_grad(set_to_none=False)
+    _backward_and_step(loss, optimizer, reducer, defer_reductions)
     if watch is not None:
         watch.after_step()
     return loss.detach(), out.detach()
@@ -575,19 +580,20 @@ class GraphedTableEpoch:
             raise RuntimeError("GraphedTableEpoch(compact_candidates=True): the candidate groups are planned on the host for every batch; a "
                                "captured step replays one fixed sequence of launches.  Capture the dense step, or run the eager loop "
                                "(train_epochs_tables(graph=False))")
+        who = type(self).__name__
         if not isinstance(optimizer, FlatAdam):
-            raise TypeError("GraphedTableEpoch needs trainer.FlatAdam (its step counter lives on the device)")
+            raise TypeError(f"{who} needs trainer.FlatAdam (its step counter lives on the device)")
         from . import native, ops
         if native.kernel_events is not None:
             raise RuntimeError("per-kernel event timing cannot be recorded inside a graph capture")
         if dist.is_available() and dist.is_initialized():
-            raise RuntimeError("GraphedTableEpoch: a process group is initialised; sharding the tables' impressions over ranks is not built "
+            raise RuntimeError(f"{who}: a process group is initialised; sharding the tables' impressions over ranks is not built "
                                "(every rank would train the whole epoch).  Run it in a process without a group")
         if int(warmup) < 1:
-            raise ValueError(f"GraphedTableEpoch(warmup={warmup}): at least one eager step comes before the capture (a model that has never "
+            raise ValueError(f"{who}(warmup={warmup}): at least one eager step comes before the capture (a model that has never "
                              "run would do its lazy initialisation inside the capture)")
         if int(batch_size) < 1:
-            raise ValueError(f"GraphedTableEpoch(batch_size={batch_size})")
+            raise ValueError(f"{who}(batch_size={batch_size})")
         from .tables import TABLE_FIELDS
         dev = optimizer.flat_param.device
         self.model, self.optimizer = model, optimizer
@@ -597,7 +603,7 @@ class GraphedTableEpoch:
         self.alpha, self.warmup = float(alpha), int(warmup)
         self.N = self.tables.n_impressions
         if self.N < 1:
-            raise ValueError("GraphedTableEpoch: the tables hold no impression")
+            raise ValueError(f"{who}: the tables hold no impression")
         self.order = torch.zeros(self.N, dtype=torch.int64, device=dev)
         self._order_host = torch.zeros(self.N, dtype=torch.int64).pin_memory()
         # ONE buffer of 8-byte words, read once per epoch: cursor | sums [3] float64 | counts [2] | step log [log_cap, 2] float32
@@ -617,7 +623,7 @@ class GraphedTableEpoch:
         """``order``: this epoch's impression order (host, [N]); copied into the device buffer in place, state zeroed, rate re-read."""
         order = np.ascontiguousarray(order, dtype=np.int64)
         if order.shape != (self.N,):
-            raise ValueError(f"GraphedTableEpoch.begin_epoch: order {order.shape} for {self.N} impressions")
+            raise ValueError(f"{type(self).__name__}.begin_epoch: order {order.shape} for {self.N} impressions")
         self.model.train()
         self.lr = float(self.optimizer.param_groups[0]["lr"])
         self._order_host.copy_(torch.from_numpy(order))
@@ -650,7 +656,7 @@ class GraphedTableEpoch:
         left = self.N - self.steps_in_epoch * self.batch_size
         n = min(self.batch_size, left) if n is None else int(n)
         if n < 1 or n > min(left, self.batch_size):
-            raise RuntimeError(f"GraphedTableEpoch.step: {n} impressions asked for, {max(left, 0)} left in the epoch and at most {self.batch_size} "
+            raise RuntimeError(f"{type(self).__name__}.step: {n} impressions asked for, {max(left, 0)} left in the epoch and at most {self.batch_size} "
                                "in a step (begin_epoch starts the next epoch)")
         if n < self.batch_size or self._warm < self.warmup:
             self.batch, self.loss, self.out = self._step_ops(n)            # (train_step watches the index flag itself)
@@ -687,6 +693,100 @@ class GraphedTableEpoch:
         if self.N % self.batch_size and not drop_last:
             self.step()
         return self.end_epoch()
+
+
+class GroupedTableEpoch(GraphedTableEpoch):
+    """``GraphedTableEpoch`` on compacted batches: the captured step computes neither the trailing all-zero history
+    rows nor (``compact_candidates``) the padded candidates, the rows the eager ``train_step(compact_history=True, ...)`` drops with a plan
+    made on the host for every batch.
+
+    Here the host plans ONCE PER EPOCH.  The tables give every impression's history length and ``empty_num`` before the epoch starts, and
+    the order inside a batch is free, so ``begin_epoch`` sorts every full batch's slice of the order by length and cuts one static plan that
+    every full batch fits (``compact.plan_epoch_groups``: the height of sorted position i is the maximum over the batches).  The captured
+    step is ``assemble_groups_at`` -- the assemble kernel writing straight into the grouped arenas -- -> ``model.forward_grouped`` ->
+    ``model.loss_grouped`` (``model.loss`` without candidate groups) -> backward -> FlatAdam -> ``out`` [B, T] through the plan's static
+    ``expand`` -> ``row_auc`` -> ``epoch_tally``; ``out``, ``label`` and the step's batch are in the SORTED order of the batch.  The graph is
+    kept over epochs while the new epoch's batches fit the plan and rate and ``alpha`` are unchanged; else the epoch is planned again and the
+    step captured again after ``warmup`` eager steps on the new shapes (``captures`` counts, ``replans`` says how many were for a plan).
+    Warm-up steps run the same grouped ops eagerly, the trailing partial batch runs the dense eager step, and under a plan with nothing worth
+    dropping (``plan.dense``) every step is ``GraphedTableEpoch``'s.  The kernel checks every impression against its group: a misfit (a plan
+    that is not this order's) raises ValueError in ``end_epoch``, after the epoch's steps have been applied."""
+
+    def __init__(self, model, optimizer, tables, batch_size, H, T, keep_target_slot=True, alpha=0.95, warmup=3, compact_history=True,
+                 compact_candidates=False, max_groups=None, quantum=16, min_saving=None):
+        if not (compact_history or compact_candidates):
+            raise ValueError("GroupedTableEpoch: neither compact_history nor compact_candidates (the dense captured epoch is GraphedTableEpoch)")
+        if not (hasattr(model, "compact_history_applies") and model.compact_history_applies()):
+            raise RuntimeError("GroupedTableEpoch: the model does not take forward_grouped (an attention without the fused attention + pool "
+                               "node, a feature width that is no multiple of 4, a substituted invariant-interest model or a forward hook); "
+                               "capture the dense step (GraphedTableEpoch)")
+        if compact_candidates and not model.compact_candidates_applies():
+            raise RuntimeError("GroupedTableEpoch(compact_candidates=True): the model's BatchNorm or gate has no row-weight form (not the "
+                               "column kernels' nn.BatchNorm1d, or no exact-GELU gate MLP); use compact_history alone or capture the dense step")
+        super().__init__(model, optimizer, tables, batch_size, H, T, keep_target_slot=keep_target_slot, alpha=alpha, warmup=warmup)
+        from . import ops
+        self.compact_history, self.compact_candidates = bool(compact_history), bool(compact_candidates)
+        self.max_groups, self.quantum, self.min_saving = max_groups, int(quantum), min_saving
+        host = self.tables.host
+        self._hist_len = host.history_len(np.arange(self.N), self.H)          # what the producer knows, once
+        self._empty = host.empty_num_all(self.T, self.keep_target_slot)
+        ops.group_fit_flag(self.order.device)                                 # (pinned: allocated before any capture)
+        self.plan, self._plan_tabs, self.replans = None, None, 0
+
+    def begin_epoch(self, order):
+        """``order``: this epoch's impression order (host, [N]).  Every full batch's slice is sorted by length before the upload; the plan
+        and the graph are kept where the sorted batches fit them."""
+        from . import compact
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        if order.shape != (self.N,):
+            raise ValueError(f"GroupedTableEpoch.begin_epoch: order {order.shape} for {self.N} impressions")
+        args = (self._hist_len, self._empty, order, self.batch_size, self.H, self.T, self.compact_history)
+        if self.plan is not None and self.plan.fits(self._hist_len, self._empty, order):
+            order = compact.sort_epoch_order(*args)
+        else:
+            self.plan = compact.plan_epoch_groups(*args, self.compact_candidates, max_groups=self.max_groups, quantum=self.quantum,
+                                                  min_saving=self.min_saving)
+            order = self.plan.order
+            self._plan_tabs = None if self.plan.dense else self.plan.upload(self.order.device)      # uploaded before any capture
+            self.graph = self._static = None                                  # the old plan's launches
+            self._warm = 0                                                    # the new shapes run eagerly first
+            self.replans += 1
+        super().begin_epoch(order)
+
+    def _step_ops(self, n):
+        """a full batch under a plan worth having: the grouped step, the same ops eagerly and inside the capture; else the dense step"""
+        if n != self.batch_size or self.plan is None or self.plan.dense:
+            return super()._step_ops(n)
+        from . import ops
+        from . import tables as _tables
+        capturing = torch.cuda.is_current_stream_capturing()
+        watch = None if capturing else _index_watch(self.order.device)
+        if watch is not None:
+            watch.before_step()
+        plan, tabs, B, T = self.plan, self._plan_tabs, self.batch_size, self.T
+        batch = _tables.assemble_groups_at(self.tables, self.order, self.cursor, B, self.H, T, plan, self.keep_target_slot)
+        xh, xt, xg = batch["x_history_arena"], batch["x_target_arena"], batch["x_global_arena"]
+        if plan.cand is not None:
+            out_arena = self.model.forward_grouped(xh, xt, xg, plan.hist, row_weight=batch["row_weight"])
+            loss = self.model.loss_grouped(batch["user_id"], out_arena, batch["label_arena"], plan.cand, self.alpha)
+            out = out_arena.detach().index_select(0, tabs["expand"]).view(B, T)
+        else:                                                                 # every group keeps all T slots: the arenas ARE the sorted batch
+            out = self.model.forward_grouped(xh, xt.view(B, T, -1), xg.view(B, T, -1), plan.hist)
+            loss = self.model.loss(batch["user_id"], out, batch["label"], self.alpha)
+        _backward_and_step(loss, self.optimizer)
+        if watch is not None:
+            watch.after_step()
+        loss, out = loss.detach(), out.detach()
+        auc, top1 = ops.row_auc(out, batch["label"], None)
+        ops.epoch_tally(loss, auc, top1, self.cursor, self.sums, self.counts, self.step_log)
+        return batch, loss, out
+
+    def end_epoch(self):
+        """``GraphedTableEpoch.end_epoch``; an impression that did not fit its group in any step of the epoch raises ValueError here."""
+        from . import ops
+        rec = super().end_epoch()                            # (waits for the stream)
+        ops.check_group_fit(self.order.device)
+        return rec
 
 
 def shard_batch(batch, rank, world):
@@ -853,6 +953,9 @@ def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuf
     seed, the same impressions in the same order).  The record gains ``step_loss`` / ``step_auc`` (per step, from the device log) and
     ``top1_avg``; ``on_batch`` is refused (a call per step would need a synchronise per step), and so is everything a captured step
     cannot do (``GraphedTableEpoch``).
+    ``graph="grouped"`` (with ``compact_history`` and / or ``compact_candidates``): the captured epoch on compacted
+    batches, a ``GroupedTableEpoch`` -- one group plan per epoch instead of one per batch, every full batch sorted by length on the host;
+    the record is ``graph=True``'s.
     ``validation``: a second set of tables (labelled) -- after every epoch's checkpoint the model is validated over it in batches of
     ``validation_batch`` as reference train.py:107-110 does, the record gains ``val_auc``, ``val_top1``, ``val_mrr``, ``val_ndcg5`` and
     ``val_ndcg10``, and the model is put back into train mode.  ``validation_graph`` (None: as ``graph``): through one
@@ -870,12 +973,20 @@ def train_epochs_tables(model, optimizer, tables, epochs, batch_size, H, T, shuf
                                              runner=val_runner)
             model.train()
             rec.update({"val_" + k: v for k, v in got.items()})
+    grouped = isinstance(graph, str) and graph == "grouped"
+    if grouped and not (compact_history or compact_candidates):
+        raise ValueError("train_epochs_tables(graph='grouped') needs compact_history=True and / or compact_candidates=True: it is the captured "
+                         "epoch on compacted batches (the dense captured epoch is graph=True)")
     if graph:
         if on_batch is not None:
             raise RuntimeError("train_epochs_tables(graph=True, on_batch=...): a call per step would need a host synchronise per step, which is "
                                "what the captured epoch removes; the per-step figures are in the record as step_loss and step_auc")
-        runner = GraphedTableEpoch(model, optimizer, tables, batch_size, H, T, keep_target_slot=keep_target_slot, warmup=graph_warmup,
-                                   compact_history=compact_history, compact_candidates=compact_candidates)
+        if grouped:
+            runner = GroupedTableEpoch(model, optimizer, tables, batch_size, H, T, keep_target_slot=keep_target_slot, warmup=graph_warmup,
+                                       compact_history=compact_history, compact_candidates=compact_candidates, max_groups=max_groups)
+        else:
+            runner = GraphedTableEpoch(model, optimizer, tables, batch_size, H, T, keep_target_slot=keep_target_slot, warmup=graph_warmup,
+                                       compact_history=compact_history, compact_candidates=compact_candidates)
         loader = TableLoader(runner.tables, batch_size, H, T, shuffle=shuffle, seed=seed, keep_target_slot=keep_target_slot, device=device,
                              drop_last=drop_last)
         history = []
