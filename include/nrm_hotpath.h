@@ -161,7 +161,11 @@ int nrm_pwattn_bwd_dp_dtdh(const float* dz, const float* t, const float* h, cons
  *      projection w1 (models/user_invariant_interest_model.py:78) and the attention's side projections.
  * Weights are re-packed per call into the kernel's streaming layout (they change every optimizer step).
  * All activation matrices are row-major with a leading dimension that is a multiple of 4 floats and 16-byte
- * aligned rows; padding columns [ncols, ld) must hold finite values (the library writes zeros there).       */
+ * aligned rows.  Padding columns [ncols, ld): those of x (nrm_gemm_nt) and of A / B (nrm_gemm_tn) are never used and may hold
+ * anything, NaN included; those of m (NRM_EPI_MUL) and of the saved z (NRM_EPI_DGELU) are multiplied by an exact zero and must hold
+ * finite values.  The library writes zeros to the columns [N, pad) of y and of the z it stores, pad = min(ld, N rounded up to 16):
+ * +0.0, except that y takes the sign of the factor there (0 * m, 0 * gelu'(z)) under NRM_EPI_MUL and NRM_EPI_DGELU; columns
+ * from pad on are not touched.  Rows >= M are not touched.                                                    */
 #define NRM_EPI_BIAS 0   /* y = x W^T + bias                                                              */
 #define NRM_EPI_GELU 1   /* z = x W^T + bias (saved for backward), y = gelu(z)                            */
 #define NRM_EPI_DGELU 2  /* y = (x W^T) * gelu'(z)      (z = pre-activation saved by NRM_EPI_GELU)        */
@@ -202,6 +206,11 @@ int nrm_gemm_nt(const float* x, int ldx, int M, const float* packed, int N, int 
 /* C[i,j] = sum_r A[r,i] B[r,j]  (dW = dY^T X): writes nsplit TRANSPOSED partial slabs ws[s][j][ldws] and, if
  * colsum != NULL, colsum[s][i] = sum_r A[r,i] (the bias gradient); sum over s.  ldws % 4 == 0, ldws >= ncols_i */
 int nrm_gemm_tn_nsplit(int ncols_i, int ncols_j, int R, int mma);
+/* The whole plan of that launch (additive entry point, the ABI version is unchanged), without any device call and with NRM_TN_WAVES
+ * (read at every call) and NRM_TN_SHAPES (latched) applied as the launch applies them: returns nsplit, and through the non-NULL
+ * pointers the wave tile (*kt x *dt MFMA tiles of 16 columns of i / of j) and the rows of a split -- split s sums the rows
+ * [s * rows_per_split, min(R, (s + 1) * rows_per_split)) into slab s.  -1: bad arguments (a width or R <= 0, unknown mma). */
+int nrm_gemm_tn_plan(int ncols_i, int ncols_j, int R, int mma, int* kt, int* dt, int* rows_per_split);
 /* zero_out (optional, 16-byte aligned): zero_n floats there are set to 0 by the same launch -- the gradient buffer that
  * nrm_slab_reduce will then add the slabs to */
 int nrm_gemm_tn(const float* A, int lda, int ncols_i, const float* B, int ldb, int ncols_j, int R,

@@ -487,6 +487,15 @@ int nrm_gemm_tn_nsplit(int ncols_i, int ncols_j, int R, int mma) {
     return nrm::gemm_tn_plan(ncols_i, ncols_j, R, tn_waves(mma), mma).nsplit;
 }
 
+int nrm_gemm_tn_plan(int ncols_i, int ncols_j, int R, int mma, int* kt, int* dt, int* rows_per_split) {
+    if (ncols_i <= 0 || ncols_j <= 0 || R <= 0 || (mma != NRM_MMA_F32 && mma != NRM_MMA_BF16 && mma != NRM_MMA_BF16X3)) return -1;
+    const nrm::GemmTnPlan pl = nrm::gemm_tn_plan(ncols_i, ncols_j, R, tn_waves(mma), mma);
+    if (kt) *kt = pl.KT;
+    if (dt) *dt = pl.DT;
+    if (rows_per_split) *rows_per_split = pl.rps;
+    return pl.nsplit;
+}
+
 int nrm_gemm_tn(const float* A, int lda, int ncols_i, const float* B, int ldb, int ncols_j, int R,
                 float* ws, int ldws, float* colsum, float* zero_out, long zero_n, int mma, nrm_stream_t stream) {
     if (!A || !B || !ws) return fail(NRM_EINVAL, "nrm_gemm_tn: null pointer");

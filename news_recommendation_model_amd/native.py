@@ -50,6 +50,7 @@ SIGNATURES = {
     "nrm_bn_finalize": (_c_i, [_c_i, _c_fp, _c_fp, _c_fp, _c_i, _c_i, ctypes.c_float, ctypes.c_float, _c_fp]),
     "nrm_mul_bwd": (_c_i, [_c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_fp]),
     "nrm_gemm_tn_nsplit": (_c_i, [_c_i, _c_i, _c_i, _c_i]),
+    "nrm_gemm_tn_plan": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_fp]),
     "nrm_gemm_tn": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_i, _c_i, _c_fp, _c_i, _c_fp, _c_fp, _c_l, _c_i, _c_fp]),
     "nrm_gemm_pack_multi": (_c_i, [_c_fp, _c_i, _c_fp]),
     "nrm_slab_reduce_multi": (_c_i, [_c_fp, _c_i, _c_fp]),

@@ -4,6 +4,12 @@ for, runs the dense ops against float64 PyTorch and prints ONE JSON line {"which
 The gates are the parent's.
 
     python tests/dense_knob_worker.py planned_mt    (NRM_NT_SMALLM=0 NRM_NT_NARROW=0 NRM_TN_SHAPES=0)
+
+Child process of tests/test_gpu_dense_elements.py::test_gemm_nt_planned_forms_in_a_child_process as well: the four forms with several row
+tiles per wave, element by element against float64 (dense_elements_util.check_nt over the C ABI) at M around one and two workgroups; prints
+ONE JSON line {"which", "forms_ok", "expected", "ran", "ratios": {key: worst error / bound}}.
+
+    python tests/dense_knob_worker.py elements_planned_mt    (NRM_NT_SMALLM=0, NRM_NT_NARROW unset)
 """
 import json
 import os
@@ -77,8 +83,30 @@ def gemm_tn_case(out, R, ni, nj):
     return 2
 
 
+def elements_planned_mt(lib):
+    import dense_elements_util as du
+    from test_gpu_dense_elements import Native, run_nt
+    planned = lambda M, N: du.nt_form(M, N, small_m=False)          # noqa: E731
+    want = {4: (4, 4, 2, 1), 5: (5, 4, 2, 1), 8: (8, 3, 2, 1), 9: (9, 2, 3, 1)}
+    forms_ok = all(du.lib_nt_form(lib, M, N, K) == planned(M, N) == want[NT] for NT in du.MT_WIDTHS for M, K, N in du.mt_shapes(NT))
+    worst, ran, expected = {}, 0, 0
+
+    def hold(tag, res):
+        for k, v in res.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    be = Native()
+    for NT in du.MT_WIDTHS:
+        launches = du.nt_launches(du.mt_shapes(NT), families=("normal", "scaled", "onehot"))
+        expected += len(launches)
+        ran += run_nt(be, launches, planned, hold)
+    torch.cuda.synchronize()
+    print(json.dumps({"which": "elements_planned_mt", "forms_ok": bool(forms_ok), "expected": expected, "ran": ran, "ratios": worst}), flush=True)
+
+
 def main(which):
     lib = native.load()
+    if which == "elements_planned_mt":
+        return elements_planned_mt(lib)
     nt = lambda M, N, K: dfu.nt_form(lib, M, N, K)               # noqa: E731
     out, n = {}, 0
     if which == "planned_mt":

@@ -76,6 +76,10 @@ def test_gemm_tn_wave_tile_shapes(lib, R, ni, nj, shape):
     cands = [(4, 4), (5, 5), (2, 8), (8, 2), (5, 2), (2, 5)]
     costs = [t(ni, k) * t(nj, d) for k, d in cands]
     assert cands[costs.index(min(costs))] == shape
+    import ctypes
+    kt, dt = ctypes.c_int(0), ctypes.c_int(0)                       # ... and the launch's own plan says so (nrm_gemm_tn_plan)
+    assert native.load().nrm_gemm_tn_plan(ni, nj, R, 0, ctypes.byref(kt), ctypes.byref(dt), None) == native.load().nrm_gemm_tn_nsplit(ni, nj, R, 0)
+    assert (kt.value, dt.value) == shape
     c, cs = ops._gemm_tn(a, b, True)
     torch.cuda.synchronize()
     ref = a.double().t() @ b.double()
